@@ -13,7 +13,9 @@ the same per-GPU batch (weak scaling), one bucketed RCCL all-reduce of the gradi
 backward (maskunet_amd/dp.py), and -- like the reference under multi-GPU nn.DataParallel -- fresh attention key masks every step
 (`config.mask_mode` = "resample": randint + mu_compact_keys on the device).
 
-One JSON line on rank 0.
+One JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and prints the headline: `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (milliseconds of one timed step), with `n_gpus`, `steps`, `warmup` and `config`.  The blocks
+below take measurements or runs of their own and are filled only with --full (the --no-* switches trim a --full run):
   * `roofline`: the dominant kernel (the dK/dV sweep of self_attention6), duration measured live with HIP events on the launch
     stream during the timed steps.  `achieved`/`frac` count the matrix products the kernel EXECUTES (masked keys are skipped
     exactly, so they are not work); the SURVEY 8-d4 full-key-set convention is carried as `algorithmic_*`.
@@ -21,6 +23,10 @@ One JSON line on rank 0.
     200.7 MB forward, ~450 GF / 602 MB forward+backward at 128x128, c_out=150; computed analytically for other shapes).
   * `cpu_baseline`: the CPU oracle (oracle/maskunet_oracle.py == restatement of the reference's PyTorch CPU path) timed on this
     host's cores on configs[0] (B=4, fp32, train mode) -- a reported baseline, not the target.
+  * `parity_gate`, `clock`, `host_inclusive`, `parity_grade_path`: see the functions and the options below.
+
+--dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy (dump_outputs): the inputs (synth) and the
+weights (torch.manual_seed) are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -71,6 +77,43 @@ def synth(B, c_out, hw, seed, device, ignore_frac=0.0):
     ns = [(hw // 2) ** 2, (hw // 4) ** 2, (hw // 8) ** 2, (hw // 4) ** 2, (hw // 2) ** 2, hw ** 2]
     keeps = [torch.from_numpy(rng.integers(0, 2, (B, n)).astype(np.uint8)) for n in ns]
     return x.to(device), y.to(device), [k.to(device) for k in keeps]
+
+
+DUMP_CAP_OUT = 1 << 21       # --dump-outputs: elements written of one module output (8 MB in float32) ...
+DUMP_CAP_GRAD = 1 << 16      # ... and of one parameter gradient (174 gradients of UNet(3,150): 11 MB)
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, last):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, one DIR/<name>.npy per array:
+    `loss` (float64), the module output `out` (`out0`..`out2` for the 3-head model; none with --fused-loss, whose logits stay inside the
+    kernel) and `grad.<parameter name>` (float32: the gradients of loss * loss_scale as the step leaves them in p.grad; with N > 1 the
+    all-reduced ones).  An array with more elements than its cap is written as a fixed sample: the flattened array at the sorted flat
+    positions np.random.default_rng(crc32(name)).choice(numel, cap, replace=False) -- the same positions in every run of a shape.
+    Smaller arrays keep their shape.  Returns the bytes written (at most DUMP_MAX_BYTES)."""
+    import zlib
+    import numpy as np
+    arrays = {"loss": last["loss"]}
+    outs = last.get("outputs")
+    if isinstance(outs, (tuple, list)):
+        arrays.update({f"out{i}": o for i, o in enumerate(outs)})
+    elif outs is not None:
+        arrays["out"] = outs
+    arrays.update({f"grad.{n}": g for n, g in last["grads"] if g is not None})
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        cap = DUMP_CAP_OUT if name.startswith("out") else DUMP_CAP_GRAD
+        if t.numel() > cap:
+            pos = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(pos).to(t.device)]
+        a = (t.double() if name == "loss" else t.float()).cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_MAX_BYTES} bytes at {name}")
+        np.save(os.path.join(path, name + ".npy"), a)
+    return total
 
 
 def algorithmic_counts(c_out, hw, three_head=False, embed_dim=16):
@@ -421,8 +464,12 @@ def spawn_ranks(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=8)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=8, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=2, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline figure: parity_gate, "
+                    "roofline / step_roofline (HIP events inside the timed steps), clock, host_inclusive, parity_grade_path, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the loss, module output(s) and parameter gradients "
+                    "of the last timed step as DIR/<name>.npy (large arrays as a fixed seeded sample; rank 0)")
     ap.add_argument("--batch", type=int, default=64, help="per-GPU batch")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "fp32", "fp32x"],
                     help="fp16: fp16 storage / fp32 accumulate (the configs[1] line); fp32: exact-fp32 MFMA (the 1e-3 parity path); fp32x: fp32 "
@@ -430,12 +477,12 @@ def main():
     ap.add_argument("--c-out", type=int, default=150)
     ap.add_argument("--hw", type=int, default=128)
     ap.add_argument("--loss-scale", type=float, default=1024.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity-gate", action="store_true", help="skip the B=2 golden check that fills `parity_gate`")
-    ap.add_argument("--no-clock-probe", action="store_true", help="skip the MFMA-loop clock probe after the timed region")
-    ap.add_argument("--no-host-inclusive", action="store_true", help="skip `host_inclusive` (the step with the batch copied from pinned host "
-                    "memory every iteration, timed behind the timed region; N = 1 only)")
-    ap.add_argument("--no-fp32x-line", action="store_true", help="skip `parity_grade_path` (the same workload timed in the fp32x "
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip `cpu_baseline`")
+    ap.add_argument("--no-parity-gate", action="store_true", help="--full: skip the B=2 golden check that fills `parity_gate`")
+    ap.add_argument("--no-clock-probe", action="store_true", help="--full: skip the MFMA-loop clock probe after the timed region")
+    ap.add_argument("--no-host-inclusive", action="store_true", help="--full: skip `host_inclusive` (the step with the batch copied from "
+                    "pinned host memory every iteration, timed behind the timed region; N = 1 only)")
+    ap.add_argument("--no-fp32x-line", action="store_true", help="--full: skip `parity_grade_path` (the same workload timed in the fp32x "
                     "parity-grade mode behind the timed region; N = 1 and --dtype fp16 only)")
     ap.add_argument("--pg-steps", type=int, default=0, help="timed steps of `parity_grade_path` (default: max(10, --steps // 2); 2 warm-up steps)")
     ap.add_argument("--three-head", action="store_true")
@@ -450,6 +497,8 @@ def main():
                          "redrawn + re-compacted on the device every step (what the reference does under multi-GPU nn.DataParallel, whose "
                          "replicas are discarded each step, :373); auto = fixed at N = 1, resample at N > 1")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: start the N ranks ourselves (torch.distributed.run as a CHILD process, before anything in this
@@ -518,12 +567,17 @@ def main():
         # so the exchange does not overlap the backward) -- opt-in, for small per-GPU batches where the host enqueue is the bound
         graphed = maskunet_amd.GraphedStep(net, criterion, x, labels, loss_scale=scale)
 
-    def step():
+    def step(keep=None):
+        """One training step; `keep` (a dict, --dump-outputs on the last timed step) receives references to what the step hands its
+        caller -- loss, module output(s), gradients -- before zero_grad drops them: no copy, no synchronisation inside the step."""
         nonlocal graphed, fwd_events
+        out = None
         if graphed is not None:
             loss = graphed(x, labels)
             if opt is not None:
                 opt.step(grad_scale=scale)
+            if keep is not None:
+                keep.update(loss=loss, outputs=graphed.outputs, grads=[(n, p.grad) for n, p in model.named_parameters()])
             return loss
         if args.fused_loss and not args.three_head:
             if multi:
@@ -547,32 +601,38 @@ def main():
             net.finish_gradient_sync()
         if opt is not None:
             opt.step(grad_scale=scale)
+        if keep is not None:
+            keep.update(loss=loss, outputs=out, grads=[(n, p.grad) for n, p in model.named_parameters()])
         model.zero_grad(set_to_none=True)
         return loss
 
-    # which parity gate the timed dtype passes: the reference-generated B = 2 golden, once, outside the timed region
+    # which parity gate the timed dtype passes: the reference-generated B = 2 golden, once, outside the timed region (--full; under a
+    # forked RNG, so the timed steps draw the same dropout masks with and without it)
     gate = None
-    if rank == 0 and not args.no_parity_gate:
-        gate = parity_gate(args, dtype)
-        torch.cuda.synchronize()
+    if rank == 0 and args.full and not args.no_parity_gate:
+        with torch.random.fork_rng(devices=[dev]):
+            gate = parity_gate(args, dtype)
+            torch.cuda.synchronize()
 
     fwd_events = None
     for _ in range(args.warmup):
         step()
-    fwd_events = []          # forward-only time: events around net(x) on the current stream (every launch of the path is on it)
-    # HIP-event probe on the three sweeps of self_attention6 (N = hw*hw, C = 64): the dK/dV sweep (attn_bwd_dkv3_kernel) is the
-    # dominant kernel of the step, the forward and dQ sweeps are reported next to it (`roofline.kernels`)
-    N6 = args.hw * args.hw
-    _lib.PROBE = {"pred": attention_probe(args.hw), "events": []}
-    sampler = SmiSampler(dev) if rank == 0 else None            # hwmon power rails over the timed region (rank 0's GPU only)
+    sampler = None
+    if args.full:
+        fwd_events = []      # forward-only time: events around net(x) on the current stream (every launch of the path is on it)
+        # HIP-event probe on the three sweeps of self_attention6 (N = hw*hw, C = 64): the dK/dV sweep (attn_bwd_dkv3_kernel) is the
+        # dominant kernel of the step, the forward and dQ sweeps are reported next to it (`roofline.kernels`)
+        _lib.PROBE = {"pred": attention_probe(args.hw), "events": []}
+        sampler = SmiSampler(dev) if rank == 0 else None        # hwmon power rails over the timed region (rank 0's GPU only)
+    last = {} if args.dump_outputs and rank == 0 else None     # --dump-outputs: what the last timed step returns
     if multi:
         dist.barrier()
     torch.cuda.synchronize()
     if sampler is not None:
         sampler.__enter__()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(last if i == args.steps - 1 else None)
     if multi:
         dist.barrier()
     torch.cuda.synchronize()
@@ -581,12 +641,15 @@ def main():
         sampler.__exit__()
     probe = _lib.PROBE
     _lib.PROBE = None
+    if last is not None:
+        dump_outputs(args.dump_outputs, last)
+        last = None
     clk = None
-    if rank == 0 and not args.no_clock_probe:
+    if rank == 0 and args.full and not args.no_clock_probe:
         clk = clock_probe(dev)                                   # right behind the timed steps: the chip is still warm
     _lib.PROBE = probe
     graphed_mode = graphed is not None
-    if graphed is not None:                     # a replayed graph makes no Python calls to probe: time the kernel in two eager steps
+    if graphed is not None and args.full:       # a replayed graph makes no Python calls to probe: time the kernel in two eager steps
         graphed = None                          # after the timed region (on every rank: eager steps all-reduce)
         for _ in range(2):
             step()
@@ -596,7 +659,7 @@ def main():
     # per iteration, ade_semantic.py:394-395): pinned fp32 NCHW images + int64 labels copied on the launch stream inside every step.
     # A side figure (`host_inclusive`), never `value`.
     host_incl = None
-    if world == 1 and not args.no_host_inclusive and graphed_mode is False and not args.fused_loss:
+    if args.full and world == 1 and not args.no_host_inclusive and graphed_mode is False and not args.fused_loss:
         xh, lh = x.detach().cpu().pin_memory(), labels.detach().cpu().pin_memory()
         for _ in range(2):
             x.copy_(xh, non_blocking=True); labels.copy_(lh, non_blocking=True)
@@ -621,6 +684,19 @@ def main():
 
     if rank == 0:
         imgs = args.batch * world * args.steps
+        rec = {
+            "metric": "128x128 images/sec (fwd+bwd)", "value": round(imgs / elapsed, 3), "unit": "images/sec",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": {"fp16": "f16", "fp32": "f32", "fp32x": "f32 storage, split 16-bit matrix products (f32 accumulate)"}[args.dtype],
+            "data": "synthetic",
+            "config": {"workload": f"{DATASET_BY_COUT.get(args.c_out, 'custom')} shape {args.hw}x{args.hw}, c_out={args.c_out}, batch={args.batch}/GPU, "
+                                   f"{'3-head' if args.three_head else '1-head'} MaskAttn-UNet fwd+bwd, train mode",
+                       "global_batch": args.batch * world, "parallelism": f"dp{world}", "loss_scale": scale, "mask_mode": mask_mode,
+                       "loss": "fused NHWC CE kernel" if args.fused_loss else ("torch CE on module output" if args.torch_loss else
+                                                                                "maskunet_amd.CrossEntropyLoss on module output"), "optimizer_in_step": bool(opt), "hip_graph": bool(args.graph)},
+        }
+    if rank == 0 and args.full:
         # fraction of keys the kernel really multiplies (the rest are skipped, not computed): of the mask the last step ran with
         kept = float(model.self_attention6._keep.float().mean().item())
         peak = PEAK_MFMA_TFLOPS[args.dtype]
@@ -649,22 +725,12 @@ def main():
                          "fwd_mfma_frac_executed": round((cnt["conv_proj_flops"] + attn_exec) * nimg / t_fwd / (peak * 1e12), 4),
                          "fwd_note": "north_star target '>= 60 % of the fp16 HBM roofline for the fused forward': the fused forward is "
                                      "MFMA-bound (680 FLOP/B), so its HBM fraction is set by its matrix time"})
-        rec = {
-            "metric": "128x128 images/sec (fwd+bwd)", "value": round(imgs / elapsed, 3), "unit": "images/sec",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": {"fp16": "f16", "fp32": "f32", "fp32x": "f32 storage, split 16-bit matrix products (f32 accumulate)"}[args.dtype],
-            "data": "synthetic",
-            "config": {"workload": f"{DATASET_BY_COUT.get(args.c_out, 'custom')} shape {args.hw}x{args.hw}, c_out={args.c_out}, batch={args.batch}/GPU, "
-                                   f"{'3-head' if args.three_head else '1-head'} MaskAttn-UNet fwd+bwd, train mode",
-                       "global_batch": args.batch * world, "parallelism": f"dp{world}", "loss_scale": scale, "mask_mode": mask_mode,
-                       "loss": "fused NHWC CE kernel" if args.fused_loss else ("torch CE on module output" if args.torch_loss else
-                                                                                "maskunet_amd.CrossEntropyLoss on module output"), "optimizer_in_step": bool(opt), "hip_graph": bool(args.graph)},
+        rec.update({
             "roofline": roof,
             "step_roofline": step,
             "clock": dict(clk or {}, smi=sampler.summary()),
             "parity_gate": gate,
-        }
+        })
         if host_incl is not None:
             rec["host_inclusive"] = host_incl
         if clk and headline_cfg:
@@ -679,6 +745,7 @@ def main():
             rec["parity_grade_path"] = parity_grade_line(args, dev, args.pg_steps or max(10, args.steps // 2), 2, clk)
         if world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(args.c_out, args.hw)
+    if rank == 0:
         print(json.dumps(rec), flush=True)
     if multi:
         dist.destroy_process_group()

@@ -307,7 +307,7 @@ def test_bench_multi_rank_path_over_rccl_one_rank(graph):
     env.pop("MU_DIST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
-           "--batch", "8", "--no-cpu-baseline"] + (["--graph"] if graph else [])
+           "--batch", "8", "--full", "--no-cpu-baseline"] + (["--graph"] if graph else [])
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -342,10 +342,11 @@ def test_bench_refuses_world_size_that_disagrees_with_gpus():
 
 
 def test_bench_line_is_self_describing():
-    """The N = 1 line carries what a reader of BENCH alone needs: which parity gate the timed dtype passes (the reference-generated
+    """The N = 1 --full line carries what a reader of BENCH alone needs: which parity gate the timed dtype passes (the reference-generated
     B = 2 golden, run outside the timed region), the clock the chip holds under a dense MFMA load, and the roofline fraction at it."""
     import json
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "4", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "4", "--full",
+                        "--no-cpu-baseline"],
                        env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")},
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -363,6 +364,39 @@ def test_bench_line_is_self_describing():
     ks = rec["roofline"]["kernels"]
     assert set(ks) == {"fwd", "dq", "dkv"} and all(0 < k["frac"] < 1 and k["launches_timed"] == 2 for k in ks.values())
     assert "power_w" not in rec["clock"]["smi"] and "power_rails_w" in rec["clock"]["smi"]
+
+
+def test_bench_plain_line_is_lean_and_dumps_the_last_timed_step(tmp_path):
+    """Without --full the line holds the headline only, for exactly --steps timed steps; --dump-outputs writes the last timed step's
+    loss, output sample and every parameter gradient, and a second run with the same arguments writes the same arrays (seeded inputs
+    and weights)."""
+    import json
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    recs = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "4",
+                            "--dump-outputs", str(tmp_path / d)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        recs.append(json.loads(lines[0]))
+    rec = recs[0]
+    assert rec["metric"] == "128x128 images/sec (fwd+bwd)" and rec["unit"] == "images/sec" and rec["higher_is_better"] is True
+    assert rec["dtype"] == "f16" and rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+    assert abs(rec["value"] - 4 * 1e3 / rec["ms_per_step"]) <= 1e-3 * rec["value"]        # images/s and ms/step of the same steps
+    for k in ("roofline", "step_roofline", "clock", "parity_gate", "host_inclusive", "parity_grade_path", "cpu_baseline"):
+        assert k not in rec, k
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"loss.npy", "out.npy"} <= set(names) and sum(n.startswith("grad.") for n in names) >= 100      # of the 174 parameters: those with a gradient
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        total += a.nbytes
+        assert a.dtype == (np.float64 if n == "loss.npy" else np.float32) and a.shape == b.shape and np.isfinite(a).all(), n
+        assert np.abs(a - b).max() <= 1e-5 * max(np.abs(a).max(), 1e-30), n
+    assert np.load(tmp_path / "a" / "out.npy").shape == (1 << 21,) and total <= 64 * 10 ** 6
 
 
 def test_bench_gpus2_over_rccl_on_a_one_gpu_box_refuses_with_a_message():

@@ -224,6 +224,39 @@ def test_bench_sweep_roofline_arithmetic():
     assert bench.sweep_rooflines("fp16", events({"fwd": 2.0}), hw, B, kept, None) is None     # no dominant-kernel launch timed
 
 
+def test_bench_dump_outputs_names_dtypes_samples_and_budget(tmp_path):
+    """bench.dump_outputs (--dump-outputs): loss in float64, outputs and gradients in float32, one file per array; an array above its
+    cap becomes a sample of its own elements at the same positions every time, a smaller one is written whole in its shape; parameters
+    without a gradient are left out; the UNet(3,150) B = 64 case stays within 64 MB."""
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(0)
+    out = torch.randn(2, 150, 96, 96, generator=g)                  # 2.8 M elements > DUMP_CAP_OUT
+    w = torch.arange(256 * 256 * 9, dtype=torch.float32).reshape(256, 256, 3, 3)     # 590 k > DUMP_CAP_GRAD; value = flat position
+    bias = torch.randn(256, generator=g, dtype=torch.float64)
+    last = {"loss": torch.tensor(1.25), "outputs": out, "grads": [("c.weight", w), ("c.bias", bias), ("dead.weight", None)]}
+    nbytes = bench.dump_outputs(str(tmp_path / "a"), last)
+    bench.dump_outputs(str(tmp_path / "b"), last)
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["grad.c.bias.npy", "grad.c.weight.npy", "loss.npy", "out.npy"]
+    ld = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("loss", "out", "grad.c.weight", "grad.c.bias")}
+    assert ld["loss"].dtype == np.float64 and float(ld["loss"]) == 1.25
+    assert ld["out"].dtype == np.float32 and ld["out"].shape == (bench.DUMP_CAP_OUT,)
+    assert ld["grad.c.weight"].shape == (bench.DUMP_CAP_GRAD,) and ld["grad.c.bias"].dtype == np.float32
+    assert np.array_equal(ld["grad.c.bias"], bias.float().numpy())
+    assert np.isin(ld["out"], out.numpy().ravel()).all()
+    assert (np.diff(ld["grad.c.weight"]) > 0).all() and ld["grad.c.weight"][-1] < w.numel()     # distinct positions, in order
+    for n, a in ld.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{n}.npy")), n
+    assert nbytes == sum(a.nbytes for a in ld.values())
+    # three module outputs (the 3-head model) are out0..out2
+    bench.dump_outputs(str(tmp_path / "c"), {"loss": torch.tensor(0.5), "outputs": (out[:1], out[:1, :1], out[:1, :16]), "grads": []})
+    assert sorted(p.name for p in (tmp_path / "c").iterdir()) == ["loss.npy", "out0.npy", "out1.npy", "out2.npy"]
+    # budget of the flagship shape: UNet(3,150)'s gradients at their caps plus one [64, 150, 128, 128] output sample
+    m = maskunet_amd.UNet(3, 150)
+    worst = 8 + 4 * bench.DUMP_CAP_OUT + 4 * sum(min(p.numel(), bench.DUMP_CAP_GRAD) for p in m.parameters())
+    assert worst <= bench.DUMP_MAX_BYTES
+
+
 
 def test_conv_stats_rows_mirror_the_kernel_dispatch():
     """mu_conv_stats_rows is host logic: it names the number of BatchNorm-statistics rows the 3x3 forward kernel of a shape writes

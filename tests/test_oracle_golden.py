@@ -1,6 +1,7 @@
 """CPU: pin the oracle (oracle/maskunet_oracle.py) against golden vectors generated from the
 real reference by tests/golden/make_golden.py.  fp32 oracle vs fp32 reference: tolerance 2e-5
-absolute on O(1) values (the fp32-vs-fp64 noise floor of the path is 7e-6..1.9e-5)."""
+absolute on O(1) values (the fp32-vs-fp64 noise floor of the path is 7e-6..1.9e-5).  The whole-model cases run the
+oracle in fp64 at the same gates (_unet_case: near-tied max-pool windows)."""
 import glob
 import os
 
@@ -95,17 +96,65 @@ def test_upsample_matches_torch():
     _check(O.upsample_bilinear2x(x), ref.numpy(), tol=1e-6)
 
 
-def _unet_case(golden_dir, name, three_head):
+NEAR_TIE = 3e-6     # 2x2 max-pool windows whose two largest inputs lie within this of the largest (relative): the fp32 noise of the
+                    # path at the pool inputs is 4e-7..2.2e-6 of their maximum, so an fp32 run may route such a window either way
+
+
+def _tie_pool(flip, seen):
+    """F.max_pool2d(x, 2) as the oracle calls it, with the same value and gradient routing (the window's maximum), that numbers its
+    near-tied windows in call order into `seen` and routes the ones whose number is in `flip` to the runner-up instead."""
+    def pool(x, kernel_size):
+        assert kernel_size == 2
+        w = x.unfold(2, 2, 2).unfold(3, 2, 2)
+        w = w.reshape(*w.shape[:4], 4)
+        top = w.detach().topk(2, dim=-1)
+        idx = top.indices[..., :1].clone()
+        near = (top.values[..., 0] - top.values[..., 1] <= NEAR_TIE * top.values[..., 0].abs()).nonzero().tolist()
+        for pos in near:
+            if len(seen) in flip:
+                idx[tuple(pos)] = top.indices[tuple(pos)][1]
+            seen.append(pos)
+        return w.gather(-1, idx).squeeze(-1)
+    return pool
+
+
+def _unet_case(golden_dir, name, three_head, monkeypatch):
+    """The whole model in fp64 against the fp32 reference, at the fp32 gates.  A max-pool window whose two largest inputs lie a few
+    fp32 ulps apart (unet1_c150_b2_train, pool 1: 9.7e-7 relative) sends its gradient to either input depending on how the host's fp32
+    conv / BatchNorm kernels round, and that moves every gradient upstream of it.  So the oracle runs in fp64, the same on any host, and
+    the windows within NEAR_TIE of a tie are the only freedom: the golden must be met with the exact routing or with one or two of those
+    windows routed to the runner-up, as the reference's own fp32 run may have done (unet3_c19_b2_train: one)."""
+    import itertools
     rec = _load(golden_dir, name)
+    seen = []
+    monkeypatch.setattr(O.F, "max_pool2d", _tie_pool((), seen))
+    try:
+        _unet_attempt(rec, three_head)
+        return
+    except AssertionError as e:
+        first = e
+    near = len(seen)
+    for flip in itertools.chain(itertools.combinations(range(near), 1), itertools.combinations(range(near), 2)):
+        monkeypatch.setattr(O.F, "max_pool2d", _tie_pool(set(flip), []))
+        try:
+            _unet_attempt(rec, three_head)
+            return
+        except AssertionError:
+            pass
+    raise AssertionError(f"no routing of the {near} near-tied pool windows meets the golden; exact routing: {first}")
+
+
+def _unet_attempt(rec, three_head):
     B, c_out, seed = int(rec["B"]), int(rec["c_out"]), int(rec["seed"])
     training = bool(rec["training"])
     shapes = O.unet_state_shapes(3, c_out, three_head)
-    p = O.make_params(shapes, seed)
+    p = {k: v.double() if v.dtype.is_floating_point else v for k, v in O.make_params(shapes, seed).items()}
     for k, v in p.items():
         if v.dtype.is_floating_point and "running" not in k:
             v.requires_grad_(training)
     keeps = O.make_keeps(seed + 1, B)
     x, labels = O.make_inputs(seed + 2, B, c_out, ignore_frac=0.1 if three_head else 0.0)
+    x = x.double()
     ns = {}
     out = O.unet_forward(p, x, keeps, training=training, new_stats=ns, three_head=three_head)
     outs = out if three_head else (out,)
@@ -139,21 +188,23 @@ def _unet_case(golden_dir, name, three_head):
     _check(p["initial_conv.conv_block.0.weight"].grad, rec["g_slice/initial_conv.conv_block.0.weight"], tol=1e-4)
 
 
-def test_unet1_eval(golden_dir):
-    _unet_case(golden_dir, "unet1_c150_b2_eval", False)
 
 
-def test_unet1_train(golden_dir):
-    _unet_case(golden_dir, "unet1_c150_b2_train", False)
+def test_unet1_eval(golden_dir, monkeypatch):
+    _unet_case(golden_dir, "unet1_c150_b2_eval", False, monkeypatch)
 
 
-def test_unet3_train(golden_dir):
-    _unet_case(golden_dir, "unet3_c19_b2_train", True)
+def test_unet1_train(golden_dir, monkeypatch):
+    _unet_case(golden_dir, "unet1_c150_b2_train", False, monkeypatch)
 
 
-def test_unet1_c133_train(golden_dir):
+def test_unet3_train(golden_dir, monkeypatch):
+    _unet_case(golden_dir, "unet3_c19_b2_train", True, monkeypatch)
+
+
+def test_unet1_c133_train(golden_dir, monkeypatch):
     """BASELINE configs[2] (COCO panoptic, c_out = 133): vectors from coco_panoptic.py's own UNet class (:279,472)."""
-    _unet_case(golden_dir, "unet1_c133_b2_train", False)
+    _unet_case(golden_dir, "unet1_c133_b2_train", False, monkeypatch)
 
 
 @pytest.mark.parametrize("name", ["miou_dense", "miou_absent_classes", "miou_ties_150"])

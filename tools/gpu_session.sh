@@ -16,7 +16,7 @@ for w in $WHAT; do
       timeout 3000 python -m pytest tests -m gpu -q --timeout 1500 -p no:cacheprovider > $OUT/${TAG}_pytest.log 2>&1
       echo "pytest rc=$?"; tail -5 $OUT/${TAG}_pytest.log ;;
     bench)
-      timeout 900 python bench.py $MU_SESSION_FLAGS --steps 20 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+      timeout 900 python bench.py --full $MU_SESSION_FLAGS --steps 20 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
       echo "bench rc=$?"; cat $OUT/${TAG}_bench.json ;;
     prof)
       cd /tmp

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 cd $ROOT
 timeout 1500 python -m pytest tests/test_gpu_kernels.py tests/test_gpu_modules.py -m gpu -q --timeout 1200 -p no:cacheprovider -k "fp32x or conv" > $OUT/${TAG}_pytest.log 2>&1
 echo "pytest rc=$?"; tail -4 $OUT/${TAG}_pytest.log
-timeout 600 python bench.py --dtype fp32x --steps 10 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_bench_fp32x.json 2> $OUT/${TAG}_bench_fp32x.err
+timeout 600 python bench.py --full --dtype fp32x --steps 10 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_bench_fp32x.json 2> $OUT/${TAG}_bench_fp32x.err
 echo "bench rc=$?"; cut -c1-400 $OUT/${TAG}_bench_fp32x.json
 cd /tmp
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_fp32x -o a -- python3 $ROOT/bench.py --dtype fp32x --no-cpu-baseline --no-parity-gate --no-clock-probe --no-fp32x-line --no-host-inclusive --steps 6 --warmup 2 > $OUT/${TAG}_prof_fp32x.log 2>&1
