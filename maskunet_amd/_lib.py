@@ -234,8 +234,8 @@ _workspaces = {}
 
 def workspace(nbytes: int, device) -> torch.Tensor:
     """Grow-only scratch buffer per (device, current stream).  Kernels that use it are stream-ordered, and every consumer finishes
-    with it before the next launch on the same stream touches it; work on another stream (side-stream weight gradients, a
-    graph-capture stream) gets a buffer of its own."""
+    with it before the next launch on the same stream touches it; work on another stream (a graph-capture stream) gets a buffer
+    of its own."""
     key = (device.type, device.index, stream())
     ws = _workspaces.get(key)
     if ws is None or ws.numel() < nbytes:

@@ -597,9 +597,6 @@ __global__ __launch_bounds__(256, SB ? MU_NT2_SB_OCC : MU_NT2_OCC) void conv_nt2
 #ifndef MU_NT3_STATS
 #define MU_NT3_STATS 1          // BatchNorm-statistics epilogue of the halo-tile kernel (fp16 and fp32x training launches)
 #endif
-#ifndef MU_XF_NT3_RING8
-#define MU_XF_NT3_RING8 0       // measured: 14.45 vs 14.5 ms/step over the 51 launches (session r04s) -- neutral, the 4-wave two-block form stays
-#endif
 // Per-channel (sum, sum of squares) of a wave's staged 64-pixel x 64-channel output tile, taken from the SAME fp16-rounded
 // values that were just stored (what BatchNorm will read): lane = (pixel sub-index lane>>3, 8-channel group q), 8 pixels per lane,
 // then the eight lanes of a channel group are folded with xor-shuffles and lanes 0-7 write 8 channels x {sum, sumsq} each.
@@ -630,7 +627,7 @@ __device__ __forceinline__ void tile_stats_store(float (&ssum)[8], float (&ssq)[
 
 // HL: see conv_nt_kernel -- here the lo / hi passes of one input chunk follow each other (chunk instance c = 2 * chunk + {lo, hi}), so the
 // halo of a chunk is staged ONCE for both (the odd instance stages the next chunk's halo, the even one stages nothing).
-template <typename T, int TM, int TN, int WR, int NWV, bool RINGP, bool FEPI, int HL = 0>
+template <typename T, int TM, int TN, int WR, bool RINGP, bool FEPI, int HL = 0>
 __device__ __forceinline__ void conv_nt3_body(const T* __restrict__ x, const T* __restrict__ w, const float* __restrict__ bias,
                                               T* __restrict__ y, int B, int H, int W, int Cin, int Cout, long x_ld, long y_ld,
                                               const float* __restrict__ scale, const T* __restrict__ res, int act,
@@ -642,6 +639,7 @@ __device__ __forceinline__ void conv_nt3_body(const T* __restrict__ x, const T* 
     using M_ = Mma<T>;
     using Frag = typename M_::Frag;
     constexpr int VN = M_::VN, KC = 8 * VN;
+    constexpr int NWV = 4;
     constexpr int WC = NWV / WR;
     constexpr int BCO = WR * TM * 16;
     constexpr int TH = WC * TN, TW = 16, HW_ = TW + 2;      // spatial tile TH x 16, halo row width 18
@@ -656,8 +654,7 @@ __device__ __forceinline__ void conv_nt3_body(const T* __restrict__ x, const T* 
     // parked 48 %, MFMA pipe 26 % busy).  Exactly PA + 1 DMAs per wave per tap (dummies to a dump page keep the counts uniform).
     // In-process A/B: 128 -> 64 @128^2 0.226 -> 0.203 ms; with a single 64-channel chunk (9 taps per tile) the longer prologue
     // costs more than the waits it removes (64 -> 64 @128^2 0.110 -> 0.116 ms), so the launcher picks RINGP for Cin >= 128 only.
-    // (fp32x, MU_XF_NT3_RING8: the same ring on 8-wave blocks with 128 output channels x 16 x 16 pixels -- one block per CU, two waves per SIMD)
-    constexpr bool RING = RINGP && MU_NT3_RING && ((sizeof(T) == 2 && BCO == 64 && NWV == 4) || (mu_is_split<T>::value && BCO == 128 && NWV == 8));
+    constexpr bool RING = RINGP && MU_NT3_RING && sizeof(T) == 2 && BCO == 64;
     constexpr int NWS = RING ? 3 : 2;
 
     __shared__ __attribute__((aligned(16))) char lds[2 * HBYTES + NWS * WBYTES + (RING ? 1024 : 0)];
@@ -945,202 +942,22 @@ __device__ __forceinline__ void conv_nt3_body(const T* __restrict__ x, const T* 
 }
 
 
-template <typename T, int TM, int TN, int WR, int NWV = 4, bool RINGP = false>
-__global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void conv_nt3_kernel(const T* __restrict__ x, const T* __restrict__ w, const float* __restrict__ bias,
-                                                       T* __restrict__ y, int B, int H, int W, int Cin, int Cout, long x_ld, long y_ld,
-                                                       float* __restrict__ stat_part = nullptr) {
-    conv_nt3_body<T, TM, TN, WR, NWV, RINGP, false>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, nullptr, nullptr, 0, stat_part);
+template <typename T, int TM, int TN, int WR, bool RINGP = false>
+__global__ __launch_bounds__(256, 2) void conv_nt3_kernel(const T* __restrict__ x, const T* __restrict__ w, const float* __restrict__ bias,
+                                                          T* __restrict__ y, int B, int H, int W, int Cin, int Cout, long x_ld, long y_ld,
+                                                          float* __restrict__ stat_part = nullptr) {
+    conv_nt3_body<T, TM, TN, WR, RINGP, false>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, nullptr, nullptr, 0, stat_part);
 }
 template <int TM, int TN, int WR, bool RINGP = false, int HL = 2>
 __global__ __launch_bounds__(256, 2) void conv_nt3hl_kernel(const h16* __restrict__ dy, const h16* __restrict__ w, float* __restrict__ dx, int B, int H,
                                                             int W, int Cin, int Cout, long x_ld, long y_ld, const float* __restrict__ oscale) {
-    conv_nt3_body<h16, TM, TN, WR, 4, RINGP, false, HL>(dy, w, nullptr, nullptr, B, H, W, Cin, Cout, x_ld, y_ld, nullptr, nullptr, 0, nullptr, dx, oscale);
+    conv_nt3_body<h16, TM, TN, WR, RINGP, false, HL>(dy, w, nullptr, nullptr, B, H, W, Cin, Cout, x_ld, y_ld, nullptr, nullptr, 0, nullptr, dx, oscale);
 }
 template <typename T, int TM, int TN, int WR>
 __global__ __launch_bounds__(256, 2) void conv_nt3f_kernel(const T* __restrict__ x, const T* __restrict__ w, const float* __restrict__ bias,
                                                            T* __restrict__ y, int B, int H, int W, int Cin, int Cout, long x_ld, long y_ld,
                                                            const float* __restrict__ scale, const T* __restrict__ res, int act) {
-    conv_nt3_body<T, TM, TN, WR, 4, false, true>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
-}
-
-// ------------------------------------------------------------------------------------------
-// v3p: persistent form of the halo-tile kernel for layers with short K loops (Cin <= 256: 18-36 tap steps per tile).
-// A block keeps its output-channel slice and walks spatial tiles (stride gridDim.x); the weight/halo DMA pipeline
-// runs ACROSS tile boundaries (the next tile's first weight tile and halo are in flight during the current tile's
-// last tap steps and epilogue), which removes the per-tile fill/drain bubble that cost v3 ~30 % on the 128-channel
-// layers (760 TF/s at 18 steps vs 1050 TF/s at 72 steps).
-// ------------------------------------------------------------------------------------------
-template <typename T, int TM, int TN, int WR>
-__global__ __launch_bounds__(256, 2) void conv_nt3p_kernel(const T* __restrict__ x, const T* __restrict__ w, const float* __restrict__ bias,
-                                                        T* __restrict__ y, int B, int H, int W, int Cin, int Cout, long x_ld, long y_ld) {
-    using M_ = Mma<T>;
-    using Frag = typename M_::Frag;
-    constexpr int NWV = 4;
-    constexpr int VN = M_::VN, KC = 8 * VN;
-    constexpr int WC = NWV / WR;
-    constexpr int BCO = WR * TM * 16;
-    constexpr int TH = WC * TN, TW = 16, HW_ = TW + 2;
-    constexpr int HROWS = (TH + 2) * HW_;
-    constexpr int HINST = (HROWS + 7) / 8;
-    constexpr int HPW = (HINST + NWV - 1) / NWV;
-    static_assert(HPW <= 9, "halo does not fit the 9 tap steps");
-    constexpr int PA = BCO / (8 * NWV);
-    constexpr int HBYTES = HINST * 1024, WBYTES = BCO * 128;
-
-    __shared__ __attribute__((aligned(16))) char lds[2 * HBYTES + 2 * WBYTES];
-    char* Hs = lds;
-    char* Ws = lds + 2 * HBYTES;
-
-    const int tiles_w = W / TW, tiles_h = H / TH;
-    const int ntile = B * tiles_h * tiles_w;
-    const int co0 = blockIdx.y * BCO;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wr = wave / WC, wc = wave % WC;
-    const int r16 = lane & 15, g = lane >> 4;
-    const int srow = lane >> 3, sch = lane & 7;
-    const int kchunks = Cin / KC;
-
-    int wl[PA];
-#pragma unroll
-    for (int i = 0; i < PA; ++i) {
-        const int row = (i * NWV + wave) * 8 + srow;
-        wl[i] = (co0 + row) * Cin + (sch ^ (row & 7)) * VN;
-    }
-    int aoff[2], boff[3][2];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-        aoff[kk] = (wr * TM * 16 + r16) * 128 + (((kk * 4 + g) ^ (r16 & 7)) << 4);
-#pragma unroll
-        for (int dw = 0; dw < 3; ++dw) boff[dw][kk] = (wc * TN * HW_ + r16 + dw) * 128 + (((kk * 4 + g) ^ ((r16 + dw) & 7)) << 4);
-    }
-
-    // halo source offsets of one tile (relative to x), -1 for the zero ring
-    auto halo_offsets = [&](int tl, long (&hl)[HPW]) {
-        const int tw_ = tl % tiles_w, th_ = (tl / tiles_w) % tiles_h, bimg = tl / (tiles_w * tiles_h);
-        const int h0 = th_ * TH, w0 = tw_ * TW;
-#pragma unroll
-        for (int k = 0; k < HPW; ++k) {
-            const int hr = (k * NWV + wave) * 8 + srow;
-            const int hy = hr / HW_, hx = hr - hy * HW_;
-            const int hh = h0 - 1 + hy, ww = w0 - 1 + hx;
-            const bool ok = (k * NWV + wave) < HINST && hr < HROWS && hh >= 0 && hh < H && ww >= 0 && ww < W;
-            hl[k] = ok ? (((long)bimg * H + hh) * W + ww) * x_ld + (sch ^ (hx & 7)) * VN : -1;
-        }
-    };
-    auto stage_w = [&](int tap, int ci0, int buf) {
-        const T* wb = w + (long)tap * Cout * Cin + ci0;
-        char* Wb = Ws + buf * WBYTES;
-#pragma unroll
-        for (int i = 0; i < PA; ++i) glds16(wb + wl[i], Wb + (i * NWV + wave) * 1024);
-    };
-    auto stage_h = [&](long off, int k, int ci0, int buf) {
-        const void* src = off >= 0 ? (const void*)(x + off + ci0) : (const void*)mu_zero_page;
-        glds16(src, Hs + buf * HBYTES + (k * NWV + wave) * 1024);
-    };
-
-    f32x4 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    int tl = blockIdx.x;
-    if (tl >= ntile) return;
-    long hl[HPW], hn[HPW];
-    halo_offsets(tl, hl);
-    stage_w(0, 0, 0);
-#pragma unroll
-    for (int k = 0; k < HPW; ++k)
-        if (k * NWV + wave < HINST) stage_h(hl[k], k, 0, 0);
-    __syncthreads();
-
-    int s = 0, hpar = 0;                                     // running weight-step counter and halo-buffer parity
-    while (true) {
-        const int tn = tl + gridDim.x;
-        const bool has_next = tn < ntile;                    // block-uniform
-        if (has_next) halo_offsets(tn, hn);
-        for (int c = 0; c < kchunks; ++c, hpar ^= 1) {
-            const bool last_c = c + 1 == kchunks;
-            const int hbuf = hpar * HBYTES;
-#pragma unroll
-            for (int dh = 0; dh < 3; ++dh) {
-#pragma unroll
-                for (int dw = 0; dw < 3; ++dw, ++s) {
-                    const int t = dh * 3 + dw;
-                    // next weight tile: next tap of this chunk, first tap of the next chunk, or of the next tile
-                    if (t < 8) stage_w(t + 1, c * KC, (s + 1) & 1);
-                    else if (!last_c) stage_w(0, (c + 1) * KC, (s + 1) & 1);
-                    else if (has_next) stage_w(0, 0, (s + 1) & 1);
-                    // one halo piece of the next chunk instance per tap step
-                    if (t < HPW && t * NWV + wave < HINST) {
-                        if (!last_c) stage_h(hl[t], t, (c + 1) * KC, hpar ^ 1);
-                        else if (has_next) stage_h(hn[t], t, 0, hpar ^ 1);
-                    }
-                    const char* Wb = Ws + (s & 1) * WBYTES;
-                    const char* Hb = Hs + hbuf + dh * (HW_ * 128);
-                    if constexpr (M_::PAIR) {
-                        typename M_::Frag2 a[TM], b[TN];
-#pragma unroll
-                        for (int i = 0; i < TM; ++i) a[i] = M_::ld2(Wb + aoff[0] + i * 2048, Wb + aoff[1] + i * 2048);
-#pragma unroll
-                        for (int j = 0; j < TN; ++j) b[j] = M_::ld2(Hb + boff[dw][0] + j * (HW_ * 128), Hb + boff[dw][1] + j * (HW_ * 128));
-#pragma unroll
-                        for (int i = 0; i < TM; ++i)
-#pragma unroll
-                            for (int j = 0; j < TN; ++j) M_::mma2(a[i], b[j], acc[i][j]);
-                    } else {
-#pragma unroll
-                    for (int kk = 0; kk < 2; ++kk) {
-                        Frag a[TM], b[TN];
-                        const char* wa = Wb + aoff[kk];
-                        const char* hb = Hb + boff[dw][kk];
-#pragma unroll
-                        for (int i = 0; i < TM; ++i) a[i] = M_::ld(wa + i * 2048);
-#pragma unroll
-                        for (int j = 0; j < TN; ++j) b[j] = M_::ld(hb + j * (HW_ * 128));
-#pragma unroll
-                        for (int i = 0; i < TM; ++i)
-#pragma unroll
-                            for (int j = 0; j < TN; ++j) M_::mma(a[i], b[j], acc[i][j]);
-                    }
-                    }
-                    __syncthreads();
-                }
-            }
-        }
-        // epilogue of this tile (the next tile's first DMAs are already in flight)
-        {
-            const int tw_ = tl % tiles_w, th_ = (tl / tiles_w) % tiles_h, bimg = tl / (tiles_w * tiles_h);
-            const int h0 = th_ * TH, w0 = tw_ * TW;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const long p = ((long)bimg * H + h0 + wc * TN + j) * W + w0 + r16;
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    const int co = co0 + (wr * TM + i) * 16 + 4 * g;
-                    float v[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        v[r] = acc[i][j][r];
-                        if constexpr (std::is_same<T, xh32>::value) v[r] *= 1.0f / (float)(1 << MU_XH_WSHIFT);
-                        v[r] += (bias ? bias[co + r] : 0.f);
-                    }
-                    if constexpr (sizeof(T) == 2) {
-                        h16x4 o = {(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
-                        *reinterpret_cast<h16x4*>(y + p * y_ld + co) = o;
-                    } else {
-                        *reinterpret_cast<float4*>(y + p * y_ld + co) = make_float4(v[0], v[1], v[2], v[3]);
-                    }
-                    acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                }
-            }
-        }
-        if (!has_next) break;
-        tl = tn;
-#pragma unroll
-        for (int k = 0; k < HPW; ++k) hl[k] = hn[k];
-    }
+    conv_nt3_body<T, TM, TN, WR, false, true>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2049,21 +1866,45 @@ __global__ __launch_bounds__(512, 1) void conv_nt5_kernel(const h16* __restrict_
 #ifndef MU_NT5_SPLIT_MINTILES
 #define MU_NT5_SPLIT_MINTILES 1024
 #endif
-static inline bool nt5_serves(int B, int H, int W, int Cin, int Cout) {
-    if (!MU_CONV_NT5 || getenv("MU_CONV_NO_NT5")) return false;
-    return Cin == 64 && Cout == 64 && H % 16 == 0 && W % 16 == 0 && (long)B * (H / 16) * (W / 16) >= MU_NT5_MINTILES;
+
+// The 3x3 forward plan: which halo-tile kernel of conv_fwd_launch<T, 9> serves the shape (K3_NONE: the shape is not on the halo-tile
+// path), and how many rows of per-tile BatchNorm statistics its epilogue writes when it is handed stat_part (0: no statistics epilogue).
+// mu_conv_stats_rows reads the same plan, so the statistics rows always describe the kernel that runs.
+enum Conv3x3Kernel { K3_NONE, K3_NT5, K3_NT5_HALVES, K3_NT4P, K3_NT4, K3_NT4X, K3_NT3_128, K3_NT3_64_RING, K3_NT3_64 };
+struct Conv3x3Plan {
+    Conv3x3Kernel kernel;
+    int stat_rows;
+};
+static Conv3x3Plan conv3x3_pick(int B, int H, int W, int Cin, int Cout, int dtype, bool with_stats) {
+    const int es = dtype == MU_F16 ? 2 : 4;
+    if ((Cin * es) % 128 || W % 16) return {K3_NONE, 0};
+    const long t16 = (long)B * (H / 16) * (W / 16);          // 16 x 16 tiles: the ping-pong kernels write one row per tile and wave group
+    const int rows16 = (int)(t16 * 4);
+    if (dtype == MU_F16) {
+        const bool nt5 = MU_CONV_NT5 && Cin == 64 && H % 16 == 0 && t16 >= MU_NT5_MINTILES;
+        if (nt5 && Cout == 64) return {K3_NT5, rows16};
+        // 64 -> 128 without a statistics epilogue (the data-gradient of the 128 -> 64 layers) as two resident 64 -> 64 halves
+        if (nt5 && MU_NT5_SPLIT128 && !with_stats && Cout == 128 && t16 >= MU_NT5_SPLIT_MINTILES) return {K3_NT5_HALVES, 0};
+        if (MU_CONV_NT4 && Cout % 128 == 0 && H % 16 == 0 && Cin % 64 == 0 && t16 * (Cout / 128) >= MU_NT4_MINBLK) {
+            // measured (in-process A/B): 128->128 @128^2 322 -> 307 us, 64->128 @128^2 205 -> 176 us, 256->256 @64^2 equal,
+            // 512->512 @32^2 and two-tile blocks 1-3 % slower -> persistent only for >= 4 tiles per block and short K loops
+            if (MU_CONV_NT4P && t16 * (Cout / 128) >= 1024 && Cin <= 256 && 256 % (Cout / 128) == 0) return {K3_NT4P, rows16};
+            return {K3_NT4, rows16};
+        }
+    }
+    // fp32x: one 512-thread block per CU: a grid of fewer than ~200 blocks (16^2 256 -> 256 at B = 64: 128) leaves half of the chip
+    // idle, where the generic kernel's 8 x 16 pixel tiles still fill it (61 vs 72 us in-process)
+    if (dtype == MU_F32X && MU_CONV_NT4X && Cout % 128 == 0 && H % 16 == 0 && t16 * (Cout / 128) >= 192) return {K3_NT4X, rows16};
+    if (H % 8) return {K3_NONE, 0};
+    const int t8 = B * (H / 8) * (W / 16);                  // 8 x 16 tiles: one row per tile and wave row
+    if (Cout % 128 == 0) return {K3_NT3_128, MU_NT3_STATS ? t8 * 2 : 0};
+    // the three-slot weight ring pays for its longer prologue from two 64-channel chunks on (see conv_nt3_body)
+    if (Cout % 64 == 0) return {Cin * es >= 256 ? K3_NT3_64_RING : K3_NT3_64, MU_NT3_STATS ? t8 * 4 : 0};
+    return {K3_NONE, 0};
 }
 
 // The same dispatch for the inference epilogue y = act(conv * scale + bias + res): FEPI instantiations of the non-persistent kernels
 // (the persistent ping-pong kernel counts its epilogue's memory operations in hand-placed vmcnt waits and takes no epilogue loads).
-// fp32x: which 3x3 shapes the ping-pong kernel serves.  One 512-thread block per CU: a grid of fewer than ~200 blocks (16^2 256 -> 256 at
-// B = 64: 128) leaves half of the chip idle, where the generic kernel's 8 x 16 pixel tiles still fill it (61 vs 72 us in-process)
-static inline bool nt4x_serves(int B, int H, int W, int Cin, int Cout) {
-    if (!MU_CONV_NT4X || getenv("MU_CONV_NO_NT4")) return false;
-    if (Cout % 128 || H % 16 || W % 16 || Cin % 32) return false;
-    return (long)B * (H / 16) * (W / 16) * (Cout / 128) >= 192;
-}
-
 template <typename T, int TAPS>
 static int conv_fwd_fused_launch(const T* x, const T* w, const float* scale, const float* bias, const T* res, int act, T* y, int B, int H, int W,
                                  int Cin, int Cout, long x_ld, long y_ld, hipStream_t st) {
@@ -2109,70 +1950,38 @@ static int conv_fwd_launch(const T* x, const T* w, const float* bias, T* y, int 
                            long y_ld, hipStream_t st, float* stat_part = nullptr) {
     const long M = (long)B * H * W;
     const int npb = (int)((M + 127) / 128);
-    if (TAPS == 9 && (Cin * (int)sizeof(T)) % 128 == 0 && W % 16 == 0) {     // halo-tile version
-        if (Cout % 128 == 0 && H % 16 == 0 && (long)B * H * W >= 262144 && getenv("MU_CONV_NW8")) {
-            // experiment kept for reference: 16x16 spatial tile, 8 waves -- the weight tile is shared by 256 pixels (half the
-            // L2->LDS bytes per flop) yet the step time is unchanged (45.39 vs 45.29 ms): v3 is no longer L2->LDS bound
-            conv_nt3_kernel<T, 4, 4, 2, 8><<<B * (H / 16) * (W / 16) * (Cout / 128), 512, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
+    if constexpr (TAPS == 9) {          // halo-tile kernels (the plan names the fp16 kernels for h16 only and conv_nt4x_kernel for xh32 only)
+        constexpr int dtype = sizeof(T) == 2 ? MU_F16 : mu_is_split<T>::value ? MU_F32X : MU_F32;
+        const int t16 = B * (H / 16) * (W / 16), t8 = B * (H / 8) * (W / 16);
+        switch (conv3x3_pick(B, H, W, Cin, Cout, dtype, stat_part != nullptr).kernel) {
+        case K3_NONE:
+            break;
+        case K3_NT5:
+            if constexpr (sizeof(T) == 2)
+                conv_nt5_kernel<<<t16 < 256 ? t16 : 256, 512, 0, st>>>((const h16*)x, (const h16*)w, bias, (h16*)y, B, H, W, x_ld, y_ld, stat_part, 64);
             return MU_OK;
-        }
-        if constexpr (mu_is_split<T>::value && MU_XF_NT3_RING8) {
-            if (Cout % 128 == 0 && H % 16 == 0) {
-                conv_nt3_kernel<T, 4, 4, 2, 8, true><<<B * (H / 16) * (W / 16) * (Cout / 128), 512, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
-                return MU_OK;
-            }
-        }
-        if constexpr (sizeof(T) == 2) {
-            if (nt5_serves(B, H, W, Cin, Cout)) {
-                const int ntile5 = B * (H / 16) * (W / 16);
-                conv_nt5_kernel<<<ntile5 < 256 ? ntile5 : 256, 512, 0, st>>>((const h16*)x, (const h16*)w, bias, (h16*)y, B, H, W, x_ld, y_ld, stat_part, 64);
-                return MU_OK;
-            }
-            // 64 -> 128 without a statistics epilogue (the data-gradient of the 128 -> 64 layers) as two resident 64 -> 64 halves
-            if (MU_NT5_SPLIT128 && !stat_part && Cout == 128 && nt5_serves(B, H, W, Cin, 64) && (long)B * (H / 16) * (W / 16) >= MU_NT5_SPLIT_MINTILES) {
+        case K3_NT5_HALVES:
+            if constexpr (sizeof(T) == 2)
                 conv_nt5_kernel<<<dim3(256, 2), 512, 0, st>>>((const h16*)x, (const h16*)w, bias, (h16*)y, B, H, W, x_ld, y_ld, nullptr, 128);
-                return MU_OK;
-            }
-        }
-        if constexpr (sizeof(T) == 2 && MU_CONV_NT4) {
-            if (Cout % 128 == 0 && H % 16 == 0 && Cin % 64 == 0 && !getenv("MU_CONV_NO_NT4") &&
-                (long)B * (H / 16) * (W / 16) * (Cout / 128) >= MU_NT4_MINBLK) {
-#if MU_CONV_NT4P
-                const int ntile4 = B * (H / 16) * (W / 16), ncb4 = Cout / 128;
-                // measured (in-process A/B): 128->128 @128^2 322 -> 307 us, 64->128 @128^2 205 -> 176 us, 256->256 @64^2 equal,
-                // 512->512 @32^2 and two-tile blocks 1-3 % slower -> persistent only for >= 4 tiles per block and short K loops
-                if (ntile4 * ncb4 >= 1024 && Cin <= 256 && 256 % ncb4 == 0) {
-                    conv_nt4p_kernel<<<256, 512, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
-                    return MU_OK;
-                }
-#endif
-                conv_nt4_kernel<<<B * (H / 16) * (W / 16) * (Cout / 128), 512, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
-                return MU_OK;
-            }
-        }
-        if constexpr (mu_is_split<T>::value && MU_CONV_NT4X) {
-            if (nt4x_serves(B, H, W, Cin, Cout)) {
-                conv_nt4x_kernel<T><<<B * (H / 16) * (W / 16) * (Cout / 128), 512, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
-                return MU_OK;
-            }
-        }
-        if (Cout % 128 == 0 && H % 8 == 0) {
-            const int ntile = B * (H / 8) * (W / 16), ncb = Cout / 128;
-            // ~2 resident blocks per CU in total (MU_CONV_PERSIST_BLOCKS overrides the block count: parity tests use tiny grids)
-            const int per_cb = getenv("MU_CONV_PERSIST_BLOCKS") ? atoi(getenv("MU_CONV_PERSIST_BLOCKS")) : 512 / ncb;
-            // measured: 407 vs 418 us on 128->128 @128^2 but 332 vs 318 us on 256->256 @64^2 -- the fill/drain bubble is already
-            // hidden by the second resident block, so the persistent walk stays opt-in (MU_CONV_PERSIST / MU_CONV_PERSIST_BLOCKS)
-            if (ntile >= 4 * per_cb && (getenv("MU_CONV_PERSIST") || getenv("MU_CONV_PERSIST_BLOCKS"))) {
-                conv_nt3p_kernel<T, 4, 4, 2><<<dim3(per_cb, ncb), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
-                return MU_OK;
-            }
-            conv_nt3_kernel<T, 4, 4, 2><<<ntile * ncb, 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
             return MU_OK;
-        }
-        if (Cout % 64 == 0 && H % 8 == 0) {
-            const int grid3 = B * (H / 8) * (W / 16) * (Cout / 64);
-            if (Cin * (int)sizeof(T) >= 256) conv_nt3_kernel<T, 4, 2, 1, 4, true><<<grid3, 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
-            else conv_nt3_kernel<T, 4, 2, 1><<<grid3, 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
+        case K3_NT4P:
+            if constexpr (sizeof(T) == 2) conv_nt4p_kernel<<<256, 512, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
+            return MU_OK;
+        case K3_NT4:
+            if constexpr (sizeof(T) == 2) conv_nt4_kernel<<<t16 * (Cout / 128), 512, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
+            return MU_OK;
+        case K3_NT4X:
+            if constexpr (mu_is_split<T>::value)
+                conv_nt4x_kernel<T><<<t16 * (Cout / 128), 512, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
+            return MU_OK;
+        case K3_NT3_128:
+            conv_nt3_kernel<T, 4, 4, 2><<<t8 * (Cout / 128), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
+            return MU_OK;
+        case K3_NT3_64_RING:
+            conv_nt3_kernel<T, 4, 2, 1, true><<<t8 * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
+            return MU_OK;
+        case K3_NT3_64:
+            conv_nt3_kernel<T, 4, 2, 1><<<t8 * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
             return MU_OK;
         }
     }
@@ -2216,22 +2025,10 @@ static int conv_fwd_launch(const T* x, const T* w, const float* bias, T* y, int 
 }
 
 // Rows of per-tile BatchNorm statistics mu_conv_fwd_stats writes for this layer shape (0: the kernel that serves it has no
-// statistics epilogue -- run mu_bn_train_stats on the output instead).  One row per 16x16 output tile and 4-image-row group.
+// statistics epilogue -- run mu_bn_train_stats on the output instead): the count of the 3x3 forward plan (conv3x3_pick).
 extern "C" int mu_conv_stats_rows(int B, int H, int W, int Cin, int Cout, int taps, int dtype) {
-    // mirrors conv_fwd_launch<T, 9>: which kernel serves the shape, and how many statistics rows its epilogue writes
     if (taps != 9 || B <= 0 || (dtype != MU_F16 && dtype != MU_F32X)) return 0;
-    const int es = dtype == MU_F16 ? 2 : 4;
-    if ((Cin * es) % 128 || W % 16 || Cout % 32) return 0;
-    if (getenv("MU_CONV_NW8") || getenv("MU_CONV_PERSIST") || getenv("MU_CONV_PERSIST_BLOCKS") || (dtype == MU_F32X && MU_XF_NT3_RING8)) return 0;
-    if (dtype == MU_F16 && MU_CONV_NT4 && !getenv("MU_CONV_NO_NT4") && Cout % 128 == 0 && H % 16 == 0 && Cin % 64 == 0 &&
-        (long)B * (H / 16) * (W / 16) * (Cout / 128) >= MU_NT4_MINBLK)
-        return B * (H / 16) * (W / 16) * 4;
-    if (dtype == MU_F32X && nt4x_serves(B, H, W, Cin, Cout)) return B * (H / 16) * (W / 16) * 4;
-    if (dtype == MU_F16 && nt5_serves(B, H, W, Cin, Cout)) return B * (H / 16) * (W / 16) * 4;     // conv_nt5_kernel: one row per wave of a group
-    if (!MU_NT3_STATS || H % 8) return 0;
-    if (Cout % 128 == 0) return B * (H / 8) * (W / 16) * 2;           // conv_nt3_kernel<T, 4, 4, 2>: two wave rows per 8 x 16 tile
-    if (Cout % 64 == 0) return B * (H / 8) * (W / 16) * 4;            // conv_nt3_kernel<T, 4, 2, 1>: four
-    return 0;
+    return conv3x3_pick(B, H, W, Cin, Cout, dtype, true).stat_rows;
 }
 
 extern "C" int mu_conv_fwd_stats(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin, int Cout,
@@ -2291,11 +2088,13 @@ extern "C" int mu_conv_fwd(const void* x, const void* w, const float* bias, void
 // of the weights (the HL data-gradient block of mu_prep_weight / mu_prep_weights_multi with MU_F32X: [9][Cout][2 * Cin] halves): two fp16
 // MFMAs per product instead of the forward's three.  dx: plain fp32 rows (row stride dx_ld floats), multiplied by dy_scale[1] = 1 / S and by
 // 2^-MU_XH_WSHIFT in the epilogue (exact: powers of two).  Cin = channels of dy (the layer's output), Cout = channels of dx (its input).
-// (1 = the weights as one fp16 term, one MFMA per product: step -1.5 ms same-box, but the small-module goldens' parameter gradients land
-//  at 1.06e-3 .. 1.17e-3 against their 1e-3 gate -- 9 * Cout = 72 .. 288 terms average too little --, so the default keeps both halves)
+// Weight terms (MU_DGRAD_H_TERMS, compile time): 2 = lo + hi halves; 1 = the hi halves only, one MFMA per product: step -1.5 ms same-box,
+// but the small-module goldens' parameter gradients land at 1.06e-3 .. 1.17e-3 against their 1e-3 gate -- 9 * Cout = 72 .. 288 terms
+// average too little --, so the default keeps both halves.
 #ifndef MU_DGRAD_H_TERMS
 #define MU_DGRAD_H_TERMS 2
 #endif
+static_assert(MU_DGRAD_H_TERMS == 1 || MU_DGRAD_H_TERMS == 2, "MU_DGRAD_H_TERMS: 1 or 2 weight terms");
 extern "C" int mu_conv_dgrad_h(const void* dy_h, const void* w_hl, const float* dy_scale, void* dx, int B, int H, int W, int Cin, int Cout,
                                long dy_ld, long dx_ld, void* stream) {
     if (!dy_h || !w_hl || !dy_scale || !dx || B <= 0 || H <= 0 || W <= 0) return MU_ERR_ARG;
@@ -2306,28 +2105,21 @@ extern "C" int mu_conv_dgrad_h(const void* dy_h, const void* w_hl, const float* 
     float* y = (float*)dx;
     const long M = (long)B * H * W;
     const int npb = (int)((M + 127) / 128);
-    // weight terms: 2 = lo + hi halves (default, MU_DGRAD_H_TERMS), 1 = the hi halves only; MU_DGRAD_H_TERMS in the environment overrides (A/B aid)
-    const int terms = getenv("MU_DGRAD_H_TERMS") ? atoi(getenv("MU_DGRAD_H_TERMS")) : MU_DGRAD_H_TERMS;
-#define MU_DGH(KERNEL2, KERNEL1, GRID, BLK) do { if (terms == 2) KERNEL2<<<GRID, BLK, 0, st>>>(x, w, y, B, H, W, Cin, Cout, dy_ld, dx_ld, dy_scale); \
-                                                 else KERNEL1<<<GRID, BLK, 0, st>>>(x, w, y, B, H, W, Cin, Cout, dy_ld, dx_ld, dy_scale); } while (0)
-#define MU_DGG(TM_, TN_, WR_, GRID) do { if (terms == 2) conv_nt_kernel<h16, TM_, TN_, WR_, 9, false, 2><<<GRID, 256, 0, st>>>(x, w, nullptr, nullptr, B, H, W, Cin, Cout, dy_ld, dx_ld, nullptr, nullptr, 0, y, dy_scale); \
-                                         else conv_nt_kernel<h16, TM_, TN_, WR_, 9, false, 1><<<GRID, 256, 0, st>>>(x, w, nullptr, nullptr, B, H, W, Cin, Cout, dy_ld, dx_ld, nullptr, nullptr, 0, y, dy_scale); } while (0)
-    if (Cin % 64 == 0 && W % 16 == 0 && H % 8 == 0 && Cout % 64 == 0 && !getenv("MU_DGRAD_H_GENERIC")) {
-        if (Cout % 128 == 0 && H % 16 == 0 && MU_CONV_NT4 && !getenv("MU_CONV_NO_NT4"))
-            MU_DGH(conv_nt4hl_kernel<2>, conv_nt4hl_kernel<1>, B * (H / 16) * (W / 16) * (Cout / 128), 512);
+    constexpr int HL = MU_DGRAD_H_TERMS;
+    if (Cin % 64 == 0 && W % 16 == 0 && H % 8 == 0 && Cout % 64 == 0) {
+        if (Cout % 128 == 0 && H % 16 == 0 && MU_CONV_NT4)
+            conv_nt4hl_kernel<HL><<<B * (H / 16) * (W / 16) * (Cout / 128), 512, 0, st>>>(x, w, y, B, H, W, Cin, Cout, dy_ld, dx_ld, dy_scale);
         else if (Cout % 128 == 0)
-            MU_DGH((conv_nt3hl_kernel<4, 4, 2, false, 2>), (conv_nt3hl_kernel<4, 4, 2, false, 1>), B * (H / 8) * (W / 16) * (Cout / 128), 256);
+            conv_nt3hl_kernel<4, 4, 2, false, HL><<<B * (H / 8) * (W / 16) * (Cout / 128), 256, 0, st>>>(x, w, y, B, H, W, Cin, Cout, dy_ld, dx_ld, dy_scale);
         else
-            MU_DGH((conv_nt3hl_kernel<4, 2, 1, true, 2>), (conv_nt3hl_kernel<4, 2, 1, true, 1>), B * (H / 8) * (W / 16) * (Cout / 64), 256);
+            conv_nt3hl_kernel<4, 2, 1, true, HL><<<B * (H / 8) * (W / 16) * (Cout / 64), 256, 0, st>>>(x, w, y, B, H, W, Cin, Cout, dy_ld, dx_ld, dy_scale);
     } else if (Cout % 128 == 0) {
-        MU_DGG(4, 4, 2, npb * (Cout / 128));
+        conv_nt_kernel<h16, 4, 4, 2, 9, false, HL><<<npb * (Cout / 128), 256, 0, st>>>(x, w, nullptr, nullptr, B, H, W, Cin, Cout, dy_ld, dx_ld, nullptr, nullptr, 0, y, dy_scale);
     } else if (Cout % 64 == 0) {
-        MU_DGG(4, 2, 1, npb * (Cout / 64));
+        conv_nt_kernel<h16, 4, 2, 1, 9, false, HL><<<npb * (Cout / 64), 256, 0, st>>>(x, w, nullptr, nullptr, B, H, W, Cin, Cout, dy_ld, dx_ld, nullptr, nullptr, 0, y, dy_scale);
     } else {
-        MU_DGG(2, 2, 1, npb * (Cout / 32));
+        conv_nt_kernel<h16, 2, 2, 1, 9, false, HL><<<npb * (Cout / 32), 256, 0, st>>>(x, w, nullptr, nullptr, B, H, W, Cin, Cout, dy_ld, dx_ld, nullptr, nullptr, 0, y, dy_scale);
     }
-#undef MU_DGH
-#undef MU_DGG
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
@@ -3666,8 +3458,8 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad9_w16_kernel(const h16* __re
 #define MU_WG9_MAXC16 512
 #endif
 // `pair` (mu_conv_wgrad_h, round 6): Cin counts the 16-bit COLUMNS of a chunk-encoded fp32x input -- two per channel -- and the layer-size
-// limits below, which were measured on real channel counts, apply to Cin / 2 (MU_WG9_PAIR_WIDE=0 in the environment: the limits as they are)
-static inline int wg9_pair_div(bool pair) { return (pair && !(getenv("MU_WG9_PAIR_WIDE") && atoi(getenv("MU_WG9_PAIR_WIDE")) == 0)) ? 2 : 1; }
+// limits below, which were measured on real channel counts, apply to Cin / 2
+static inline int wg9_pair_div(bool pair) { return pair ? 2 : 1; }
 static inline bool wgrad9_w16_choose(int B, int H, int W, int Cin, int Cout, int taps, int dtype, int* nb, int* rpb, bool pair = false) {
     if (!MU_WG9_W16 || dtype != MU_F16 || taps != 9 || W != 16 || H % 2 || Cin % 64 || Cout % 64 || Cin / wg9_pair_div(pair) > MU_WG9_MAXC16 || Cout > MU_WG9_MAXC16) return false;
     const long rows = (long)B * H;

@@ -252,16 +252,12 @@ class DataParallel(nn.Module):
 
     def _reduce(self, params):
         """Flatten the gradients of `params` and start their all-reduce -> (flat, work).  On a GPU both are issued with the
-        comm stream current, after it has waited for the producing stream(s)."""
+        comm stream current, after it has waited for the producing stream."""
         grads = [p.grad for p in params]
         dev = grads[0].device
         if dev.type == "cuda":
             comm = self._comm(dev)
             comm.wait_stream(torch.cuda.current_stream(dev))
-            from . import ops
-            side = ops.wgrad_stream(dev)          # conv weight gradients may be produced on their own stream (ops._wgrad_side)
-            if side is not None:
-                comm.wait_stream(side)
             with torch.cuda.stream(comm):
                 flat = torch.cat([g.reshape(-1).float() for g in grads])
                 # RCCL averages inside the collective (ncclAvg); other backends sum and _write_back divides
@@ -296,10 +292,6 @@ class DataParallel(nn.Module):
         if dev.type == "cuda":
             comm = self._comm(dev)
             comm.wait_stream(torch.cuda.current_stream(dev))
-            from . import ops
-            side = ops.wgrad_stream(dev)
-            if side is not None:
-                comm.wait_stream(side)
             with torch.cuda.stream(comm):
                 if src:
                     torch._foreach_copy_(dst, src)

@@ -76,7 +76,7 @@ def dy_encode_h(gy):
     gy = gy.contiguous()
     out = torch.empty_like(gy)
     scale = torch.empty(2, dtype=torch.float32, device=gy.device)
-    ws = torch.empty(_lib.load().mu_dy_encode_h_workspace_bytes(), dtype=torch.uint8, device=gy.device)      # (own buffer: also called on the side stream)
+    ws = torch.empty(_lib.load().mu_dy_encode_h_workspace_bytes(), dtype=torch.uint8, device=gy.device)
     call("mu_dy_encode_h", ptr(gy), ptr(out), ptr(scale), gy.numel(), ptr(ws), ws.numel(), stream())
     return out, scale
 
@@ -157,9 +157,8 @@ class EncLink:
 
 
 def enc_link(x):
-    """A fresh EncLink when x is an fp32 tensor in the fp32x mode and a backward can follow, else None (also None with the side-stream
-    weight gradient, MU_WGRAD_SIDE=1, which reads dy plain)."""
-    return EncLink() if (FUSED_ENCODE and not WGRAD_SIDE_STREAM and torch.is_grad_enabled() and _is_x(x)) else None
+    """A fresh EncLink when x is an fp32 tensor in the fp32x mode and a backward can follow, else None."""
+    return EncLink() if (torch.is_grad_enabled() and _is_x(x)) else None
 
 
 def _same_mode(ctx_is_x, t):
@@ -169,7 +168,6 @@ def _same_mode(ctx_is_x, t):
         raise RuntimeError("maskunet_amd: set_float32_matmul_precision() changed between a forward pass and its backward")
 
 
-FUSED_ENCODE = os.environ.get("MU_FUSED_ENCODE", "1") != "0"     # debug switch: 0 = every operand through mu_split_encode
 GRAD_LINKS = os.environ.get("MU_GRAD_LINKS", "1") != "0"      # debug switch: 0 = leave every gradient join to autograd
 
 
@@ -468,12 +466,9 @@ def grad_out(param, shape, device):
     return torch.empty(shape, dtype=torch.float32, device=device)
 
 
-WGRAD_X16 = os.environ.get("MU_WGRAD_X16", "1") != "0"         # debug switch: 0 = the two-term weight gradient on the encoded input (mu_conv_wgrad_h)
-
-
-def _wgrad_raw(x, gy, w_shape, taps, st=None, ws=None, gy_encoded=False, x_encoded=False, param=None, gy_scale=None):
-    """gy_scale (fp32x 3x3 layers): gy holds ONE scaled fp16 operand (dy_encode_h form) and this is its scale pair.  x may then be the
-    fp16 rounding of the layer's input (a float16 tensor: the one-term weight gradient) or its chunk-encoded fp32x form (two terms)."""
+def _wgrad_raw(x, gy, w_shape, taps, gy_encoded=False, x_encoded=False, param=None, gy_scale=None):
+    """gy_scale (fp32x 3x3 layers): gy holds ONE scaled fp16 operand (dy_encode_h form) and this is its scale pair; x is then the fp16
+    rounding of the layer's input (a float16 tensor: the one-term weight gradient)."""
     B, H, W, Cin_p = x.shape
     O, I = w_shape[0], w_shape[1]
     if x.dtype == torch.float16 and gy.dtype == torch.float32:      # (fp16-mode layers hand over an fp16 dy and take the ordinary path below)
@@ -481,29 +476,15 @@ def _wgrad_raw(x, gy, w_shape, taps, st=None, ws=None, gy_encoded=False, x_encod
             gy, gy_scale = dy_encode_h(gy)
         Cout_p = gy.shape[-1]
         gw = grad_out(param, tuple(w_shape), x.device)
-        if ws is None:
-            ws = workspace(_lib.load().mu_conv_wgrad_workspace_bytes(B, H, W, Cin_p, Cout_p, 9), x.device)
+        ws = workspace(_lib.load().mu_conv_wgrad_workspace_bytes(B, H, W, Cin_p, Cout_p, 9), x.device)
         call("mu_conv_wgrad_h1", ptr(x), ptr(gy), ptr(gy_scale), ptr(gw), B, H, W, Cin_p, Cout_p, I, O, Cin_p, Cout_p, ptr(ws), ws.numel(),
-             stream() if st is None else st)
+             stream())
         return gw
     code = mdt(x)
-    if code == _lib.MU_F32X and taps == 9 and I <= 3 and not gy_encoded and not x_encoded:
-        code = _lib.MU_F32               # the first layer's weight gradient is a plain-FMA kernel (no matrix cores): plain fp32 operands
     if code == _lib.MU_F32X and taps == 9:
-        # two-term weight gradient (round 6): the saved input as fp16 pairs x dy as one scaled fp16 operand
-        if not x_encoded:
-            x = _enc3(x)
-        if gy_scale is None:
-            if gy_encoded:
-                raise RuntimeError("conv weight gradient: a 3x3 layer takes dy as a scaled fp16 operand, not chunk-encoded")
-            gy, gy_scale = dy_encode_h(gy)
-        Cout_p = gy.shape[-1]
-        gw = grad_out(param, tuple(w_shape), x.device)
-        if ws is None:
-            ws = workspace(_lib.load().mu_conv_wgrad_h_workspace_bytes(B, H, W, Cin_p, Cout_p), x.device)
-        call("mu_conv_wgrad_h", ptr(x), ptr(gy), ptr(gy_scale), ptr(gw), B, H, W, Cin_p, Cout_p, I, O, Cin_p, Cout_p, ptr(ws), ws.numel(),
-             stream() if st is None else st)
-        return gw
+        if I > 3 or gy_encoded or x_encoded:
+            raise RuntimeError("conv weight gradient: an fp32x 3x3 layer takes the fp16 rounding of its input (mu_conv_wgrad_h1)")
+        code = _lib.MU_F32               # the first layer's weight gradient is a plain-FMA kernel (no matrix cores): plain fp32 operands
     if code == _lib.MU_F32X:
         if not x_encoded:
             x = _enc(x)
@@ -511,14 +492,9 @@ def _wgrad_raw(x, gy, w_shape, taps, st=None, ws=None, gy_encoded=False, x_encod
             gy = _enc(gy)
     Cout_p = gy.shape[-1]
     gw = grad_out(param, tuple(w_shape), x.device)
-    if ws is None:
-        ws = workspace(_lib.load().mu_conv_wgrad_workspace_bytes(B, H, W, Cin_p, Cout_p, taps), x.device)
-    call("mu_conv_wgrad", ptr(x), ptr(gy), ptr(gw), B, H, W, Cin_p, Cout_p, taps, I, O, Cin_p, Cout_p, ptr(ws), ws.numel(),
-         code, stream() if st is None else st)
+    ws = workspace(_lib.load().mu_conv_wgrad_workspace_bytes(B, H, W, Cin_p, Cout_p, taps), x.device)
+    call("mu_conv_wgrad", ptr(x), ptr(gy), ptr(gw), B, H, W, Cin_p, Cout_p, taps, I, O, Cin_p, Cout_p, ptr(ws), ws.numel(), code, stream())
     return gw
-
-
-WGRAD_BIAS = os.environ.get("MU_WGRAD_BIAS", "1") != "0"        # debug switch: 0 = separate column-sum sweep for the bias gradients
 
 
 def _wgrad_bias_raw(x, gy, w_shape, taps, param=None):
@@ -526,7 +502,7 @@ def _wgrad_bias_raw(x, gy, w_shape, taps, param=None):
     B, H, W, Cin_p = x.shape
     Cout_p = gy.shape[-1]
     lib = _lib.load()
-    if not WGRAD_BIAS or not lib.mu_conv_wgrad_bias_supported(Cin_p, Cout_p, taps, dt(x)):
+    if not lib.mu_conv_wgrad_bias_supported(Cin_p, Cout_p, taps, dt(x)):
         return None
     O, I = w_shape[0], w_shape[1]
     gw = grad_out(param, tuple(w_shape), x.device)
@@ -535,63 +511,6 @@ def _wgrad_bias_raw(x, gy, w_shape, taps, param=None):
     call("mu_conv_wgrad_bias", ptr(x), ptr(gy), ptr(gw), ptr(gb), B, H, W, Cin_p, Cout_p, taps, I, O, Cin_p, Cout_p, ptr(ws), ws.numel(),
          dt(x), stream())
     return gw, gb
-
-
-# Weight gradients on a side stream.  dW of a layer is needed by nobody until the backward pass is over, while the chain
-# dgrad -> BatchNorm backward -> ... of the layers below is mostly HBM-bound: the MFMA-bound weight-gradient kernels run
-# beside it (one 8-wave block per CU leaves room for the elementwise kernels' waves).  Ordering:
-#   * the side stream waits for the main stream (x and gy are ready), the main stream re-joins in an end-of-backward callback
-#     (queued on the autograd engine), so everything after loss.backward() sees finished gradients;
-#   * x, gy and gw are recorded on the other stream for the caching allocator;
-#   * only used when weight.grad is None (AccumulateGrad then adopts gw without launching a kernel; an existing .grad would be
-#     added to on the main stream) -- gradient accumulation over micro-batches falls back to the in-stream path;
-#   * maskunet_amd.DataParallel makes its bucket all-reduce wait for this stream as well (dp.py).
-_SIDE = {}
-_SIDE_WS = {}
-_JOIN_QUEUED = set()
-# Measured (B=64 bench, same box, two rounds): 36.20 / 36.25 ms per step in-stream vs 36.54 / 36.45 ms with the side stream
-# (36.78 / 36.50 when launched ahead of the data gradient): the kernels do not overlap usefully, so this stays opt-in.
-WGRAD_SIDE_STREAM = os.environ.get("MU_WGRAD_SIDE", "0") != "0"
-# only layers whose feature map is at most this high (at 16^2 / 32^2 the data- and weight-gradient grids each fill half of the
-# chip at B = 64, so the pair could run side by side; the big layers compete for HBM / LDS -- the round-3 finding)
-WGRAD_SIDE_MAXHW = int(os.environ.get("MU_WGRAD_SIDE_MAXHW", "100000"))
-
-
-def wgrad_stream(device):
-    """The side stream weight gradients are computed on (None if it has not been used on this device)."""
-    return _SIDE.get(torch.device(device).index if not isinstance(device, int) else device)
-
-
-def _join_side(index):
-    def cb():
-        _JOIN_QUEUED.discard(index)
-        torch.cuda.current_stream(index).wait_stream(_SIDE[index])
-    return cb
-
-
-def _wgrad_side(x, gy, w_shape, taps, x_encoded=False, param=None):
-    dev = x.device
-    side = _SIDE.get(dev.index)
-    if side is None:
-        side = _SIDE[dev.index] = torch.cuda.Stream(dev)
-    main = torch.cuda.current_stream(dev)
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
-        B, H, W, Cin_p = x.shape
-        nbytes = _lib.load().mu_conv_wgrad_workspace_bytes(B, H, W, Cin_p, gy.shape[-1], taps)
-        if taps == 9 and _is_x(x):
-            nbytes = max(nbytes, _lib.load().mu_conv_wgrad_h_workspace_bytes(B, H, W, Cin_p, gy.shape[-1]))
-        ws = _SIDE_WS.get(dev.index)
-        if ws is None or ws.numel() < nbytes:
-            ws = _SIDE_WS[dev.index] = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=dev)
-        gw = _wgrad_raw(x, gy, w_shape, taps, st=side.cuda_stream, ws=ws, x_encoded=x_encoded, param=param)
-    x.record_stream(side)
-    gy.record_stream(side)
-    gw.record_stream(main)
-    if dev.index not in _JOIN_QUEUED:
-        _JOIN_QUEUED.add(dev.index)
-        torch.autograd.Variable._execution_engine.queue_callback(_join_side(dev.index))
-    return gw
 
 
 def _colsum(gy, n_valid, encoded=False):
@@ -635,18 +554,20 @@ class _Conv(torch.autograd.Function):
             raise RuntimeError("conv: a pre-encoded input needs the fp32x mode and a matrix-core layer")
         # fp32x 3x3 layers (round 6): the backward keeps only the fp16 ROUNDING of the input (x16: half the bytes of the encoded form) for the
         # one-term weight gradient; the encoded form feeds the forward conv and is dropped.  x16 comes from the producer that wrote x
-        # encoded (bn_act: `_mu_x16`), or from the same pass that encodes x here; without it the two-term form on the encoded input remains.
-        keep16 = ctx.x_enc and taps == 9 and WGRAD_X16 and ctx.needs_input_grad[1]
+        # encoded (bn_act: `_mu_x16`), or from the same pass that encodes x here.
+        keep16 = ctx.x_enc and taps == 9 and ctx.needs_input_grad[1]
         if ctx.x_enc and not x_encoded:
             if keep16:
                 x, x16 = _enc3x(x)
             else:
                 x = _enc_for(x, taps)
+        if keep16 and x16 is None:
+            raise RuntimeError("conv: a pre-encoded 3x3 input needs its fp16 rounding beside it (bn_act(..., enc_out=True))")
         if want_stats:
             y, part = _conv_raw(x, wprep, bias_p, Cout_p, taps, True, x_encoded=ctx.x_enc)
         else:
             y = _conv_raw(x, wprep, bias_p, Cout_p, taps, x_encoded=ctx.x_enc)
-        ctx.save_for_backward(x16 if (keep16 and x16 is not None) else x, weight)
+        ctx.save_for_backward(x16 if keep16 else x, weight)
         ctx.wparam = weight                      # the Parameter itself: backward looks at its .grad
         ctx.has_bias, ctx.taps = bias is not None, taps
         if not want_stats:
@@ -669,15 +590,12 @@ class _Conv(torch.autograd.Function):
         gy_pre = gy_sc is not None
         O, I = weight.shape[0], weight.shape[1]
         gx = gw = gb = None
-        side = ctx.needs_input_grad[1] and WGRAD_SIDE_STREAM and ctx.wparam.grad is None and x.shape[1] <= WGRAD_SIDE_MAXHW
-        if side and os.environ.get("MU_WGRAD_SIDE_FIRST"):
-            gw = _wgrad_side(x, gy, tuple(weight.shape), ctx.taps, ctx.x_enc, ctx.wparam)
-        if gy_pre and (side or not ctx.x_enc or ctx.taps != 9 or (ctx.has_bias and ctx.needs_input_grad[2])):
+        if gy_pre and (not ctx.x_enc or ctx.taps != 9 or (ctx.has_bias and ctx.needs_input_grad[2])):
             raise RuntimeError("conv backward: an encoded dy reached a path that needs it plain")
         if ctx.is_x and ctx.taps == 9:
             # fp32x 3x3 layer (round 6): dy as ONE power-of-two-scaled fp16 operand, shared by the data gradient (against the fp16 pair of
             # the weights: two MFMAs per product) and the weight gradient (against the fp16 rounding of the saved input: one)
-            wg_h = ctx.needs_input_grad[1] and not side and ctx.x_enc      # (a <= 3-channel layer's weight gradient: plain-FMA kernel, plain dy)
+            wg_h = ctx.needs_input_grad[1] and ctx.x_enc      # (a <= 3-channel layer's weight gradient: plain-FMA kernel, plain dy)
             gh = gy if gy_pre else None
             if gh is None and (ctx.needs_input_grad[0] or wg_h):
                 gh, gy_sc = dy_encode_h(gy)
@@ -687,23 +605,19 @@ class _Conv(torch.autograd.Function):
                 B, H, W, Cin_p = x.shape
                 gx = torch.empty((B, H, W, Cin_p), dtype=torch.float32, device=x.device)
                 call("mu_conv_dgrad_h", ptr(gh), ptr(wd), ptr(gy_sc), ptr(gx), B, H, W, gy.shape[-1], Cin_p, gy.shape[-1], Cin_p, stream())
-            if side and gw is None:
-                gw = _wgrad_side(x, gy, tuple(weight.shape), ctx.taps, ctx.x_enc, ctx.wparam)
-            if wg_h:         # x: the fp16 rounding of the input (one term) or its encoded form (two terms) -- _wgrad_raw tells by dtype
-                gw = _wgrad_raw(x, gh, tuple(weight.shape), 9, x_encoded=True, param=ctx.wparam, gy_scale=gy_sc)
-            elif ctx.needs_input_grad[1] and not side:
+            if wg_h:         # x: the fp16 rounding of the input (one term)
+                gw = _wgrad_raw(x, gh, tuple(weight.shape), 9, param=ctx.wparam, gy_scale=gy_sc)
+            elif ctx.needs_input_grad[1]:
                 gw = _wgrad_raw(x, gy, tuple(weight.shape), 9, param=ctx.wparam)
             if ctx.has_bias and ctx.needs_input_grad[2]:
                 gb = _colsum(gy, O)
             return gx, gw, gb, None, None, None, None, None
-        ge = _enc(gy) if (ctx.needs_input_grad[0] or (ctx.needs_input_grad[1] and not side)) else gy     # fp32x: one encoding of dy for both
+        ge = _enc(gy) if (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) else gy     # fp32x: one encoding of dy for both
         if ctx.needs_input_grad[0]:
             wd = ctx.wd if ctx.wd is not None else _prep_weight(weight, gy.dtype, x.shape[-1], gy.shape[-1], 1)
             ctx.wd = None
             gx = _conv_raw(ge, wd, None, x.shape[-1], ctx.taps, x_encoded=True)
-        if side and gw is None:                  # behind the data gradient (both want every CU's LDS): it then runs beside the
-            gw = _wgrad_side(x, gy, tuple(weight.shape), ctx.taps, ctx.x_enc, ctx.wparam)      # HBM-bound kernels that follow on the main stream
-        if ctx.needs_input_grad[1] and not side:
+        if ctx.needs_input_grad[1]:
             both = _wgrad_bias_raw(x, gy, tuple(weight.shape), ctx.taps, ctx.wparam) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
             if both is not None:
                 gw, gb = both
@@ -720,7 +634,7 @@ def conv(x, weight, bias=None):
     return _Conv.apply(x, weight, bias, False, _cache_ok(), False, None, None)
 
 
-CONV_STATS = os.environ.get("MU_CONV_STATS", "1") != "0"      # debug switch: 0 = always the separate statistics sweep
+CONV_STATS = True      # no longer a switch: conv_stats always takes the epilogue's rows (the name stays for code that reads it)
 
 
 def conv_stats(x, weight, bias=None, want=True, x_encoded=False, dy_link=None):
@@ -728,7 +642,7 @@ def conv_stats(x, weight, bias=None, want=True, x_encoded=False, dy_link=None):
     pass them to bn_act(..., stats=rows) to skip the separate statistics sweep.  fp32x: x_encoded = x was written chunk-encoded by its
     producer (bn_act(..., enc_out=True)); dy_link = EncLink shared with the BatchNorm behind this conv (see EncLink)."""
     x16 = getattr(x, "_mu_x16", None) if x_encoded else None      # the fp16 rounding its producer wrote beside the encoded form (bn_act)
-    if not want or not CONV_STATS:
+    if not want:
         return _Conv.apply(x, weight, bias, False, _cache_ok(), x_encoded, dy_link, x16), None
     return _Conv.apply(x, weight, bias, True, _cache_ok(), x_encoded, dy_link, x16)
 
@@ -889,7 +803,7 @@ def bn_act(x, bn, act=ACT_NONE, res=None, stats=None, res_link=None, enc_out=Fal
         nbt.add_(1)
         nbt = None
     momentum = 0.1 if bn.momentum is None else bn.momentum
-    box = [] if (enc_out and WGRAD_X16 and torch.is_grad_enabled() and _is_x(x)) else None
+    box = [] if (enc_out and torch.is_grad_enabled() and _is_x(x)) else None
     y = _BNAct.apply(x, res, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum, bn.eps, act, nbt,
                      stats if training else None, res_link, enc_out, dx_link, box)
     if box:

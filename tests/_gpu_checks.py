@@ -190,7 +190,7 @@ def check_conv_stats(dtype):
     from maskunet_amd import ops, _lib
     gen = np.random.default_rng(12)
     out = []
-    if dtype == torch.bfloat16 or not ops.CONV_STATS:         # MU_CONV_STATS=0 (debug switch): nothing to check
+    if dtype == torch.bfloat16:
         return [("conv_stats (fp16 / fp32x only)", 0.0, 0.0)]
     shapes = [(2, 16, 32, 64, 128), (3, 32, 32, 128, 256), (8, 64, 64, 64, 128),      # the last runs the persistent kernel
               (2, 16, 32, 64, 64), (2, 24, 16, 128, 64), (3, 8, 48, 64, 128), (1, 40, 16, 256, 256),

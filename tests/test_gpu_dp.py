@@ -428,7 +428,7 @@ dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cu
 import maskunet_amd
 from maskunet_amd.dp import DataParallel
 from oracle import maskunet_oracle as O          # deterministic parameter / input recipe only
-maskunet_amd.set_float32_matmul_precision("high")          # fp32x: the 3x3 weight gradients come out of mu_conv_wgrad_h (round 6)
+maskunet_amd.set_float32_matmul_precision("high")          # fp32x: the 3x3 weight gradients come out of mu_conv_wgrad_h1 (round 6)
 c_out, B = 19, 2
 params = O.make_params(O.unet_state_shapes(3, c_out, False), 91)
 keeps = O.make_keeps(92, B)
@@ -451,7 +451,7 @@ for step in range(3):
             assert torch.equal(p.grad, ref[n]), (step, n)          # one rank: the mean is the gradient itself, bit for bit
             if step:
                 assert p.grad.data_ptr() == ddp.gradient_slice(p).data_ptr(), n
-# the two-term weight-gradient kernels wrote straight into their bucket slices (no copy in between)
+# the one-term weight-gradient kernels wrote straight into their bucket slices (no copy in between)
 model.zero_grad(set_to_none=True)
 with ddp.no_sync():
     F.cross_entropy(ddp(xd), ld).backward()
@@ -468,7 +468,7 @@ print("fp32x exchange ok", flush=True)
 
 
 def test_rccl_single_rank_exchange_in_the_fp32x_mode():
-    """The zero-copy exchange with the round-6 fp32x backward: mu_conv_wgrad_h (two-term weight gradient, pair-reduced slabs) writes the 3x3
+    """The zero-copy exchange with the round-6 fp32x backward: mu_conv_wgrad_h1 (one-term weight gradient on the input's fp16 rounding) writes the 3x3
     weight gradients into DataParallel's bucket slices like the kernels of the other modes; gradients bit-equal to the plain model's."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, "-c", _RCCL_FP32X_WORKER.format(root=ROOT)], env=env, capture_output=True, text=True, timeout=900)
