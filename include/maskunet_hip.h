@@ -146,6 +146,22 @@ int mu_conv_fwd_fused(const void* x, const void* w, const float* scale, const fl
 int mu_conv_stats_rows(int B, int H, int W, int Cin, int Cout, int taps, int dtype);
 int mu_conv_fwd_stats(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin, int Cout, int taps,
                       long x_ld, long y_ld, int dtype, float* stat_part, void* stream);
+/* Which kernel serves a shape -- host-only queries that never touch the device.  Each returns a small stable plan id (> 0; 0 = the
+ * arguments are not served) read from the same selection function the entry point's launch switches on:
+ *   mu_conv_fwd_plan        mu_conv_fwd (with_stats = 0) / mu_conv_fwd_stats with a statistics buffer (with_stats = 1);
+ *   mu_conv_fwd_fused_plan  mu_conv_fwd_fused;
+ *   mu_conv_dgrad_h_plan    mu_conv_dgrad_h (Cin = channels of dy, Cout = channels of dx, as in that entry);
+ *   mu_conv_wgrad_plan      mu_conv_wgrad (pair = 0), mu_conv_wgrad_h1 (dtype MU_F16, pair = 0), mu_conv_wgrad_h (dtype MU_F16, pair = 1);
+ *   mu_conv_wgrad_bias_plan mu_conv_wgrad_bias.
+ * mu_conv_plan_name(op, id): the kernel's name, op = 0 forward, 1 fused, 2 dgrad_h, 3 wgrad; ids run from 1 to mu_conv_plan_count(op) - 1;
+ * NULL for an id outside that range or one this build cannot select. */
+int mu_conv_fwd_plan(int B, int H, int W, int Cin, int Cout, int taps, int dtype, int with_stats);
+int mu_conv_fwd_fused_plan(int B, int H, int W, int Cin, int Cout, int taps, int dtype);
+int mu_conv_dgrad_h_plan(int B, int H, int W, int Cin, int Cout);
+int mu_conv_wgrad_plan(int B, int H, int W, int Cin, int Cout, int taps, int cin_valid, int dtype, int pair);
+int mu_conv_wgrad_bias_plan(int B, int H, int W, int Cin, int Cout, int taps, int cin_valid, int dtype);
+int mu_conv_plan_count(int op);
+const char* mu_conv_plan_name(int op, int id);
 /* fp32x 3x3 layers, two-term data gradient (round 6; autograd of nn.Conv2d k = 3, ade_semantic.py:199,202,400): dx[p][ci] =
  * (1 / S) sum_{tap,co} dy_h[p - shift(tap)][co] * w[co][ci][tap] with dy_h = fp16(S dy) ONE scaled fp16 operand (rows of Cin halves,
  * stride dy_ld halves; Cin = the layer's OUTPUT channels) and w_hl the HL data-gradient block of mu_prep_weight(MU_F32X, taps 9);

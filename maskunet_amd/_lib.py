@@ -43,6 +43,13 @@ SIGNATURES = {
     "mu_prep_weight": (I, [P, P, I, I, I, I, I, I, I, P]),
     "mu_conv_fwd": (I, [P, P, P, P, I, I, I, I, I, I, L, L, I, P]),
     "mu_conv_stats_rows": (I, [I, I, I, I, I, I, I]),
+    "mu_conv_fwd_plan": (I, [I, I, I, I, I, I, I, I]),
+    "mu_conv_fwd_fused_plan": (I, [I, I, I, I, I, I, I]),
+    "mu_conv_dgrad_h_plan": (I, [I, I, I, I, I]),
+    "mu_conv_wgrad_plan": (I, [I, I, I, I, I, I, I, I, I]),
+    "mu_conv_wgrad_bias_plan": (I, [I, I, I, I, I, I, I, I]),
+    "mu_conv_plan_count": (I, [I]),
+    "mu_conv_plan_name": (c_char_p, [I, I]),
     "mu_conv_fwd_stats": (I, [P, P, P, P, I, I, I, I, I, I, L, L, I, P, P]),
     "mu_conv_wgrad_workspace_bytes": (L, [I, I, I, I, I, I]),
     "mu_conv_wgrad": (I, [P, P, P, I, I, I, I, I, I, I, I, L, L, P, L, I, P]),

@@ -1903,6 +1903,50 @@ static Conv3x3Plan conv3x3_pick(int B, int H, int W, int Cin, int Cout, int dtyp
     return {K3_NONE, 0};
 }
 
+// Plan ids of the other conv entry points (mu_conv_*_plan; names: mu_conv_plan_name).  0 = no kernel serves the arguments.  Every launch
+// function below switches on its *_pick, so a query and the launch it describes cannot disagree.
+// Forward (mu_conv_fwd / mu_conv_fwd_stats): the Conv3x3Kernel values for the halo-tile kernels, then the shape-agnostic kernels.
+enum ConvFwdKernel {
+    KF_WIDE192_SB = K3_NT3_64 + 1,      // fp16 1x1, Cout % 192 == 0, Cin == 64: single-stage form, row-staged epilogue
+    KF_WIDE192,                         // fp16 1x1, Cout % 192 == 0
+    KF_HEAD160_SB,                      // fp16 1x1, Cout == 160, Cin == 64
+    KF_HEAD160,                         // fp16 / fp32x 1x1, Cout == 160
+    KF_DMA128, KF_DMA64,                // LDS-DMA kernel, 128 / 64 output channels per tile
+    KF_GEN128, KF_GEN64, KF_GEN32,      // generic register-staged kernel
+    KF_COUNT
+};
+static int conv_fwd_pick(int B, int H, int W, int Cin, int Cout, int taps, int dtype, bool with_stats) {
+    const int es = dtype == MU_F16 ? 2 : 4;
+    if (taps == 9) {
+        const Conv3x3Kernel k3 = conv3x3_pick(B, H, W, Cin, Cout, dtype, with_stats).kernel;
+        if (k3 != K3_NONE) return k3;
+    }
+    if (taps == 1 && dtype == MU_F16 && MU_CONV_WIDE1X1) {
+        if ((Cin * 2) % 128 == 0 && Cout % 192 == 0) return Cin == 64 && MU_NT2_SB ? KF_WIDE192_SB : KF_WIDE192;
+        if ((Cin * 2) % 128 == 0 && Cout == 160) return Cin == 64 && MU_NT2_SB ? KF_HEAD160_SB : KF_HEAD160;
+    }
+    if (taps == 1 && dtype == MU_F32X && MU_CONV_WIDE1X1) {
+        if ((Cin * 4) % 128 == 0 && Cout == 160) return KF_HEAD160;
+    }
+    if ((Cin * es) % 128 == 0 && Cout % 64 == 0) return Cout % 128 == 0 ? KF_DMA128 : KF_DMA64;
+    return Cout % 128 == 0 ? KF_GEN128 : Cout % 64 == 0 ? KF_GEN64 : KF_GEN32;
+}
+
+// Inference epilogue (mu_conv_fwd_fused)
+enum ConvFusedKernel { FF_NONE, FF_NT4F, FF_NT3F_128, FF_NT3F_64, FF_HEAD160, FF_DMA128, FF_DMA64, FF_GEN128, FF_GEN64, FF_GEN32, FF_COUNT };
+static ConvFusedKernel conv_fused_pick(int B, int H, int W, int Cin, int Cout, int taps, int dtype) {
+    (void)B;
+    const int es = dtype == MU_F16 ? 2 : 4;
+    if (taps == 9 && (Cin * es) % 128 == 0 && W % 16 == 0) {
+        if (dtype == MU_F16 && MU_CONV_NT4 && Cout % 128 == 0 && H % 16 == 0 && Cin % 64 == 0) return FF_NT4F;
+        if (Cout % 128 == 0 && H % 8 == 0) return FF_NT3F_128;
+        if (Cout % 64 == 0 && H % 8 == 0) return FF_NT3F_64;
+    }
+    if (taps == 1 && dtype == MU_F16 && (Cin * 2) % 128 == 0 && Cout == 160) return FF_HEAD160;
+    if ((Cin * es) % 128 == 0 && Cout % 64 == 0) return Cout % 128 == 0 ? FF_DMA128 : FF_DMA64;
+    return Cout % 128 == 0 ? FF_GEN128 : Cout % 64 == 0 ? FF_GEN64 : FF_GEN32;
+}
+
 // The same dispatch for the inference epilogue y = act(conv * scale + bias + res): FEPI instantiations of the non-persistent kernels
 // (the persistent ping-pong kernel counts its epilogue's memory operations in hand-placed vmcnt waits and takes no epilogue loads).
 template <typename T, int TAPS>
@@ -1910,38 +1954,44 @@ static int conv_fwd_fused_launch(const T* x, const T* w, const float* scale, con
                                  int Cin, int Cout, long x_ld, long y_ld, hipStream_t st) {
     const long M = (long)B * H * W;
     const int npb = (int)((M + 127) / 128);
-    if (TAPS == 9 && (Cin * (int)sizeof(T)) % 128 == 0 && W % 16 == 0) {
-        if constexpr (sizeof(T) == 2 && MU_CONV_NT4) {
-            if (Cout % 128 == 0 && H % 16 == 0 && Cin % 64 == 0) {
-                conv_nt4f_kernel<<<B * (H / 16) * (W / 16) * (Cout / 128), 512, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
-                return MU_OK;
-            }
-        }
-        if (Cout % 128 == 0 && H % 8 == 0) {
+    constexpr int dtype = sizeof(T) == 2 ? MU_F16 : mu_is_split<T>::value ? MU_F32X : MU_F32;
+    switch (conv_fused_pick(B, H, W, Cin, Cout, TAPS, dtype)) {
+    case FF_NONE:
+        break;
+    case FF_NT4F:
+        if constexpr (sizeof(T) == 2 && TAPS == 9)
+            conv_nt4f_kernel<<<B * (H / 16) * (W / 16) * (Cout / 128), 512, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
+        break;
+    case FF_NT3F_128:
+        if constexpr (TAPS == 9)
             conv_nt3f_kernel<T, 4, 4, 2><<<B * (H / 8) * (W / 16) * (Cout / 128), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
-            return MU_OK;
-        }
-        if (Cout % 64 == 0 && H % 8 == 0) {
+        break;
+    case FF_NT3F_64:
+        if constexpr (TAPS == 9)
             conv_nt3f_kernel<T, 4, 2, 1><<<B * (H / 8) * (W / 16) * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
-            return MU_OK;
-        }
-    }
-    if constexpr (TAPS == 1 && sizeof(T) == 2) {
-        if ((Cin * 2) % 128 == 0 && Cout == 160) {                      // the 150-class head: one tile spans all output channels
+        break;
+    case FF_HEAD160:                                                     // the 150-class head: one tile spans all output channels
+        if constexpr (TAPS == 1 && sizeof(T) == 2)
             conv_nt2_kernel<T, 5, 4, 2, 1, false, true><<<npb, 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, res, scale, act);
-            return MU_OK;
-        }
+        break;
+    case FF_DMA128:                                                      // LDS-DMA version (run-time epilogue arguments)
+        conv_nt2_kernel<T, 4, 4, 2, TAPS, false, true><<<npb * (Cout / 128), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, res, scale, act);
+        break;
+    case FF_DMA64:
+        conv_nt2_kernel<T, 4, 4, 1, TAPS, false, true><<<(int)((M + 255) / 256) * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, res, scale, act);
+        break;
+    case FF_GEN128:
+        conv_nt_kernel<T, 4, 4, 2, TAPS, true><<<npb * (Cout / 128), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
+        break;
+    case FF_GEN64:
+        conv_nt_kernel<T, 4, 2, 1, TAPS, true><<<npb * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
+        break;
+    case FF_GEN32:
+        conv_nt_kernel<T, 2, 2, 1, TAPS, true><<<npb * (Cout / 32), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
+        break;
+    case FF_COUNT:
+        break;
     }
-    if ((Cin * (int)sizeof(T)) % 128 == 0 && Cout % 64 == 0) {         // LDS-DMA version (run-time epilogue arguments)
-        if (Cout % 128 == 0)
-            conv_nt2_kernel<T, 4, 4, 2, TAPS, false, true><<<npb * (Cout / 128), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, res, scale, act);
-        else
-            conv_nt2_kernel<T, 4, 4, 1, TAPS, false, true><<<(int)((M + 255) / 256) * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, res, scale, act);
-        return MU_OK;
-    }
-    if (Cout % 128 == 0) conv_nt_kernel<T, 4, 4, 2, TAPS, true><<<npb * (Cout / 128), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
-    else if (Cout % 64 == 0) conv_nt_kernel<T, 4, 2, 1, TAPS, true><<<npb * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
-    else conv_nt_kernel<T, 2, 2, 1, TAPS, true><<<npb * (Cout / 32), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
     return MU_OK;
 }
 
@@ -1950,76 +2000,69 @@ static int conv_fwd_launch(const T* x, const T* w, const float* bias, T* y, int 
                            long y_ld, hipStream_t st, float* stat_part = nullptr) {
     const long M = (long)B * H * W;
     const int npb = (int)((M + 127) / 128);
-    if constexpr (TAPS == 9) {          // halo-tile kernels (the plan names the fp16 kernels for h16 only and conv_nt4x_kernel for xh32 only)
-        constexpr int dtype = sizeof(T) == 2 ? MU_F16 : mu_is_split<T>::value ? MU_F32X : MU_F32;
-        const int t16 = B * (H / 16) * (W / 16), t8 = B * (H / 8) * (W / 16);
-        switch (conv3x3_pick(B, H, W, Cin, Cout, dtype, stat_part != nullptr).kernel) {
-        case K3_NONE:
-            break;
-        case K3_NT5:
-            if constexpr (sizeof(T) == 2)
-                conv_nt5_kernel<<<t16 < 256 ? t16 : 256, 512, 0, st>>>((const h16*)x, (const h16*)w, bias, (h16*)y, B, H, W, x_ld, y_ld, stat_part, 64);
-            return MU_OK;
-        case K3_NT5_HALVES:
-            if constexpr (sizeof(T) == 2)
-                conv_nt5_kernel<<<dim3(256, 2), 512, 0, st>>>((const h16*)x, (const h16*)w, bias, (h16*)y, B, H, W, x_ld, y_ld, nullptr, 128);
-            return MU_OK;
-        case K3_NT4P:
-            if constexpr (sizeof(T) == 2) conv_nt4p_kernel<<<256, 512, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
-            return MU_OK;
-        case K3_NT4:
-            if constexpr (sizeof(T) == 2) conv_nt4_kernel<<<t16 * (Cout / 128), 512, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
-            return MU_OK;
-        case K3_NT4X:
-            if constexpr (mu_is_split<T>::value)
-                conv_nt4x_kernel<T><<<t16 * (Cout / 128), 512, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
-            return MU_OK;
-        case K3_NT3_128:
-            conv_nt3_kernel<T, 4, 4, 2><<<t8 * (Cout / 128), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
-            return MU_OK;
-        case K3_NT3_64_RING:
-            conv_nt3_kernel<T, 4, 2, 1, true><<<t8 * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
-            return MU_OK;
-        case K3_NT3_64:
-            conv_nt3_kernel<T, 4, 2, 1><<<t8 * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
-            return MU_OK;
-        }
-    }
-    if constexpr (TAPS == 1 && sizeof(T) == 2 && MU_CONV_WIDE1X1) {
-        // 1x1 layers are HBM-bound streams (q/k/v projection of the N = 16384 block: 134 MB in, 402 MB out): a tile that spans all
-        // output channels reads the activations once instead of once per 64-channel tile
-        if ((Cin * 2) % 128 == 0 && Cout % 192 == 0) {
-            if (Cin == 64 && MU_NT2_SB) conv_nt2_kernel<T, 6, 4, 2, 1, true><<<npb * (Cout / 192), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
-            else conv_nt2_kernel<T, 6, 4, 2, 1><<<npb * (Cout / 192), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
-            return MU_OK;
-        }
-        if ((Cin * 2) % 128 == 0 && Cout == 160) {
-            if (Cin == 64 && MU_NT2_SB) conv_nt2_kernel<T, 5, 4, 2, 1, true><<<npb, 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
-            else conv_nt2_kernel<T, 5, 4, 2, 1><<<npb, 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
-            return MU_OK;
-        }
-    }
-    if constexpr (TAPS == 1 && mu_is_split<T>::value && MU_CONV_WIDE1X1) {
-        // fp32x: the 150-class head (64 -> 160) on one tile that spans all output channels instead of five 32-wide tiles of the generic
-        // register-staged kernel (320 -> ~130 us at B = 64)
-        if ((Cin * 4) % 128 == 0 && Cout == 160) {
+    // (the plan names the fp16 kernels for h16 only, conv_nt4x_kernel for xh32 only and the wide 1x1 tiles for the types that have them)
+    constexpr int dtype = sizeof(T) == 2 ? MU_F16 : mu_is_split<T>::value ? MU_F32X : MU_F32;
+    const int t16 = B * (H / 16) * (W / 16), t8 = B * (H / 8) * (W / 16);
+    switch (conv_fwd_pick(B, H, W, Cin, Cout, TAPS, dtype, stat_part != nullptr)) {
+    case K3_NT5:
+        if constexpr (sizeof(T) == 2 && TAPS == 9)
+            conv_nt5_kernel<<<t16 < 256 ? t16 : 256, 512, 0, st>>>((const h16*)x, (const h16*)w, bias, (h16*)y, B, H, W, x_ld, y_ld, stat_part, 64);
+        break;
+    case K3_NT5_HALVES:
+        if constexpr (sizeof(T) == 2 && TAPS == 9)
+            conv_nt5_kernel<<<dim3(256, 2), 512, 0, st>>>((const h16*)x, (const h16*)w, bias, (h16*)y, B, H, W, x_ld, y_ld, nullptr, 128);
+        break;
+    case K3_NT4P:
+        if constexpr (sizeof(T) == 2 && TAPS == 9) conv_nt4p_kernel<<<256, 512, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
+        break;
+    case K3_NT4:
+        if constexpr (sizeof(T) == 2 && TAPS == 9) conv_nt4_kernel<<<t16 * (Cout / 128), 512, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
+        break;
+    case K3_NT4X:
+        if constexpr (mu_is_split<T>::value && TAPS == 9)
+            conv_nt4x_kernel<T><<<t16 * (Cout / 128), 512, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
+        break;
+    case K3_NT3_128:
+        if constexpr (TAPS == 9) conv_nt3_kernel<T, 4, 4, 2><<<t8 * (Cout / 128), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
+        break;
+    case K3_NT3_64_RING:
+        if constexpr (TAPS == 9) conv_nt3_kernel<T, 4, 2, 1, true><<<t8 * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
+        break;
+    case K3_NT3_64:
+        if constexpr (TAPS == 9) conv_nt3_kernel<T, 4, 2, 1><<<t8 * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, stat_part);
+        break;
+    // 1x1 layers are HBM-bound streams (q/k/v projection of the N = 16384 block: 134 MB in, 402 MB out): a tile that spans all
+    // output channels reads the activations once instead of once per 64-channel tile
+    case KF_WIDE192_SB:
+        if constexpr (TAPS == 1 && sizeof(T) == 2) conv_nt2_kernel<T, 6, 4, 2, 1, true><<<npb * (Cout / 192), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
+        break;
+    case KF_WIDE192:
+        if constexpr (TAPS == 1 && sizeof(T) == 2) conv_nt2_kernel<T, 6, 4, 2, 1><<<npb * (Cout / 192), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
+        break;
+    case KF_HEAD160_SB:
+        if constexpr (TAPS == 1 && sizeof(T) == 2) conv_nt2_kernel<T, 5, 4, 2, 1, true><<<npb, 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
+        break;
+    // (fp32x: the 150-class head (64 -> 160) on one tile that spans all output channels instead of five 32-wide tiles of the generic
+    // register-staged kernel: 320 -> ~130 us at B = 64)
+    case KF_HEAD160:
+        if constexpr (TAPS == 1 && (sizeof(T) == 2 || mu_is_split<T>::value))
             conv_nt2_kernel<T, 5, 4, 2, 1><<<npb, 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
-            return MU_OK;
-        }
-    }
-    if ((Cin * (int)sizeof(T)) % 128 == 0 && Cout % 64 == 0) {         // LDS-DMA version
-        if (Cout % 128 == 0)
-            conv_nt2_kernel<T, 4, 4, 2, TAPS><<<npb * (Cout / 128), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
-        else
-            conv_nt2_kernel<T, 4, 4, 1, TAPS><<<(int)((M + 255) / 256) * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
-        return MU_OK;
-    }
-    if (Cout % 128 == 0) {
+        break;
+    case KF_DMA128:                                                      // LDS-DMA version
+        conv_nt2_kernel<T, 4, 4, 2, TAPS><<<npb * (Cout / 128), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
+        break;
+    case KF_DMA64:
+        conv_nt2_kernel<T, 4, 4, 1, TAPS><<<(int)((M + 255) / 256) * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
+        break;
+    case KF_GEN128:
         conv_nt_kernel<T, 4, 4, 2, TAPS><<<npb * (Cout / 128), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
-    } else if (Cout % 64 == 0) {
+        break;
+    case KF_GEN64:
         conv_nt_kernel<T, 4, 2, 1, TAPS><<<npb * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
-    } else {
+        break;
+    case KF_GEN32:
         conv_nt_kernel<T, 2, 2, 1, TAPS><<<npb * (Cout / 32), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
+        break;
     }
     return MU_OK;
 }
@@ -2029,6 +2072,23 @@ static int conv_fwd_launch(const T* x, const T* w, const float* bias, T* y, int 
 extern "C" int mu_conv_stats_rows(int B, int H, int W, int Cin, int Cout, int taps, int dtype) {
     if (taps != 9 || B <= 0 || (dtype != MU_F16 && dtype != MU_F32X)) return 0;
     return conv3x3_pick(B, H, W, Cin, Cout, dtype, true).stat_rows;
+}
+
+static bool conv_plan_args_ok(int B, int H, int W, int Cin, int Cout, int taps, int dtype) {
+    return B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0 && (taps == 1 || taps == 9) &&
+           (dtype == MU_F32 || dtype == MU_F16 || dtype == MU_F32X);
+}
+
+// Host-only queries: the plan id (> 0; 0 = the arguments are not served) of the kernel the entry point launches for these arguments.
+// with_stats = 1: mu_conv_fwd_stats with a statistics buffer (fp16 / fp32x 3x3 layers only).
+extern "C" int mu_conv_fwd_plan(int B, int H, int W, int Cin, int Cout, int taps, int dtype, int with_stats) {
+    if (!conv_plan_args_ok(B, H, W, Cin, Cout, taps, dtype)) return 0;
+    if (with_stats && mu_conv_stats_rows(B, H, W, Cin, Cout, taps, dtype) == 0) return 0;
+    return conv_fwd_pick(B, H, W, Cin, Cout, taps, dtype, with_stats != 0);
+}
+extern "C" int mu_conv_fwd_fused_plan(int B, int H, int W, int Cin, int Cout, int taps, int dtype) {
+    if (!conv_plan_args_ok(B, H, W, Cin, Cout, taps, dtype)) return 0;
+    return conv_fused_pick(B, H, W, Cin, Cout, taps, dtype);
 }
 
 extern "C" int mu_conv_fwd_stats(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin, int Cout,
@@ -2095,6 +2155,20 @@ extern "C" int mu_conv_fwd(const void* x, const void* w, const float* bias, void
 #define MU_DGRAD_H_TERMS 2
 #endif
 static_assert(MU_DGRAD_H_TERMS == 1 || MU_DGRAD_H_TERMS == 2, "MU_DGRAD_H_TERMS: 1 or 2 weight terms");
+enum ConvDgradHKernel { DH_NONE, DH_NT4HL, DH_NT3HL_128, DH_NT3HL_64, DH_GEN128, DH_GEN64, DH_GEN32, DH_COUNT };
+static ConvDgradHKernel conv_dgrad_h_pick(int B, int H, int W, int Cin, int Cout) {
+    (void)B;
+    if (Cin % 64 == 0 && W % 16 == 0 && H % 8 == 0 && Cout % 64 == 0) {
+        if (Cout % 128 == 0 && H % 16 == 0 && MU_CONV_NT4) return DH_NT4HL;
+        return Cout % 128 == 0 ? DH_NT3HL_128 : DH_NT3HL_64;
+    }
+    return Cout % 128 == 0 ? DH_GEN128 : Cout % 64 == 0 ? DH_GEN64 : DH_GEN32;
+}
+// (Cin = channels of dy, Cout = channels of dx, as in mu_conv_dgrad_h)
+extern "C" int mu_conv_dgrad_h_plan(int B, int H, int W, int Cin, int Cout) {
+    if (!conv_plan_args_ok(B, H, W, Cin, Cout, 9, MU_F32X)) return 0;
+    return conv_dgrad_h_pick(B, H, W, Cin, Cout);
+}
 extern "C" int mu_conv_dgrad_h(const void* dy_h, const void* w_hl, const float* dy_scale, void* dx, int B, int H, int W, int Cin, int Cout,
                                long dy_ld, long dx_ld, void* stream) {
     if (!dy_h || !w_hl || !dy_scale || !dx || B <= 0 || H <= 0 || W <= 0) return MU_ERR_ARG;
@@ -2106,19 +2180,27 @@ extern "C" int mu_conv_dgrad_h(const void* dy_h, const void* w_hl, const float* 
     const long M = (long)B * H * W;
     const int npb = (int)((M + 127) / 128);
     constexpr int HL = MU_DGRAD_H_TERMS;
-    if (Cin % 64 == 0 && W % 16 == 0 && H % 8 == 0 && Cout % 64 == 0) {
-        if (Cout % 128 == 0 && H % 16 == 0 && MU_CONV_NT4)
-            conv_nt4hl_kernel<HL><<<B * (H / 16) * (W / 16) * (Cout / 128), 512, 0, st>>>(x, w, y, B, H, W, Cin, Cout, dy_ld, dx_ld, dy_scale);
-        else if (Cout % 128 == 0)
-            conv_nt3hl_kernel<4, 4, 2, false, HL><<<B * (H / 8) * (W / 16) * (Cout / 128), 256, 0, st>>>(x, w, y, B, H, W, Cin, Cout, dy_ld, dx_ld, dy_scale);
-        else
-            conv_nt3hl_kernel<4, 2, 1, true, HL><<<B * (H / 8) * (W / 16) * (Cout / 64), 256, 0, st>>>(x, w, y, B, H, W, Cin, Cout, dy_ld, dx_ld, dy_scale);
-    } else if (Cout % 128 == 0) {
+    switch (conv_dgrad_h_pick(B, H, W, Cin, Cout)) {
+    case DH_NT4HL:
+        conv_nt4hl_kernel<HL><<<B * (H / 16) * (W / 16) * (Cout / 128), 512, 0, st>>>(x, w, y, B, H, W, Cin, Cout, dy_ld, dx_ld, dy_scale);
+        break;
+    case DH_NT3HL_128:
+        conv_nt3hl_kernel<4, 4, 2, false, HL><<<B * (H / 8) * (W / 16) * (Cout / 128), 256, 0, st>>>(x, w, y, B, H, W, Cin, Cout, dy_ld, dx_ld, dy_scale);
+        break;
+    case DH_NT3HL_64:
+        conv_nt3hl_kernel<4, 2, 1, true, HL><<<B * (H / 8) * (W / 16) * (Cout / 64), 256, 0, st>>>(x, w, y, B, H, W, Cin, Cout, dy_ld, dx_ld, dy_scale);
+        break;
+    case DH_GEN128:
         conv_nt_kernel<h16, 4, 4, 2, 9, false, HL><<<npb * (Cout / 128), 256, 0, st>>>(x, w, nullptr, nullptr, B, H, W, Cin, Cout, dy_ld, dx_ld, nullptr, nullptr, 0, y, dy_scale);
-    } else if (Cout % 64 == 0) {
+        break;
+    case DH_GEN64:
         conv_nt_kernel<h16, 4, 2, 1, 9, false, HL><<<npb * (Cout / 64), 256, 0, st>>>(x, w, nullptr, nullptr, B, H, W, Cin, Cout, dy_ld, dx_ld, nullptr, nullptr, 0, y, dy_scale);
-    } else {
+        break;
+    case DH_GEN32:
         conv_nt_kernel<h16, 2, 2, 1, 9, false, HL><<<npb * (Cout / 32), 256, 0, st>>>(x, w, nullptr, nullptr, B, H, W, Cin, Cout, dy_ld, dx_ld, nullptr, nullptr, 0, y, dy_scale);
+        break;
+    case DH_NONE: case DH_COUNT:
+        break;
     }
     MU_CHECK_LAUNCH();
     return MU_OK;
@@ -3554,6 +3636,78 @@ extern "C" int mu_conv_wgrad_bias_supported(int Cin, int Cout, int taps, int dty
     return dtype == MU_F16 && taps == 1 && Cin % 32 == 0 && Cout % 32 == 0 && wgrad_is_wide(bco) ? 1 : 0;
 }
 
+// The weight-gradient plan: which kernel family and variant conv_wgrad_impl launches, with the split plan it launches it with.
+// Ids (mu_conv_wgrad_plan / mu_conv_wgrad_bias_plan): the first-layer kernels, the nine-tap band kernels, the three-tap ring kernel by
+// tile and row staging, the wide 1x1 tiles (with bias partials: + WG_WIDE_BIAS), the generic square tiles.
+enum ConvWgradKernel {
+    WG_NONE,
+    WG_RGB_FMA,
+    WG_RGB2_NPT1, WG_RGB2_NPT2, WG_RGB2_NPT3, WG_RGB2_NPT4, WG_RGB2_NPT5, WG_RGB2_NPT6, WG_RGB2_NPT7, WG_RGB2_NPT8,
+    WG_WG9_NPT1, WG_WG9_NPT2, WG_WG9_NPT3, WG_WG9_NPT4,
+    WG_WG9_W16,
+    WG_WG3_128_W16, WG_WG3_128_ROWS2, WG_WG3_128_FLAT64, WG_WG3_128,
+    WG_WG3_128X64_W16, WG_WG3_128X64, WG_WG3_64X128_W16, WG_WG3_64X128,        // (MU_WG_MIXED builds only)
+    WG_WG3_64_W16, WG_WG3_64_ROWS2, WG_WG3_64_FLAT64, WG_WG3_64,
+    WG_WIDE192_CI64, WG_WIDE192_CI128, WG_WIDE160_CI64, WG_WIDE160_CI128,
+    WG_WIDE192_CI64_BIAS, WG_WIDE192_CI128_BIAS, WG_WIDE160_CI64_BIAS, WG_WIDE160_CI128_BIAS,
+    WG_GEN128, WG_GEN64, WG_GEN32,
+    WG_COUNT
+};
+static const int WG_WIDE_BIAS = WG_WIDE192_CI64_BIAS - WG_WIDE192_CI64;
+struct ConvWgradPlan {
+    int id;
+    int err;                // id == WG_NONE: the status conv_wgrad_impl returns
+    int bco, bci, nsplit;   // generic / wide tiles (wgrad_tile, wgrad_plan) -- nsplit: the three-tap kernel's count when that one is picked
+    long pps;
+    int tco, tci;           // three-tap kernel
+    int nb9, rpb9;          // nine-tap band kernels
+};
+static ConvWgradPlan conv_wgrad_pick(int B, int H, int W, int Cin, int Cout, int taps, int cin_valid, int dtype, bool pair, bool with_bias) {
+    ConvWgradPlan p = {WG_NONE, MU_ERR_ARG, 0, 0, 0, 0, 0, 0, 0, 0};
+    // (fp32x: the wide 160-channel tile of the class head as well -- 32 x 32 tiles otherwise; the 192-wide q/k/v tiles stay fp16-only:
+    //  64 x 64 tiles serve those layers)
+    wgrad_tile(Cin, Cout, &p.bco, &p.bci, taps, dtype == MU_F16 || (dtype == MU_F32X && Cout == 160));
+    wgrad_plan((long)B * H * W, Cin, Cout, taps, p.bco, p.bci, &p.nsplit, &p.pps);
+    if (taps == 9 && cin_valid <= 3 && Cout % 64 == 0 && W <= MU_RGB_MAXW && (dtype == MU_F16 || dtype == MU_F32 || dtype == MU_F32X)) {
+        if (dtype == MU_F16 && MU_RGB2 && W % 32 == 0) p.id = WG_RGB2_NPT1 + (W / 32 > 8 ? 8 : W / 32) - 1;
+        else p.id = WG_RGB_FMA;
+        return p;
+    }
+    if (wgrad9_choose(B, H, W, Cin, Cout, taps, dtype, &p.nb9, &p.rpb9, pair)) {
+        p.id = WG_WG9_NPT1 + (W / 32 > 4 ? 4 : W / 32) - 1;
+        p.nsplit = p.nb9;
+        return p;
+    }
+    if (wgrad9_w16_choose(B, H, W, Cin, Cout, taps, dtype, &p.nb9, &p.rpb9, pair)) {
+        p.id = WG_WG9_W16;
+        p.nsplit = p.nb9;
+        return p;
+    }
+    if (wgrad3_choose(H, W, Cin, Cout, taps, dtype, &p.tco, &p.tci)) {
+        wgrad3_plan((long)B * H * W, Cin, Cout, p.tco, p.tci, &p.nsplit, &p.pps);
+        const bool two_row32 = W == 32 && H % 2 == 0, flat64 = W % 64 == 0;
+        if (p.tco == 128 && p.tci == 128)
+            p.id = W == 16 ? WG_WG3_128_W16 : two_row32 && MU_WG_SPS2 ? WG_WG3_128_ROWS2 : flat64 && MU_WG_SPS2 ? WG_WG3_128_FLAT64 : WG_WG3_128;
+        else if (p.tco == 128) p.id = W == 16 ? WG_WG3_128X64_W16 : WG_WG3_128X64;
+        else if (p.tci == 128) p.id = W == 16 ? WG_WG3_64X128_W16 : WG_WG3_64X128;
+        else p.id = W == 16 ? WG_WG3_64_W16 : two_row32 && MU_WG_SPS2_64 ? WG_WG3_64_ROWS2 : flat64 && MU_WG_SPS2_64 ? WG_WG3_64_FLAT64 : WG_WG3_64;
+        return p;
+    }
+    if (dtype != MU_F16 && dtype != MU_F32 && dtype != MU_F32X) return p;
+    // (3x3 layers of the fp32x mode: mu_conv_wgrad_h -- fp16-pair input, one scaled fp16 dy; only the <= 3-channel first layer, served above on
+    //  plain operands, comes through here with taps = 9)
+    if (dtype == MU_F32X && taps == 9) return p;
+    const bool wide_ok = taps == 1 && (dtype == MU_F16 || dtype == MU_F32X);      // (the types wgrad_launch has wide tiles for)
+    if (wide_ok && wgrad_is_wide(p.bco)) {
+        p.id = (p.bco == 192 ? (p.bci == 64 ? WG_WIDE192_CI64 : WG_WIDE192_CI128) : (p.bci == 64 ? WG_WIDE160_CI64 : WG_WIDE160_CI128)) +
+               (with_bias ? WG_WIDE_BIAS : 0);
+        return p;
+    }
+    if (with_bias) { p.err = MU_ERR_SHAPE; return p; }
+    p.id = p.bco == 128 ? WG_GEN128 : p.bco == 64 ? WG_GEN64 : WG_GEN32;
+    return p;
+}
+
 // pair_I > 0 (mu_conv_wgrad_h): x is the 16-bit view of a chunk-encoded fp32x input (Cin = 2 x its channels), dy the scaled fp16 gradient;
 // the slabs are reduced pairwise into dw_oihw[cout_valid][pair_I][taps] and multiplied by oscale[1]
 static int conv_wgrad_impl(const void* x, const void* dy, float* dw_oihw, float* db, int B, int H, int W, int Cin, int Cout, int taps,
@@ -3564,21 +3718,25 @@ static int conv_wgrad_impl(const void* x, const void* dy, float* dw_oihw, float*
     if (Cin % 32 || Cout % 32 || x_ld < Cin || dy_ld < Cout || x_ld % 8 || dy_ld % 8) return MU_ERR_SHAPE;
     if (cin_valid <= 0 || cin_valid > Cin || cout_valid <= 0 || cout_valid > Cout) return MU_ERR_ARG;
     if (taps != 1 && taps != 9) return MU_ERR_ARG;
-    int bco, bci, nsplit; long pps;
-    // (fp32x: the wide 160-channel tile of the class head as well -- 32 x 32 tiles otherwise; the 192-wide q/k/v tiles stay fp16-only:
-    //  64 x 64 tiles serve those layers)
-    wgrad_tile(Cin, Cout, &bco, &bci, taps, dtype == MU_F16 || (dtype == MU_F32X && Cout == 160));
-    wgrad_plan((long)B * H * W, Cin, Cout, taps, bco, bci, &nsplit, &pps);
+    const ConvWgradPlan plan = conv_wgrad_pick(B, H, W, Cin, Cout, taps, cin_valid, dtype, pair_I > 0, db != nullptr);
+    const int bco = plan.bco, bci = plan.bci, tco = plan.tco, tci = plan.tci, nb9 = plan.nb9, rpb9 = plan.rpb9, nsplit = plan.nsplit;
+    const long pps = plan.pps;
     hipStream_t st = (hipStream_t)stream;
     float* part = (float*)workspace;
-    if (taps == 9 && cin_valid <= 3 && Cout % 64 == 0 && W <= MU_RGB_MAXW && (dtype == MU_F16 || dtype == MU_F32 || dtype == MU_F32X)) {
+    const h16 *xh = (const h16*)x, *dyh = (const h16*)dy;
+    switch (plan.id) {
+    case WG_NONE:
+        return plan.err;
+    case WG_RGB_FMA:
+    case WG_RGB2_NPT1: case WG_RGB2_NPT2: case WG_RGB2_NPT3: case WG_RGB2_NPT4:
+    case WG_RGB2_NPT5: case WG_RGB2_NPT6: case WG_RGB2_NPT7: case WG_RGB2_NPT8: {
         // (plain-FMA kernel: the fp32x mode runs it as fp32)
         long nb = ws_bytes / ((long)9 * Cout * 4 * (long)sizeof(float));
         if (nb > MU_RGB_MAXBLK) nb = MU_RGB_MAXBLK;
         if (nb > (long)B * H) nb = (long)B * H;
         if (nb < 1) return MU_ERR_WORKSPACE;
         dim3 grid((int)nb, Cout / 64);
-        if (dtype == MU_F16 && MU_RGB2 && W % 32 == 0 && x_ld % 4 == 0) {
+        if (plan.id != WG_RGB_FMA) {
             // matrix-core form: a band of consecutive image rows per block (the grid covers the rows exactly: an idle block writes a zero slab)
             if (nb > 768) nb = 768;                            // three 45 KB blocks per CU: one round
             const int rpb = (int)(((long)B * H + nb - 1) / nb);
@@ -3586,14 +3744,15 @@ static int conv_wgrad_impl(const void* x, const void* dy, float* dw_oihw, float*
             grid.x = (int)nb;
             const size_t lds = ((size_t)2 * W * MU_RGB2_DYS + 5 * (size_t)(W + 2) * 4) * sizeof(h16);
             const size_t lds_red = (size_t)4 * 64 * 16 * sizeof(float);
-#define RGB2(NPT) wgrad_rgb2_kernel<NPT><<<grid, 256, lds > lds_red ? lds : lds_red, st>>>((const h16*)x, (const h16*)dy, part, B, H, W, Cout, x_ld, dy_ld, rpb)
-            switch (W / 32) {
-                case 1: RGB2(1); break; case 2: RGB2(2); break; case 3: RGB2(3); break; case 4: RGB2(4); break;
-                case 5: RGB2(5); break; case 6: RGB2(6); break; case 7: RGB2(7); break; default: RGB2(8); break;
+#define RGB2(NPT) wgrad_rgb2_kernel<NPT><<<grid, 256, lds > lds_red ? lds : lds_red, st>>>(xh, dyh, part, B, H, W, Cout, x_ld, dy_ld, rpb)
+            switch (plan.id) {
+                case WG_RGB2_NPT1: RGB2(1); break; case WG_RGB2_NPT2: RGB2(2); break; case WG_RGB2_NPT3: RGB2(3); break;
+                case WG_RGB2_NPT4: RGB2(4); break; case WG_RGB2_NPT5: RGB2(5); break; case WG_RGB2_NPT6: RGB2(6); break;
+                case WG_RGB2_NPT7: RGB2(7); break; default: RGB2(8); break;
             }
 #undef RGB2
         }
-        else if (dtype == MU_F16) wgrad_rgb_kernel<h16><<<grid, 256, 0, st>>>((const h16*)x, (const h16*)dy, part, B, H, W, Cout, cin_valid, x_ld, dy_ld);
+        else if (dtype == MU_F16) wgrad_rgb_kernel<h16><<<grid, 256, 0, st>>>(xh, dyh, part, B, H, W, Cout, cin_valid, x_ld, dy_ld);
         else wgrad_rgb_kernel<float><<<grid, 256, 0, st>>>((const float*)x, (const float*)dy, part, B, H, W, Cout, cin_valid, x_ld, dy_ld);
         const long n = (long)cout_valid * cin_valid * 9;
         const long nblk = (n + 63) / 64;
@@ -3601,66 +3760,70 @@ static int conv_wgrad_impl(const void* x, const void* dy, float* dw_oihw, float*
         MU_CHECK_LAUNCH();
         return MU_OK;
     }
-    int tco, tci, nb9, rpb9;
-    if (wgrad9_choose(B, H, W, Cin, Cout, taps, dtype, &nb9, &rpb9, pair_I > 0) && x_ld % 8 == 0 && dy_ld % 8 == 0) {
+    case WG_WG9_NPT1: case WG_WG9_NPT2: case WG_WG9_NPT3: case WG_WG9_NPT4: {
         if (ws_bytes < (long)nb9 * taps * Cout * Cin * (long)sizeof(float)) return MU_ERR_WORKSPACE;
         const dim3 grid9(nb9, Cout / 64, Cin / 64);
-#define WG9(NPT) conv_wgrad9_kernel<NPT><<<grid9, 256, 0, st>>>((const h16*)x, (const h16*)dy, part, B, H, W, Cin, Cout, x_ld, dy_ld, rpb9)
-        switch (W / 32) { case 1: WG9(1); break; case 2: WG9(2); break; case 3: WG9(3); break; default: WG9(4); break; }
+#define WG9(NPT) conv_wgrad9_kernel<NPT><<<grid9, 256, 0, st>>>(xh, dyh, part, B, H, W, Cin, Cout, x_ld, dy_ld, rpb9)
+        switch (plan.id) { case WG_WG9_NPT1: WG9(1); break; case WG_WG9_NPT2: WG9(2); break; case WG_WG9_NPT3: WG9(3); break; default: WG9(4); break; }
 #undef WG9
-        nsplit = nb9;
-    } else if (wgrad9_w16_choose(B, H, W, Cin, Cout, taps, dtype, &nb9, &rpb9, pair_I > 0) && x_ld % 8 == 0 && dy_ld % 8 == 0) {
+        break;
+    }
+    case WG_WG9_W16:
         if (ws_bytes < (long)nb9 * taps * Cout * Cin * (long)sizeof(float)) return MU_ERR_WORKSPACE;
-        conv_wgrad9_w16_kernel<<<dim3(nb9, Cout / 64, Cin / 64), 256, 0, st>>>((const h16*)x, (const h16*)dy, part, B, H, Cin, Cout, x_ld, dy_ld, rpb9);
-        nsplit = nb9;
-    } else
-    if (wgrad3_choose(H, W, Cin, Cout, taps, dtype, &tco, &tci)) {
-        wgrad3_plan((long)B * H * W, Cin, Cout, tco, tci, &nsplit, &pps);
+        conv_wgrad9_w16_kernel<<<dim3(nb9, Cout / 64, Cin / 64), 256, 0, st>>>(xh, dyh, part, B, H, Cin, Cout, x_ld, dy_ld, rpb9);
+        break;
+    case WG_WG3_128_W16: case WG_WG3_128_ROWS2: case WG_WG3_128_FLAT64: case WG_WG3_128:
+    case WG_WG3_128X64_W16: case WG_WG3_128X64: case WG_WG3_64X128_W16: case WG_WG3_64X128:
+    case WG_WG3_64_W16: case WG_WG3_64_ROWS2: case WG_WG3_64_FLAT64: case WG_WG3_64: {
         if (ws_bytes < (long)nsplit * taps * Cout * Cin * (long)sizeof(float)) return MU_ERR_WORKSPACE;
         const int grid = 3 * (Cout / tco) * (Cin / tci) * nsplit;
-        const h16 *xh = (const h16*)x, *dyh = (const h16*)dy;
 #define WG3(...) conv_wgrad3_kernel<h16, __VA_ARGS__><<<grid, (tco == 128 && tci == 128) ? 512 : 256, 0, st>>>(xh, dyh, part, B, H, W, Cin, Cout, x_ld, dy_ld, nsplit, pps)
-        const bool two_row32 = W == 32 && H % 2 == 0, flat64 = W % 64 == 0;
-        if (tco == 128 && tci == 128) {   // 8 waves, 64x32 tile x 3 taps per wave (96 accumulators): 2 waves/SIMD
-            if (W == 16) WG3(4, 2, 2, 8, true);
-            else if (two_row32 && MU_WG_SPS2 && MU_WG_PP == 2) WG3(4, 2, 2, 8, true, 2, true);      // (W = 32: +2.6 % slower, opt-in)
-            else if (two_row32 && MU_WG_SPS2) WG3(4, 2, 2, 8, true, 2);
-            else if (flat64 && MU_WG_SPS2 && MU_WG_PP) WG3(4, 2, 2, 8, false, 2, true);
-            else if (flat64 && MU_WG_SPS2) WG3(4, 2, 2, 8, false, 2);
-            else WG3(4, 2, 2, 8);
-        } else if (tco == 128) {          // 128 x 64: 4 waves, 64x32 per wave
-            if (W == 16) WG3(4, 2, 2, 4, true);
-            else WG3(4, 2, 2, 4);
-        } else if (tci == 128) {          // 64 x 128: 4 waves, 32x64 per wave
-            if (W == 16) WG3(2, 4, 2, 4, true);
-            else WG3(2, 4, 2, 4);
-        } else {
-            if (W == 16) WG3(2, 2, 2, 4, true);
-            else if (two_row32 && MU_WG_SPS2_64) WG3(2, 2, 2, 4, true, 2);
-            else if (flat64 && MU_WG_SPS2_64) WG3(2, 2, 2, 4, false, 2);
-            else WG3(2, 2, 2);
+        switch (plan.id) {
+        // 128 x 128: 8 waves, 64x32 tile x 3 taps per wave (96 accumulators): 2 waves/SIMD
+        case WG_WG3_128_W16: WG3(4, 2, 2, 8, true); break;
+        case WG_WG3_128_ROWS2:
+            if (MU_WG_PP == 2) WG3(4, 2, 2, 8, true, 2, true);      // (W = 32: +2.6 % slower, opt-in)
+            else WG3(4, 2, 2, 8, true, 2);
+            break;
+        case WG_WG3_128_FLAT64:
+            if (MU_WG_PP) WG3(4, 2, 2, 8, false, 2, true);
+            else WG3(4, 2, 2, 8, false, 2);
+            break;
+        case WG_WG3_128: WG3(4, 2, 2, 8); break;
+        // 128 x 64: 4 waves, 64x32 per wave
+        case WG_WG3_128X64_W16: WG3(4, 2, 2, 4, true); break;
+        case WG_WG3_128X64: WG3(4, 2, 2, 4); break;
+        // 64 x 128: 4 waves, 32x64 per wave
+        case WG_WG3_64X128_W16: WG3(2, 4, 2, 4, true); break;
+        case WG_WG3_64X128: WG3(2, 4, 2, 4); break;
+        case WG_WG3_64_W16: WG3(2, 2, 2, 4, true); break;
+        case WG_WG3_64_ROWS2: WG3(2, 2, 2, 4, true, 2); break;
+        case WG_WG3_64_FLAT64: WG3(2, 2, 2, 4, false, 2); break;
+        default: WG3(2, 2, 2); break;
         }
 #undef WG3
-    } else if (ws_bytes < (long)nsplit * taps * Cout * Cin * (long)sizeof(float)) {
-        return MU_ERR_WORKSPACE;
-    } else if (dtype == MU_F16) {
-        if (taps == 9) wgrad_launch<h16, 9>((const h16*)x, (const h16*)dy, part, B, H, W, Cin, Cout, x_ld, dy_ld, bco, nsplit, pps, st);
-        else {
-            float* bias_part = db ? part + (long)nsplit * Cout * Cin : nullptr;
-            if (db && ws_bytes < ((long)nsplit * Cout * Cin + (long)nsplit * Cout) * (long)sizeof(float)) return MU_ERR_WORKSPACE;
-            int rc = wgrad_launch<h16, 1>((const h16*)x, (const h16*)dy, part, B, H, W, Cin, Cout, x_ld, dy_ld, bco, nsplit, pps, st, bci, bias_part);
-            if (rc) return rc;
-            if (db) wgrad_bias_reduce_kernel<<<mu_cdiv(cout_valid, 16), 256, 0, st>>>(bias_part, nsplit, Cout, cout_valid, db);
+        break;
+    }
+    default: {          // wide 1x1 tiles and the generic square tiles (wgrad_launch reads the tile from bco / bci)
+        if (ws_bytes < (long)nsplit * taps * Cout * Cin * (long)sizeof(float)) return MU_ERR_WORKSPACE;
+        if (dtype == MU_F16) {
+            if (taps == 9) wgrad_launch<h16, 9>(xh, dyh, part, B, H, W, Cin, Cout, x_ld, dy_ld, bco, nsplit, pps, st);
+            else {
+                float* bias_part = db ? part + (long)nsplit * Cout * Cin : nullptr;
+                if (db && ws_bytes < ((long)nsplit * Cout * Cin + (long)nsplit * Cout) * (long)sizeof(float)) return MU_ERR_WORKSPACE;
+                int rc = wgrad_launch<h16, 1>(xh, dyh, part, B, H, W, Cin, Cout, x_ld, dy_ld, bco, nsplit, pps, st, bci, bias_part);
+                if (rc) return rc;
+                if (db) wgrad_bias_reduce_kernel<<<mu_cdiv(cout_valid, 16), 256, 0, st>>>(bias_part, nsplit, Cout, cout_valid, db);
+            }
+        } else if (dtype == MU_F32) {
+            if (taps == 9) wgrad_launch<float, 9>((const float*)x, (const float*)dy, part, B, H, W, Cin, Cout, x_ld, dy_ld, bco, nsplit, pps, st);
+            else wgrad_launch<float, 1>((const float*)x, (const float*)dy, part, B, H, W, Cin, Cout, x_ld, dy_ld, bco, nsplit, pps, st);
+        } else {
+            wgrad_launch<xf32, 1>((const xf32*)x, (const xf32*)dy, part, B, H, W, Cin, Cout, x_ld, dy_ld, bco, nsplit, pps, st, bci);
         }
-    } else if (dtype == MU_F32) {
-        if (taps == 9) wgrad_launch<float, 9>((const float*)x, (const float*)dy, part, B, H, W, Cin, Cout, x_ld, dy_ld, bco, nsplit, pps, st);
-        else wgrad_launch<float, 1>((const float*)x, (const float*)dy, part, B, H, W, Cin, Cout, x_ld, dy_ld, bco, nsplit, pps, st);
-    } else if (dtype == MU_F32X) {
-        // (3x3 layers of this mode: mu_conv_wgrad_h -- fp16-pair input, one scaled fp16 dy; only the <= 3-channel first layer, served above on
-        //  plain operands, comes through here with taps = 9)
-        if (taps == 9) return MU_ERR_ARG;
-        else wgrad_launch<xf32, 1>((const xf32*)x, (const xf32*)dy, part, B, H, W, Cin, Cout, x_ld, dy_ld, bco, nsplit, pps, st, bci);
-    } else return MU_ERR_ARG;
+        break;
+    }
+    }
     if (pair_I > 0) {
         const long n2 = (long)cout_valid * pair_I * taps;
         if (nsplit >= 16) {
@@ -3683,6 +3846,52 @@ static int conv_wgrad_impl(const void* x, const void* dy, float* dw_oihw, float*
     }
     MU_CHECK_LAUNCH();
     return MU_OK;
+}
+
+// Host-only: the plan id of mu_conv_wgrad (pair = 0), mu_conv_wgrad_h1 (dtype MU_F16, pair = 0) and mu_conv_wgrad_h (pair = 1: Cin = the
+// layer's fp32 channels, as that entry takes them) for these arguments; mu_conv_wgrad_bias_plan: of mu_conv_wgrad_bias (0 where
+// mu_conv_wgrad_bias_supported is 0).
+static int conv_wgrad_plan_query(int B, int H, int W, int Cin, int Cout, int taps, int cin_valid, int dtype, int pair, bool with_bias) {
+    if (!conv_plan_args_ok(B, H, W, Cin, Cout, taps, dtype) || cin_valid <= 0 || cin_valid > Cin) return 0;
+    if (pair) {
+        if (dtype != MU_F16 || taps != 9 || cin_valid <= 3 || with_bias) return 0;
+        return conv_wgrad_pick(B, H, W, 2 * Cin, Cout, 9, 2 * Cin, MU_F16, true, false).id;
+    }
+    if (with_bias && !mu_conv_wgrad_bias_supported(Cin, Cout, taps, dtype)) return 0;
+    return conv_wgrad_pick(B, H, W, Cin, Cout, taps, cin_valid, dtype, false, with_bias).id;
+}
+extern "C" int mu_conv_wgrad_plan(int B, int H, int W, int Cin, int Cout, int taps, int cin_valid, int dtype, int pair) {
+    return conv_wgrad_plan_query(B, H, W, Cin, Cout, taps, cin_valid, dtype, pair, false);
+}
+extern "C" int mu_conv_wgrad_bias_plan(int B, int H, int W, int Cin, int Cout, int taps, int cin_valid, int dtype) {
+    return conv_wgrad_plan_query(B, H, W, Cin, Cout, taps, cin_valid, dtype, 0, true);
+}
+
+// One table of plan names: op 0 = mu_conv_fwd_plan, 1 = mu_conv_fwd_fused_plan, 2 = mu_conv_dgrad_h_plan, 3 = mu_conv_wgrad_plan /
+// mu_conv_wgrad_bias_plan.  mu_conv_plan_count(op): ids run from 1 to count - 1; mu_conv_plan_name: NULL for an id outside that range and
+// for an id this build cannot reach (the mixed three-tap tiles without MU_WG_MIXED).
+static const char* const conv_fwd_names[KF_COUNT] = {
+    nullptr, "nt5", "nt5_halves", "nt4p", "nt4", "nt4x", "nt3_128", "nt3_64_ring", "nt3_64",
+    "wide192_sb", "wide192", "head160_sb", "head160", "dma128", "dma64", "gen128", "gen64", "gen32"};
+static const char* const conv_fused_names[FF_COUNT] = {
+    nullptr, "nt4f", "nt3f_128", "nt3f_64", "head160f", "dma128f", "dma64f", "gen128f", "gen64f", "gen32f"};
+static const char* const conv_dgrad_h_names[DH_COUNT] = {nullptr, "nt4hl", "nt3hl_128", "nt3hl_64", "gen128hl", "gen64hl", "gen32hl"};
+static const char* const conv_wgrad_names[WG_COUNT] = {
+    nullptr, "rgb_fma", "rgb2_npt1", "rgb2_npt2", "rgb2_npt3", "rgb2_npt4", "rgb2_npt5", "rgb2_npt6", "rgb2_npt7", "rgb2_npt8",
+    "wgrad9_npt1", "wgrad9_npt2", "wgrad9_npt3", "wgrad9_npt4", "wgrad9_w16",
+    "wgrad3_128_w16", "wgrad3_128_rows2", "wgrad3_128_flat64", "wgrad3_128",
+    "wgrad3_128x64_w16", "wgrad3_128x64", "wgrad3_64x128_w16", "wgrad3_64x128",
+    "wgrad3_64_w16", "wgrad3_64_rows2", "wgrad3_64_flat64", "wgrad3_64",
+    "wide192_ci64", "wide192_ci128", "wide160_ci64", "wide160_ci128",
+    "wide192_ci64_bias", "wide192_ci128_bias", "wide160_ci64_bias", "wide160_ci128_bias",
+    "gen128", "gen64", "gen32"};
+extern "C" int mu_conv_plan_count(int op) {
+    return op == 0 ? KF_COUNT : op == 1 ? FF_COUNT : op == 2 ? DH_COUNT : op == 3 ? WG_COUNT : 0;
+}
+extern "C" const char* mu_conv_plan_name(int op, int id) {
+    if (id <= 0 || id >= mu_conv_plan_count(op)) return nullptr;
+    if (op == 3 && !MU_WG_MIXED && id >= WG_WG3_128X64_W16 && id <= WG_WG3_64X128) return nullptr;
+    return op == 0 ? conv_fwd_names[id] : op == 1 ? conv_fused_names[id] : op == 2 ? conv_dgrad_h_names[id] : conv_wgrad_names[id];
 }
 
 extern "C" int mu_conv_wgrad(const void* x, const void* dy, float* dw_oihw, int B, int H, int W, int Cin, int Cout, int taps,

@@ -126,38 +126,8 @@ def check_conv(dtype, cases=None):
     from maskunet_amd import ops
     gen = np.random.default_rng(3)
     out = []
-    cases = cases or [(2, 12, 12, 32, 32, 3), (1, 16, 16, 64, 128, 3), (2, 8, 8, 128, 64, 3), (1, 10, 6, 19, 32, 3),
-                      (1, 8, 8, 64, 150, 1), (2, 9, 7, 256, 256, 3), (1, 16, 16, 3, 64, 3), (2, 8, 8, 32, 1, 1),
-                      (1, 6, 6, 512, 256, 3),
-                      # W % 32 == 0: exercises the 3-taps-per-block weight-gradient kernel (fp16) incl. row/image borders
-                      (2, 32, 32, 64, 64, 3), (1, 64, 32, 128, 128, 3), (2, 16, 64, 64, 128, 3), (1, 32, 32, 256, 128, 3),
-                      # 16x16-tile ping-pong kernel: odd number of 64-channel chunks, non-square image, two channel blocks
-                      (2, 32, 48, 192, 256, 3), (3, 16, 16, 128, 128, 3),
-                      # first-layer weight-gradient kernel (<= 3 valid input channels): ragged width, two channel blocks, 1 channel
-                      (2, 20, 24, 3, 128, 3), (1, 8, 8, 1, 64, 3),
-                      # its matrix-core form (fp16, W % 32 == 0): one row per block, two channel blocks, 2 valid channels, bands of two rows
-                      # that straddle image borders (4 x 255 rows over 512 blocks), four k-steps per row
-                      (2, 8, 32, 3, 64, 3), (1, 5, 64, 3, 128, 3), (3, 4, 96, 2, 64, 3), (4, 255, 32, 3, 64, 3), (1, 6, 128, 3, 64, 3),
-                      # nine-taps-per-block weight-gradient kernel (fp16, 64-channel-wide layers, W % 32 == 0, W <= 128): bands of two rows
-                      # that straddle image borders, W = 96 / 128, both mixed channel shapes
-                      (4, 99, 32, 64, 64, 3), (2, 5, 96, 64, 64, 3), (1, 6, 128, 128, 64, 3), (2, 7, 64, 64, 128, 3),
-                      # its 16-pixel-wide form (a k-step = a pair of image rows): bands of four rows over images of six rows, 128 -> 256
-                      (100, 6, 16, 64, 64, 3), (3, 4, 16, 128, 256, 3),
-                      # weights-resident kernel in its two-halves form (fp16, 64 -> 128 without a statistics epilogue, >= 1024 tiles)
-                      (16, 128, 128, 64, 128, 3),
-                      # 16-pixel-wide images through the 3-tap weight-gradient kernel (two image rows per stage)
-                      (2, 8, 16, 256, 128, 3), (5, 16, 16, 64, 64, 3),
-                      # shapes around the kernel-selection edges: 80-wide (16x16 conv tiles, one-tap weight-grad), 192-wide (64-pixel
-                      # weight-grad stages), 32-wide with even / odd height (two-row stages / flat stages), persistent conv with a tail
-                      (2, 48, 80, 64, 128, 3), (1, 32, 192, 128, 128, 3), (2, 6, 32, 128, 128, 3), (1, 5, 32, 128, 128, 3),
-                      (5, 64, 64, 64, 128, 3),
-                      # weights-resident persistent kernel (fp16, 64 -> 64, >= 512 tiles of 16 x 16 pixels): two to three tiles per block
-                      # (each of its two wave groups one or two), ragged tail, non-square images
-                      (10, 128, 112, 64, 64, 3), (3, 192, 240, 64, 64, 3),
-                      # 1x1 layers: q/k/v projection shapes (Cout = 3C: row-staged epilogue, single-stage Cin = 64 kernel, wide
-                      # weight-grad tiles), their data-gradient shape, the 150-class head with a ragged pixel count
-                      (2, 9, 7, 64, 192, 1), (1, 16, 16, 128, 384, 1), (2, 5, 5, 256, 768, 1), (3, 7, 9, 192, 64, 1), (2, 33, 17, 64, 150, 1),
-                      (1, 40, 40, 64, 192, 1)]
+    from tests._conv_cases import CONV_CASES
+    cases = cases or CONV_CASES
     for (B, H, W, Cin, Cout, k) in cases:
         x = _rnd(gen, B, Cin, H, W)
         w = _rnd(gen, Cout, Cin, k, k, scale=1.0 / math.sqrt(Cin * k * k))
@@ -180,6 +150,51 @@ def check_conv(dtype, cases=None):
                 (tag + " dw", _rel_err(wd.grad, wr.grad), tol)]
         if b is not None:
             out.append((tag + " db", _rel_err(bd.grad, br.grad), tol))
+    return out
+
+
+def check_conv_fused(dtype, fp32x=False):
+    """mu_conv_fwd_fused through the C ABI on Gaussian inputs against fp64: y = act(conv(x, w) * scale + shift + res) with a random
+    positive scale and a random shift, every activation, with and without the residual, over the fused cases of the shape table
+    (every branch of the fused dispatch: see tests/test_conv_plan_coverage.py)."""
+    from maskunet_amd import _lib
+    from tests import _conv_cases as CC
+    gen = np.random.default_rng(17)
+    out = []
+    code = _lib.MU_F32X if fp32x else _lib.dt(dtype)
+    st = _lib.stream()
+    for c in CC.LAYERS:
+        if c["heavy"]:
+            continue
+        B, H, W, Cin, Cout, taps, cin, cout = c["B"], c["H"], c["W"], c["Cin"], c["Cout"], c["taps"], c["cin"], c["cout"]
+        k = 3 if taps == 9 else 1
+        kern = CC.plan_name("fused", _lib.load().mu_conv_fwd_fused_plan(B, H, W, Cin, Cout, taps, code))
+        x = _rnd(gen, B, cin, H, W).to(dtype).float()
+        w = _rnd(gen, cout, cin, k, k, scale=1.0 / math.sqrt(cin * k * k))
+        scale = torch.from_numpy(gen.uniform(0.5, 1.5, Cout).astype(np.float32))
+        shift = _rnd(gen, Cout, scale=0.3)
+        res = _rnd(gen, B, H, W, Cout).to(dtype).float()
+        xd = torch.zeros(B, H, W, Cin)
+        xd[..., :cin] = x.permute(0, 2, 3, 1)
+        xd = xd.to(DEV, dtype)
+        if fp32x:
+            xe = torch.empty_like(xd)
+            _lib.call("mu_split_encode_h4" if taps == 9 else "mu_split_encode", xd.data_ptr(), xe.data_ptr(), xd.numel(), st)
+            xd = xe
+        wd = w.to(DEV).contiguous()
+        wp = torch.empty(taps * Cout * Cin, dtype=dtype, device=DEV)
+        _lib.call("mu_prep_weight", wd.data_ptr(), wp.data_ptr(), code, cout, cin, taps, Cout, Cin, 0, st)
+        sd, hd, rd = scale.to(DEV), shift.to(DEV), res.to(DEV, dtype)
+        conv = torch.zeros(B, H, W, Cout, dtype=torch.float64)
+        conv[..., :cout] = F.conv2d(x.double(), (w.to(dtype).double() if dtype == torch.float16 else w.double()), None, padding=k // 2).permute(0, 2, 3, 1)
+        for act in (_lib.ACT_NONE, _lib.ACT_GELU, _lib.ACT_RELU):
+            for use_res in (False, True):
+                y = torch.full((B, H, W, Cout), float("nan"), dtype=dtype, device=DEV)
+                _lib.call("mu_conv_fwd_fused", xd.data_ptr(), wp.data_ptr(), sd.data_ptr(), hd.data_ptr(), rd.data_ptr() if use_res else None, act,
+                          y.data_ptr(), B, H, W, Cin, Cout, taps, Cin, Cout, code, st)
+                pre = conv * scale.double() + shift.double() + (res.double() if use_res else 0)
+                ref = F.gelu(pre) if act == _lib.ACT_GELU else (pre.clamp(min=0) if act == _lib.ACT_RELU else pre)
+                out.append((f"conv_fused[{kern}]{(B, H, W, cin, cout, k)} act{act} res{int(use_res)}", _err(y, ref), TOL[dtype]))
     return out
 
 

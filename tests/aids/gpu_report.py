@@ -35,6 +35,7 @@ if __name__ == "__main__":
             run(f"prep_weight {tag}", G.check_prep_weight, dt)
             run(f"conv_stats {tag}", G.check_conv_stats, dt)
             run(f"conv {tag}", G.check_conv, dt)
+            run(f"conv_fused {tag}", G.check_conv_fused, dt)
             run(f"bn_act {tag}", G.check_bn_act, dt)
             run(f"pool/up {tag}", G.check_pool_up, dt)
             run(f"ln_sample {tag}", G.check_ln_sample, dt)
