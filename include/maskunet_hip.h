@@ -411,6 +411,27 @@ int mu_inst_triplet_fwd(const float* feat, const long* mask, int B, int C, int H
                         const float* u, int id_cap, int max_inst, void* workspace, long ws_bytes, float* loss, void* stream);
 int mu_inst_triplet_bwd(const float* feat, int B, int C, int H, int W, const void* workspace, int id_cap, int max_inst,
                         const float* grad_out, float* dfeat, void* stream);
+/* f5: instance post-processing of the instance / panoptic scripts on the device (no host round trip of the [B,c,H,W] output).
+ * mu_argmax_prob: probs = softmax(outputs / 0.5, dim=1); preds = argmax(probs, 1) (ade_instance.py:408-411, ade_panoptic.py:529-532)
+ * in one read of the logits, addressed as in mu_mean_iou.  cls[r] = first arg-max over the C channels (taken on the logits: softmax is
+ * monotone), prob[r] = 1 / sum_c exp((x_c - x_max) * inv_temperature) = the soft-max probability of that class; prob may be null.
+ * The logits must be finite. */
+int mu_argmax_prob(const void* logits, long M, int C, long inner, long outer_stride, long c_stride, long p_stride,
+                   float inv_temperature, int* cls, float* prob_or_null, int dtype, void* stream);
+/* get_instances_from_mask (ade_instance.py:367-397: per class cv2.connectedComponents, 8-connected; per component bbox and mean
+ * probability), its sorted(..., key=score, reverse=True) (ade_instance.py:417-419) and generate_instance_mask (ade_panoptic.py:36-47).
+ * cls: int32 [B,H,W], values <= 0 are background; prob: fp32 [B,H,W] or null (score 1.0, the ground-truth case).
+ * ids [B,H,W]: 0 = background, else 1..count[b] in raster order of each instance's first pixel (always complete, also past max_inst);
+ * count [B]: the true number of instances; rows k < min(count, max_inst) of
+ *   table [B,max_inst,8] = class, area, x_min, y_min, x_max, y_max, first_pixel (y*W+x), class_rank (1-based among the instances of
+ *                          the same class in id order: the value generate_instance_mask writes),
+ *   score [B,max_inst]   = mean of prob over the instance (fixed-point sums: bit-identical from run to run),
+ *   order [B,max_inst]   = ids by descending score, ties by ascending id;
+ * the remaining rows are zero.  H*W <= 65536 and 1 <= max_inst <= 4096, else MU_ERR_SHAPE (mu_instances_supported: host only). */
+long mu_instances_workspace_bytes(int B, int H, int W, int max_inst);
+int mu_instances_supported(int H, int W, int max_inst);
+int mu_instances(const int* cls, const float* prob_or_null, int B, int H, int W, int max_inst, int* ids, int* table, float* score,
+                 int* count, int* order, void* workspace, long ws_bytes, void* stream);
 /* f4: uint8 HWC image bytes [npix, C] -> [0,1] floats in the NHWC compute layout [npix, Cp] (ToTensor, ade_semantic.py:85) */
 int mu_u8_to_nhwc(const unsigned char* src, void* dst, long npix, int C, int Cp, int dtype, void* stream);
 /* f4, resize half: the sample preparation of the reference datasets on the device.  src: decoded image bytes [B][Hs][Ws][C] (C <= 4, as

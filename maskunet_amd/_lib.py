@@ -96,6 +96,10 @@ SIGNATURES = {
     "mu_inst_triplet_workspace_bytes": (L, [I, I]),
     "mu_inst_triplet_fwd": (I, [P, P, I, I, I, I, I, F, P, I, I, P, L, P, P]),
     "mu_inst_triplet_bwd": (I, [P, I, I, I, I, P, I, I, P, P, P]),
+    "mu_argmax_prob": (I, [P, L, I, L, L, L, L, F, P, P, I, P]),
+    "mu_instances_workspace_bytes": (L, [I, I, I, I]),
+    "mu_instances_supported": (I, [I, I, I]),
+    "mu_instances": (I, [P, P, I, I, I, I, P, P, P, P, P, P, L, P]),
     "mu_u8_to_nhwc": (I, [P, P, L, I, I, I, P]),
     "mu_adamw_chunk": (I, []),
     "mu_adamw_multi": (I, [P, P, P, I, I, F, F, F, F, F, F, P, P, I, P, P]),

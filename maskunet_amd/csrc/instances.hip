@@ -1,0 +1,444 @@
+// On-device instance extraction for the instance / panoptic evaluation scripts (gfx950):
+//   mu_argmax_prob  softmax(outputs / T) + argmax of evaluate_instances (ade_instance.py:407-411) in ONE read of the logits;
+//   mu_instances    get_instances_from_mask (ade_instance.py:367-397) and generate_instance_mask (ade_panoptic.py:36-47):
+//                   8-connected components per class, per-instance bbox / area / mean probability, and the score order of
+//                   sorted(..., key=score, reverse=True) (ade_instance.py:417-419).
+// Scheme (DESIGN.md "Instance extraction"): one workgroup per image.
+//   label kernel  union-find over 16-bit links held in LDS (2 bytes per pixel: 128 KiB at the 65536-pixel limit).  Links always
+//                 point to a smaller raster index, so a component's root is its first pixel in raster order and the instance ids are
+//                 an exclusive scan over root flags.
+//   stats kernel  integer LDS atomics per instance (area, bbox, 2^-24 fixed-point probability sum: order-independent, so scores
+//                 are bit-identical from run to run), class_rank, and a bitonic sort of (score desc, id asc) keys in LDS.
+#include "common.h"
+
+#define INST_THREADS 1024
+#define INST_WAVES (INST_THREADS / 64)
+#define INST_MAX_PIXELS 65536
+#define INST_MAX_INSTANCES 4096
+
+// ------------------------------------------------------------------------------------------
+// arg-max + probability of the arg-max class.  Element (pixel r, class c) at
+//   logits[(r / inner) * outer_stride + c * c_stride + (r % inner) * p_stride]            (the convention of mu_mean_iou, loss.hip)
+// One thread per pixel walks the channels in ascending order with an online maximum and sum, so NCHW (lanes along pixels:
+// coalesced) and NHWC (16-byte loads along channels) do the SAME arithmetic per pixel and agree bit for bit.
+//   first maximum wins (strict >, as torch.argmax / mu_mean_iou);  prob = 1 / sum_c exp((x_c - x_max) / T)
+// Logits are assumed finite (inf - inf in the running update would give NaN).
+// ------------------------------------------------------------------------------------------
+struct ArgmaxState {
+    float m, k;             // running maximum; k = log2(e) / T
+    double s;               // sum of exp2((x - m) * k).  fp64: an fp32 running sum near 1 drops every term below 2^-25, and with 150
+                            // classes the dropped tail reaches several 1e-6 of the probability.  Costs a convert and an fp64 add
+                            // per channel and one fp64 divide per pixel (not timed apart from the pass)
+    int arg;
+    __device__ __forceinline__ void first(float v) { m = v; s = 1.0; arg = 0; }
+    __device__ __forceinline__ void next(float v, int c) {
+        if (v > m) {
+            s = s * (double)__builtin_amdgcn_exp2f((m - v) * k) + 1.0;
+            m = v;
+            arg = c;
+        } else {
+            s += (double)__builtin_amdgcn_exp2f((v - m) * k);
+        }
+    }
+};
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void argmax_prob_kernel(const T* __restrict__ logits, long M, int C, long inner, long outer_stride,
+                                                          long c_stride, long p_stride, float k, int* __restrict__ cls,
+                                                          float* __restrict__ prob) {
+    constexpr int V = 16 / sizeof(T);              // elements per 16-byte load
+    for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < M; r += (long)gridDim.x * 256) {
+        const T* base = logits + (r / inner) * outer_stride + (r % inner) * p_stride;
+        ArgmaxState st;
+        st.k = k;
+        if (VEC) {                                  // c_stride == 1, rows 16-byte aligned: vector loads along the channels
+            typedef T TV __attribute__((ext_vector_type(V)));
+            const int Cv = C / V * V;
+            for (int c0 = 0; c0 < Cv; c0 += V) {
+                const TV v = *(const TV*)(base + c0);
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    if (c0 + j == 0) st.first((float)v[j]);
+                    else st.next((float)v[j], c0 + j);
+                }
+            }
+            for (int c = Cv; c < C; ++c) {
+                if (c == 0) st.first((float)base[c]);
+                else st.next((float)base[c], c);
+            }
+        } else {                                    // strided channels: four independent loads in flight, then the ordered update
+            st.first((float)base[0]);
+            int c = 1;
+            for (; c + 4 <= C; c += 4) {
+                const float v0 = (float)base[(long)c * c_stride], v1 = (float)base[(long)(c + 1) * c_stride];
+                const float v2 = (float)base[(long)(c + 2) * c_stride], v3 = (float)base[(long)(c + 3) * c_stride];
+                st.next(v0, c);
+                st.next(v1, c + 1);
+                st.next(v2, c + 2);
+                st.next(v3, c + 3);
+            }
+            for (; c < C; ++c) st.next((float)base[(long)c * c_stride], c);
+        }
+        cls[r] = st.arg;
+        if (prob) prob[r] = (float)(1.0 / st.s);
+    }
+}
+
+template <typename T>
+static int argmax_prob_launch(const void* logits, long M, int C, long inner, long outer_stride, long c_stride, long p_stride, float k,
+                              int* cls, float* prob, hipStream_t st) {
+    constexpr long V = 16 / sizeof(T);
+    const bool vec = c_stride == 1 && p_stride % V == 0 && outer_stride % V == 0 && ((uintptr_t)logits & 15) == 0;
+    const long blocks = (M + 255) / 256;
+    const int g = (int)(blocks > 65536 ? 65536 : blocks);
+    if (vec) argmax_prob_kernel<T, true><<<g, 256, 0, st>>>((const T*)logits, M, C, inner, outer_stride, c_stride, p_stride, k, cls, prob);
+    else argmax_prob_kernel<T, false><<<g, 256, 0, st>>>((const T*)logits, M, C, inner, outer_stride, c_stride, p_stride, k, cls, prob);
+    MU_CHECK_LAUNCH();
+    return MU_OK;
+}
+
+extern "C" int mu_argmax_prob(const void* logits, long M, int C, long inner, long outer_stride, long c_stride, long p_stride,
+                              float inv_temperature, int* cls, float* prob_or_null, int dtype, void* stream) {
+    if (!logits || !cls || M <= 0 || C <= 0 || inner <= 0 || !(inv_temperature > 0.f)) return MU_ERR_ARG;
+    if (dtype != MU_F32 && dtype != MU_F16) return MU_ERR_ARG;
+    const float k = inv_temperature * 1.44269504088896340736f;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MU_F16) return argmax_prob_launch<h16>(logits, M, C, inner, outer_stride, c_stride, p_stride, k, cls, prob_or_null, st);
+    return argmax_prob_launch<float>(logits, M, C, inner, outer_stride, c_stride, p_stride, k, cls, prob_or_null, st);
+}
+
+// ------------------------------------------------------------------------------------------
+// Labelling: union-find with 16-bit links in LDS.
+// ------------------------------------------------------------------------------------------
+typedef unsigned short u16;
+
+__device__ __forceinline__ unsigned uf_find(const volatile u16* p, unsigned x) {
+    for (;;) {
+        const unsigned q = p[x];
+        if (q == x) return x;
+        x = q;
+    }
+}
+
+// compare-and-swap on one 16-bit link through the 32-bit word that holds it (LDS has no 16-bit atomics); returns the link's
+// previous value.  A neighbour changing the other half of the word only costs a retry.
+__device__ __forceinline__ unsigned uf_cas16(u16* p, unsigned idx, unsigned expect, unsigned val) {
+    unsigned* w = (unsigned*)p + (idx >> 1);
+    const unsigned sh = (idx & 1u) * 16u;
+    unsigned old = *(volatile unsigned*)w;
+    for (;;) {
+        const unsigned cur = (old >> sh) & 0xffffu;
+        if (cur != expect) return cur;
+        const unsigned nw = (old & ~(0xffffu << sh)) | (val << sh);
+        const unsigned prev = atomicCAS(w, old, nw);
+        if (prev == old) return cur;
+        old = prev;
+    }
+}
+
+// hook the larger root under the smaller one; only roots are ever re-linked, so every link points to a smaller index of the
+// same component at all times.  No thread waits for another: a failed CAS means someone else made progress.
+__device__ __forceinline__ void uf_unite(u16* p, unsigned a, unsigned b) {
+    for (;;) {
+        a = uf_find(p, a);
+        b = uf_find(p, b);
+        if (a == b) return;
+        if (a < b) { const unsigned t = a; a = b; b = t; }
+        const unsigned old = uf_cas16(p, a, a, b);
+        if (old == a) return;
+        a = old;
+    }
+}
+
+// cls[B][N] -> ids[B][N] (1..count in raster order of the first pixel, 0 = background), count[B], first[B][max_inst] (first pixel
+// of ids 1..max_inst).  Dynamic LDS: u16 parent[N rounded up to 2] then unsigned wave_total[INST_WAVES].
+__global__ __launch_bounds__(INST_THREADS) void inst_label_kernel(const int* __restrict__ cls_all, int N, int W, int max_inst,
+                                                                   int* __restrict__ ids_all, int* __restrict__ count,
+                                                                   int* __restrict__ first_all) {
+    extern __shared__ unsigned inst_lds[];
+    u16* parent = (u16*)inst_lds;
+    unsigned* wave_total = inst_lds + ((N + 1) >> 1);
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int* cls = cls_all + (long)b * N;
+    int* ids = ids_all + (long)b * N;
+    int* first = first_all + (long)b * max_inst;
+
+    // 1. horizontal runs inside each 64-pixel chunk: every pixel links to the start of its run (no chains along rows)
+    for (int base = wave * 64; base < N; base += INST_THREADS) {
+        const int i = base + lane;
+        const bool valid = i < N;
+        const int c = valid ? cls[i] : 0;
+        const bool link = valid && c > 0 && (i % W) > 0 && cls[i - 1] == c;
+        const unsigned long long mask = __ballot(link);
+        const unsigned long long upto = (lane == 63) ? ~0ull : ((2ull << lane) - 1ull);
+        const unsigned long long zeros = ~mask & upto;                 // pixels at or before this lane that start a run
+        const int start = zeros ? 63 - __builtin_clzll(zeros) : 0;     // none: the run comes in from the previous chunk
+        if (valid) parent[i] = (u16)(base + start);
+    }
+    __syncthreads();
+
+    // 2. unions across chunk borders and with the row above.  A union is skipped where the pixel to the left (or right) makes the
+    //    same connection: with W and NW of the class, i-1 ~ NW and NW ~ N already; with E of the class, E unites with NE itself.
+    for (int base = wave * 64; base < N; base += INST_THREADS) {
+        const int i = base + lane;
+        if (i >= N) continue;
+        const int c = cls[i];
+        if (c <= 0) continue;
+        const int x = i % W;
+        const bool w = x > 0 && cls[i - 1] == c;
+        if (lane == 0 && w) uf_unite(parent, i, i - 1);
+        if (i < W) continue;
+        if (cls[i - W] == c) {
+            const bool nw = x > 0 && cls[i - W - 1] == c;
+            if (!(w && nw)) uf_unite(parent, i, i - W);
+        } else {
+            if (x > 0 && !w && cls[i - W - 1] == c) uf_unite(parent, i, i - W - 1);
+            if (x < W - 1 && cls[i - W + 1] == c && cls[i + 1] != c) uf_unite(parent, i, i - W + 1);
+        }
+    }
+    __syncthreads();
+
+    // 3. flatten, in raster order: ancestors have smaller indices, so most chains are already short when a pixel is reached
+    for (int i = tid; i < N; i += INST_THREADS) {
+        const unsigned r = uf_find(parent, i);
+        parent[i] = (u16)r;          // a concurrent reader sees the old link or the root: both are ancestors
+    }
+    __syncthreads();
+
+    // 4. ids = exclusive scan of the root flags in raster order: wave v owns pixels [v * seg, (v + 1) * seg)
+    const int seg = ((N + INST_WAVES * 64 - 1) / (INST_WAVES * 64)) * 64;
+    const int lo = wave * seg, hi = min(N, lo + seg);
+    unsigned mine = 0;
+    for (int base = lo; base < hi; base += 64) {
+        const int i = base + lane;
+        const bool root = i < hi && parent[i] == i && cls[i] > 0;
+        mine += __popcll(__ballot(root));
+    }
+    if (lane == 0) wave_total[wave] = mine;
+    __syncthreads();
+    unsigned running = 0, total = 0;
+    for (int v = 0; v < INST_WAVES; ++v) {
+        const unsigned t = wave_total[v];
+        if (v < wave) running += t;
+        total += t;
+    }
+    if (tid == 0) count[b] = (int)total;
+    for (int base = lo; base < hi; base += 64) {
+        const int i = base + lane;
+        const bool valid = i < hi;
+        const bool fg = valid && cls[i] > 0;
+        const bool root = fg && parent[i] == i;
+        const unsigned long long mask = __ballot(root);
+        if (root) {
+            const unsigned id = running + __popcll(mask & ((1ull << lane) - 1ull)) + 1u;
+            ids[i] = (int)id;
+            if (id <= (unsigned)max_inst) first[id - 1] = i;
+        } else if (valid && !fg) {
+            ids[i] = 0;
+        }
+        running += __popcll(mask);
+    }
+    __syncthreads();                 // the roots' ids (global memory, same workgroup) are visible past this barrier
+    for (int i = tid; i < N; i += INST_THREADS) {
+        const unsigned r = parent[i];
+        if (r != (unsigned)i) ids[i] = ids[r];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Per-instance statistics, table, score order.  Dynamic LDS, P = max_inst rounded up to a power of two:
+//   unsigned long long acc[P] (fixed-point sums, then the sort keys);  unsigned area[P], xmin[P], ymin[P], xmax[P], ymax[P]
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned wave_min_u(unsigned v) {
+    for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, o));
+    return v;
+}
+__device__ __forceinline__ unsigned wave_max_u(unsigned v) {
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o));
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum_ull(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+
+__device__ __forceinline__ unsigned long long prob_fixed(float p) {      // round(p * 2^24), two's complement
+    return (unsigned long long)(long long)__float2ll_rn(p * 16777216.f);
+}
+
+__global__ __launch_bounds__(INST_THREADS) void inst_stats_kernel(const int* __restrict__ cls_all, const float* __restrict__ prob_all,
+                                                                   const int* __restrict__ ids_all, const int* __restrict__ count,
+                                                                   const int* __restrict__ first_all, int N, int W, int max_inst, int P,
+                                                                   int* __restrict__ table_all, float* __restrict__ score_all,
+                                                                   int* __restrict__ order_all) {
+    extern __shared__ unsigned inst_lds[];
+    unsigned long long* acc = (unsigned long long*)inst_lds;      // first: 8-byte aligned for every P (P = 1 included)
+    unsigned* area = inst_lds + 2 * P;
+    unsigned* xmin = area + P;
+    unsigned* ymin = xmin + P;
+    unsigned* xmax = ymin + P;
+    unsigned* ymax = xmax + P;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int* cls = cls_all + (long)b * N;
+    const int* ids = ids_all + (long)b * N;
+    const float* prob = prob_all ? prob_all + (long)b * N : nullptr;
+    const int* first = first_all + (long)b * max_inst;
+    int* table = table_all + (long)b * max_inst * 8;
+    float* score = score_all + (long)b * max_inst;
+    int* order = order_all + (long)b * max_inst;
+    const int K = min(count[b], max_inst);
+
+    for (int k = tid; k < P; k += INST_THREADS) {
+        area[k] = 0;
+        xmin[k] = 0x7fffffffu;
+        ymin[k] = 0x7fffffffu;
+        xmax[k] = 0;
+        ymax[k] = 0;
+        acc[k] = 0;
+    }
+    __syncthreads();
+
+    for (int base = wave * 64; base < N; base += INST_THREADS) {
+        const int i = base + lane;
+        const bool valid = i < N;
+        const int id = valid ? ids[i] : 0;
+        const bool active = id > 0 && id <= K;
+        const unsigned x = (unsigned)(i % W), y = (unsigned)(i / W);
+        const unsigned long long q = (active && prob) ? prob_fixed(prob[i]) : 0ull;
+        const int id0 = __shfl(id, 0);
+        if (__ballot(valid && id == id0) == ~0ull) {          // the whole wave inside one instance: one set of atomics per wave
+            if (id0 > 0 && id0 <= K) {
+                const unsigned x0 = wave_min_u(x), x1 = wave_max_u(x), y0 = wave_min_u(y), y1 = wave_max_u(y);
+                const unsigned long long qs = wave_sum_ull(q);
+                if (lane == 0) {
+                    const int k = id0 - 1;
+                    atomicAdd(&area[k], 64u);
+                    atomicMin(&xmin[k], x0);
+                    atomicMax(&xmax[k], x1);
+                    atomicMin(&ymin[k], y0);
+                    atomicMax(&ymax[k], y1);
+                    if (prob) atomicAdd(&acc[k], qs);
+                }
+            }
+        } else if (active) {
+            const int k = id - 1;
+            atomicAdd(&area[k], 1u);
+            atomicMin(&xmin[k], x);
+            atomicMax(&xmax[k], x);
+            atomicMin(&ymin[k], y);
+            atomicMax(&ymax[k], y);
+            if (prob) atomicAdd(&acc[k], q);
+        }
+    }
+    __syncthreads();
+
+    // table columns 0..6, scores, sort keys; xmin[] is re-used for the class of the instance (class_rank below)
+    for (int k = tid; k < P; k += INST_THREADS) {
+        unsigned long long key = ~0ull;                        // padding sorts last
+        int c = 0;
+        if (k < K) {
+            const int f = first[k];
+            c = cls[f];
+            const float s = prob ? (float)((double)(long long)acc[k] / ((double)area[k] * 16777216.0)) : 1.f;
+            int* row = table + (long)k * 8;
+            row[0] = c;
+            row[1] = (int)area[k];
+            row[2] = (int)xmin[k];
+            row[3] = (int)ymin[k];
+            row[4] = (int)xmax[k];
+            row[5] = (int)ymax[k];
+            row[6] = f;
+            score[k] = s;
+            unsigned u = __float_as_uint(s);
+            u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // ascending-sortable float bits
+            key = ((unsigned long long)(~u) << 32) | (unsigned)(k + 1);   // descending score, then ascending id
+        } else if (k < max_inst) {
+            int* row = table + (long)k * 8;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) row[j] = 0;
+            score[k] = 0.f;
+        }
+        acc[k] = key;
+        xmin[k] = (unsigned)c;
+    }
+    __syncthreads();
+
+    // class_rank: 1-based rank among the instances of the same class, in id order (what generate_instance_mask writes)
+    for (int k = tid; k < K; k += INST_THREADS) {
+        const unsigned c = xmin[k];
+        int rank = 1;
+        for (int j = 0; j < k; ++j) rank += (xmin[j] == c);
+        table[(long)k * 8 + 7] = rank;
+    }
+
+    // bitonic sort of the keys, ascending, over the power of two that holds K
+    int S = 1;
+    while (S < K) S <<= 1;
+    for (int size = 2; size <= S; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            __syncthreads();
+            for (int t = tid; t < (S >> 1); t += INST_THREADS) {
+                const int lo = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), hi = lo + stride;
+                const bool up = (lo & size) == 0;
+                const unsigned long long a = acc[lo], c = acc[hi];
+                if ((a > c) == up) {
+                    acc[lo] = c;
+                    acc[hi] = a;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int k = tid; k < max_inst; k += INST_THREADS) order[k] = k < K ? (int)(unsigned)(acc[k] & 0xffffffffull) : 0;
+}
+
+static int inst_pow2(int v) {
+    int p = 1;
+    while (p < v) p <<= 1;
+    return p;
+}
+
+// More than 64 KiB of dynamic LDS has to be granted per kernel (a CU has 160 KiB; one workgroup may take all of it).  The grant is
+// a property of the kernel, not of a call: it is set ONCE per process, to the most either kernel can ever ask for, so concurrent
+// callers with different shapes cannot undercut each other and no runtime call sits on the per-call path.
+#define INST_LDS_LABEL_MAX (INST_MAX_PIXELS * 2 + INST_WAVES * 4)
+#define INST_LDS_STATS_MAX (INST_MAX_INSTANCES * 28)
+static bool inst_lds_granted() {
+    static const bool ok =
+        hipFuncSetAttribute((const void*)inst_label_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, INST_LDS_LABEL_MAX) == hipSuccess &&
+        hipFuncSetAttribute((const void*)inst_stats_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, INST_LDS_STATS_MAX) == hipSuccess;
+    return ok;
+}
+
+extern "C" int mu_instances_supported(int H, int W, int max_inst) {
+    if (H <= 0 || W <= 0 || (long)H * W > INST_MAX_PIXELS) return MU_ERR_SHAPE;
+    if (max_inst < 1 || max_inst > INST_MAX_INSTANCES) return MU_ERR_SHAPE;
+    return MU_OK;
+}
+
+// int first_pixel[B][max_inst]: the label kernel's hand-over to the statistics kernel
+extern "C" long mu_instances_workspace_bytes(int B, int H, int W, int max_inst) {
+    if (B <= 0 || mu_instances_supported(H, W, max_inst) != MU_OK) return 0;
+    return (long)B * max_inst * (long)sizeof(int);
+}
+
+extern "C" int mu_instances(const int* cls, const float* prob_or_null, int B, int H, int W, int max_inst, int* ids, int* table,
+                            float* score, int* count, int* order, void* workspace, long ws_bytes, void* stream) {
+    if (!cls || !ids || !table || !score || !count || !order || !workspace || B <= 0 || H <= 0 || W <= 0) return MU_ERR_ARG;
+    if (mu_instances_supported(H, W, max_inst) != MU_OK) return MU_ERR_SHAPE;
+    if (ws_bytes < mu_instances_workspace_bytes(B, H, W, max_inst)) return MU_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int N = H * W, P = inst_pow2(max_inst);
+    int* first = (int*)workspace;
+    const size_t lds_label = (size_t)((N + 1) >> 1) * 4 + INST_WAVES * sizeof(unsigned);
+    const size_t lds_stats = (size_t)P * (5 * sizeof(unsigned) + sizeof(unsigned long long));
+    if (!inst_lds_granted()) return MU_ERR_LAUNCH;
+    inst_label_kernel<<<B, INST_THREADS, lds_label, st>>>(cls, N, W, max_inst, ids, count, first);
+    MU_CHECK_LAUNCH();
+    inst_stats_kernel<<<B, INST_THREADS, lds_stats, st>>>(cls, prob_or_null, ids, count, first, N, W, max_inst, P, table, score, order);
+    MU_CHECK_LAUNCH();
+    return MU_OK;
+}

@@ -1,0 +1,124 @@
+"""Instance post-processing of the `*_instance.py` / `*_panoptic.py` scripts on the device.
+
+The reference pulls softmax(outputs / 0.5) to the host and labels it there per class with cv2.connectedComponents
+(get_instances_from_mask, ade_instance.py:367-397; evaluate_instances, ade_instance.py:399-425; generate_instance_mask,
+ade_panoptic.py:36-47).  Here the logits are read once on the device (mu_argmax_prob) and one workgroup per image labels the class
+map, gathers the per-instance statistics and sorts the scores (mu_instances); nothing crosses to the host until the caller asks.
+
+Class 0 is background, and so is every negative value.  An instance is a maximal 8-connected set of pixels of one non-zero class;
+ids run 1..count within an image, ordered by each instance's first pixel in raster order.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import torch
+
+from . import _lib
+from ._lib import call, dt, ptr, stream
+from .losses import _nhwc_source
+
+TABLE_COLUMNS = ("class", "area", "x_min", "y_min", "x_max", "y_max", "first_pixel", "class_rank")
+
+
+@dataclass
+class Instances:
+    """Device tensors of one call.  `table` rows / `scores` / `order` hold ids 1..min(count, max_instances); the rest is zero.
+    `count` is the true number of instances per image and `ids` is always complete, also past max_instances."""
+    classes: torch.Tensor        # int32 [B,H,W]   class map (arg-max of the logits, or the labels)
+    ids: torch.Tensor            # int32 [B,H,W]   0 = background, else the instance id
+    table: torch.Tensor          # int32 [B,max_instances,8]   TABLE_COLUMNS; row k-1 describes id k
+    scores: torch.Tensor         # fp32  [B,max_instances]     mean probability of the instance's class over its pixels
+    count: torch.Tensor          # int32 [B]
+    order: torch.Tensor          # int32 [B,max_instances]     ids by descending score (ties: ascending id), padded with 0
+    prob: torch.Tensor | None = None     # fp32 [B,H,W] probability of the arg-max class (None for label input)
+
+    def top(self, max_queries):
+        """(ids, scores) [B, max_queries] of the reference's sorted(instances, key=score, reverse=True)[:max_queries]; id 0 (score 0)
+        pads images with fewer instances.  No host synchronisation."""
+        ids = self.order[:, :max_queries]
+        sc = torch.gather(self.scores, 1, (ids - 1).clamp_(min=0).long())
+        return ids, torch.where(ids > 0, sc, torch.zeros_like(sc))
+
+    def to_reference(self, image, max_queries=None):
+        """The reference's list of dicts for one image, on the host, best score first: `bbox` = [x_min, y_min, x_max - x_min,
+        y_max - y_min] (no +1, as the reference), `category_id`, `score`, and a boolean `mask` where the reference has the
+        pycocotools RLE."""
+        order = self.order[image].cpu().tolist()
+        table = self.table[image].cpu().tolist()
+        scores = self.scores[image].cpu().tolist()
+        ids = self.ids[image].cpu()
+        if max_queries is not None:
+            order = order[:max_queries]
+        out = []
+        for k in order:
+            if k == 0:
+                break
+            c, _, x0, y0, x1, y1, _, _ = table[k - 1]
+            out.append({"bbox": [float(x0), float(y0), float(x1 - x0), float(y1 - y0)], "category_id": int(c),
+                        "score": float(scores[k - 1]), "mask": (ids == k).numpy()})
+        return out
+
+
+def _label(classes, prob, max_instances):
+    B, H, W = classes.shape
+    lib = _lib.load()
+    max_instances = int(max_instances)
+    if lib.mu_instances_supported(H, W, max_instances) != 0:
+        raise RuntimeError(f"maskunet_amd: instances need H*W <= 65536 and 1 <= max_instances <= 4096, got {H}x{W}, {max_instances}")
+    dev = classes.device
+    ids = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    table = torch.empty((B, max_instances, 8), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, max_instances), dtype=torch.float32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    order = torch.empty((B, max_instances), dtype=torch.int32, device=dev)
+    ws = torch.empty(lib.mu_instances_workspace_bytes(B, H, W, max_instances), dtype=torch.uint8, device=dev)
+    call("mu_instances", ptr(classes), ptr(prob), B, H, W, max_instances, ptr(ids), ptr(table), ptr(scores), ptr(count), ptr(order),
+         ptr(ws), ws.numel(), stream())
+    return Instances(classes, ids, table, scores, count, order, prob)
+
+
+def predict_instances(outputs, temperature=0.5, max_instances=1024):
+    """evaluate_instances' post-processing (ade_instance.py:408-419) of the module output `outputs` [B,C,H,W] (fp32 or fp16): class =
+    first arg-max of the logits, probability = softmax(outputs / temperature) of that class, instances and their mean-probability
+    scores.  An untouched output of a maskunet_amd module is read through the NHWC tensor it was converted from.  Never synchronises."""
+    if outputs.dim() != 4 or not outputs.is_cuda:
+        raise RuntimeError("predict_instances expects the module output [B,C,H,W] on the GPU")
+    if not temperature > 0:
+        raise ValueError("temperature must be positive")
+    B, C, H, W = outputs.shape
+    M = B * H * W
+    src = _nhwc_source(outputs)
+    if src is not None and src[0].is_contiguous():
+        x = src[0].detach()
+        inner, outer, cs, ps = M, 0, 1, x.shape[-1]
+    else:
+        x = outputs.detach().contiguous()
+        inner, outer, cs, ps = H * W, C * H * W, H * W, 1
+    classes = torch.empty((B, H, W), dtype=torch.int32, device=x.device)
+    prob = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
+    call("mu_argmax_prob", ptr(x), M, C, inner, outer, cs, ps, 1.0 / float(temperature), ptr(classes), ptr(prob), dt(x), stream())
+    return _label(classes, prob, max_instances)
+
+
+def instances_from_labels(labels, max_instances=1024):
+    """Instances of an int64 / int32 class map [B,H,W] (the ground-truth side: every score is 1.0)."""
+    if labels.dim() != 3 or labels.dtype not in (torch.int64, torch.int32) or not labels.is_cuda:
+        raise RuntimeError("instances_from_labels expects an int64 / int32 [B,H,W] class map on the GPU")
+    return _label(labels.to(torch.int32).contiguous(), None, max_instances)
+
+
+def generate_instance_mask(semantic_mask, max_instances=1024):
+    """generate_instance_mask of the panoptic datasets (ade_panoptic.py:36-47): an int32 map in which every pixel holds the 1-based
+    number of its connected component WITHIN ITS CLASS (numbers restart per class -- the reference's quirk, and what it feeds to
+    InstanceContrastiveLoss); 0 = background, -1 = instance past `max_instances`.  Components of a class are numbered by their first
+    pixel in raster order.  Accepts [H,W] or [B,H,W]."""
+    squeeze = semantic_mask.dim() == 2
+    r = instances_from_labels(semantic_mask[None] if squeeze else semantic_mask, max_instances)
+    B = r.ids.shape[0]
+    lut = torch.cat([torch.zeros((B, 1), dtype=torch.int32, device=r.ids.device), r.table[:, :, 7]], 1)      # id -> class_rank
+    ids = r.ids.view(B, -1).long()
+    over = ids > max_instances
+    out = torch.gather(lut, 1, ids.clamp(max=max_instances))
+    out = torch.where(over, torch.full_like(out, -1), out).view_as(r.ids)
+    return out[0] if squeeze else out
