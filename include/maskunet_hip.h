@@ -154,7 +154,7 @@ int mu_conv_fwd_stats(const void* x, const void* w, const float* bias, void* y, 
  *   mu_conv_wgrad_plan      mu_conv_wgrad (pair = 0), mu_conv_wgrad_h1 (dtype MU_F16, pair = 0), mu_conv_wgrad_h (dtype MU_F16, pair = 1);
  *   mu_conv_wgrad_bias_plan mu_conv_wgrad_bias.
  * mu_conv_plan_name(op, id): the kernel's name, op = 0 forward, 1 fused, 2 dgrad_h, 3 wgrad; ids run from 1 to mu_conv_plan_count(op) - 1;
- * NULL for an id outside that range or one this build cannot select. */
+ * NULL for an id outside that range. */
 int mu_conv_fwd_plan(int B, int H, int W, int Cin, int Cout, int taps, int dtype, int with_stats);
 int mu_conv_fwd_fused_plan(int B, int H, int W, int Cin, int Cout, int taps, int dtype);
 int mu_conv_dgrad_h_plan(int B, int H, int W, int Cin, int Cout);

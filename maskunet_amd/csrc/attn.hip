@@ -16,135 +16,9 @@
 #include "../../include/maskunet_hip.h"
 #include <stdlib.h>
 #include <type_traits>
-// Tuning knobs (overridable with -D for tools/ab_bench.py A/B runs).  Measured in-process, N=16384 C=64 B=64 fp16:
-//   dK/dV  : 3 waves/SIMD (168 VGPRs, 4 spilled) 4.70 ms vs 2 waves/SIMD 5.24 ms; 1 wave/SIMD with 64 keys/wave 9 ms
-//   dQ     : 32-key tiles (152 VGPRs, 3 waves/SIMD) 3.07 ms vs 64-key tiles (196 VGPRs) 3.22 ms; forcing 3 waves/SIMD on the
-//            64-key version spills into the loop: 10.97 ms
-//   forward: already 3 waves/SIMD at 158 VGPRs
-#ifndef MU_DKV_OCC
-#define MU_DKV_OCC 3
-#endif
-#ifndef MU_DQ_OCC
-#define MU_DQ_OCC 3
-#endif
-#ifndef MU_FWD_OCC
-#define MU_FWD_OCC 2
-#endif
-// C = 128 blocks (N = 4096): without a bound the compiler takes ~320 registers (VGPR + AGPR) and runs ONE wave per SIMD.
-// In-process A/B (B=64, N=4096, C=128): forward 0.624 -> 0.341 ms with a 2-waves/SIMD bound and 32-key tiles (168 VGPRs),
-// dQ 0.520 -> 0.374 ms with the bound alone (226 VGPRs, no spills), dK/dV 1.174 -> 0.959 ms with 16 keys per wave (NKT = 1,
-// 150 VGPRs; the 32-key version spills under the bound).  3 waves/SIMD: no further gain.
-#ifndef MU_FWD_OCC128
-#define MU_FWD_OCC128 3       // (round 2, with the conflict-free swizzle of the 256-byte rows: 0.346 -> 0.301 ms; dQ spills under the same bound)
-#endif
-#ifndef MU_DQ_OCC128
-#define MU_DQ_OCC128 2
-#endif
-#ifndef MU_DKV_OCC128
-#define MU_DKV_OCC128 2
-#endif
-// C = 256 (N = 1024): the forward gains from the 2-waves/SIMD bound even with 26 spilled registers (0.134 -> 0.102 ms), dQ loses
-// (115 spills: 0.092 -> 0.197 ms), dK/dV does not fit at all
-#ifndef MU_FWD_OCC256
-#define MU_FWD_OCC256 2
-#endif
-#ifndef MU_DQ_NQT128
-#define MU_DQ_NQT128 2          // 1 = one 16-query tile per wave in the C = 128 dQ sweep (A/B below)
-#endif
-#ifndef MU_DQ_OCC128_Q1
-#define MU_DQ_OCC128_Q1 3
-#endif
-#ifndef MU_DQ_OCC256
-#define MU_DQ_OCC256 1
-#endif
-#ifndef MU_DKV_OCC256
-#define MU_DKV_OCC256 1
-#endif
-#ifndef MU_FWD_KT128
-#define MU_FWD_KT128 32
-#endif
-#ifndef MU_FWD_NW128
-#define MU_FWD_NW128 4
-#endif
-#ifndef MU_DKV_NKT128
-#define MU_DKV_NKT128 1
-#endif
-#ifndef MU_DKV_NW128
-#define MU_DKV_NW128 12      // 12-wave blocks = 3 waves/SIMD at 168 VGPRs (in-process, N = 4096: 4 waves x 2 blocks 0.68, 8 waves 0.67, 12 waves 0.58 ms)
-#endif
-#ifndef MU_DKV_NW64
-#define MU_DKV_NW64 4
-#endif
-#ifndef MU_DKV_NW256
-#define MU_DKV_NW256 4
-#endif
-#ifndef MU_DQ_KT
-#define MU_DQ_KT 32
-#endif
-// forward: optimistic sweep without per-tile running-max tracking, verified afterwards (see attn_fwd2_kernel); 0 = always exact
-#ifndef MU_FWD_OPTIMISTIC
-#define MU_FWD_OPTIMISTIC 1
-#endif
-// s_setprio(1) around the MFMA clusters.  In-process A/B (B=64, N=16384, C=64, fp16): dQ 2.94 -> 2.87 ms, dK/dV 3.98 -> 3.90 ms,
-// forward 2.03 -> 2.02 ms (noise); at C=128 the dK/dV sweep LOSES 1.5 %.  1 = the C <= 64 backward sweeps only, 2 = everywhere, 0 = off
-#ifndef MU_ATTN_SETPRIO
-#define MU_ATTN_SETPRIO 1
-#endif
-// LDS operand prefetch ahead of the VALU phase (number of 16-column blocks; 0 = off)
-#ifndef MU_DKV_PREFETCH128
-#define MU_DKV_PREFETCH128 0   // (8 = all blocks prefetched: -5 % with 8-wave blocks, spills under the 3-waves/SIMD bound of the 12-wave blocks)
-#endif
-#ifndef MU_DKV_PREFETCH
-#define MU_DKV_PREFETCH 0
-#endif
-#ifndef MU_DQ_PREFETCH
-#define MU_DQ_PREFETCH 0
-#endif
-#ifndef MU_DKV_PKMUL
-#define MU_DKV_PKMUL 1
-#endif
-#ifndef MU_DKV_ROWC_ONE
-#define MU_DKV_ROWC_ONE 0
-#endif
-// fp32x (chunk-encoded fp32 tiles): the 256-/512-byte-row swizzle of the fp16 tiles for the row fragment + transposed reads, and
-// the occupancy bound of the C <= 64 sweeps (the fp32 instantiations run one wave per SIMD)
-#ifndef MU_XF_SWZ256
-#define MU_XF_SWZ256 1
-#endif
-// fp32x, C = 128 dK/dV: the 4-deep Q / dO ring takes 128 KB, so a 4-wave block is alone on its CU (one wave per SIMD: matrix pipe busy 25 %);
-// 8 waves share the ring (two per SIMD, 16 keys each)
-#ifndef MU_XF_DKV_NW128
-#define MU_XF_DKV_NW128 8
-#endif
-#ifndef MU_XF_FWD_KT32
-#define MU_XF_FWD_KT32 1
-#endif
-#ifndef MU_XF_OCC
-#define MU_XF_OCC 2
-#endif
-#ifndef MU_XF_DQ_OCC
-#define MU_XF_DQ_OCC 2
-#endif
-#ifndef MU_XF_DKV_SCHED
-#define MU_XF_DKV_SCHED 0
-#endif
-#ifndef MU_XF_DKV_SCHED2
-#define MU_XF_DKV_SCHED2 0
-#endif
-#ifndef MU_XF_OPAQUE
-#define MU_XF_OPAQUE 1
-#endif
-#ifndef MU_H16_OPAQUE
-#define MU_H16_OPAQUE 0
-#endif
-#ifndef MU_XF_PK_MAXD
-#define MU_XF_PK_MAXD 512
-#endif
-#ifndef MU_FWD_PREFETCH
-#define MU_FWD_PREFETCH 0
-#endif
-#define MU_PRIO_ON(bwd) (MU_ATTN_SETPRIO == 2 || (MU_ATTN_SETPRIO == 1 && (bwd) && D <= 64 && sizeof(T) == 2))
-#define MU_PRIO(x) do { if (MU_PRIO_ON(MU_PRIO_BWD)) __builtin_amdgcn_s_setprio(x); } while (0)
+// s_setprio(1) around the MFMA clusters of the C <= 64 fp16 backward sweeps.  In-process A/B (B=64, N=16384, C=64, fp16): dQ 2.94 -> 2.87 ms,
+// dK/dV 3.98 -> 3.90 ms, forward 2.03 -> 2.02 ms (noise: the forward does not raise its priority); at C=128 the dK/dV sweep LOSES 1.5 %.
+#define MU_PRIO(x) do { if (D <= 64 && sizeof(T) == 2) __builtin_amdgcn_s_setprio(x); } while (0)
 
 typedef __fp16 fp16x4v __attribute__((__vector_size__(4 * sizeof(__fp16))));
 // LDS-DMA through inline asm (see conv.hip glds16a): hipcc's waitcnt pass puts s_waitcnt vmcnt(0) in front of every
@@ -186,18 +60,10 @@ template <typename T> __device__ __forceinline__ const T* lds_opaque(const T* p)
 
 // Block -> (image, tile) through the XCD-aware remap: the tiles of one image run on ONE XCD, so the K/V (forward, dQ) or Q/dO (dK/dV)
 // rows that every block of the image streams are fetched into that XCD's L2 once instead of once per XCD.
-#ifndef MU_ATTN_XCD
-#define MU_ATTN_XCD 1
-#endif
 __device__ __forceinline__ void attn_block(int& bx, int& b) {
-    if (MU_ATTN_XCD) {
-        const int L = xcd_remap(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
-        b = L / gridDim.x;
-        bx = L - b * gridDim.x;
-    } else {
-        b = blockIdx.y;
-        bx = blockIdx.x;
-    }
+    const int L = xcd_remap(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
+    b = L / gridDim.x;
+    bx = L - b * gridDim.x;
 }
 
 template <typename T> struct AT;
@@ -254,7 +120,7 @@ template <> struct AT<h16> {
     }
     // the row-sum product (A = the constant-ones operand)
     static __device__ __forceinline__ void mma_ones(const AccA& a, const f32x4& p0, const f32x4& p1, f32x4& c) { mma_acc(a, p0, p1, c); }
-    // the same with the B operand already packed (MU_DKV_PKMUL: dS = P * dP' as four v_pk_mul_f16 on the packed halves)
+    // the same with the B operand already packed (dS = P * dP' as four v_pk_mul_f16 on the packed halves)
     using Packed = h16x8;
     static __device__ __forceinline__ Packed pack(const f32x4& p0, const f32x4& p1) {
         return (h16x8){(h16)p0[0], (h16)p0[1], (h16)p0[2], (h16)p0[3], (h16)p1[0], (h16)p1[1], (h16)p1[2], (h16)p1[3]};
@@ -367,26 +233,19 @@ template <> struct AT<xf32> {
     // dK/dV sweep (`_sb`: it is B) alike, so every sweep recomputes exactly the S the forward normalised with.  Sized on the CPU oracle
     // first (tests/aids/numerics_attn_single_term.py, KSINGLE / VSINGLE): outputs 2.0e-5 -> 2.3e-5, worst gradient 5.9e-3 -> 8.7e-3
     // (gates 1e-3 / 5e-2), the value operand without any measurable effect.  The lo halves of K / V stay in memory: P V, dS K keep them.
-#ifndef MU_XF_KSINGLE
-#define MU_XF_KSINGLE 1
-#endif
     static __device__ __forceinline__ void mma_row_sa(const Frag& a, const Frag& b, f32x4& c) {
-        if (!MU_XF_KSINGLE) { mma_row(a, b, c); return; }
         c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.lo, c, 0, 0, 0);
         c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.hi, c, 0, 0, 0);
     }
     static __device__ __forceinline__ void mma_row_sb(const Frag& a, const Frag& b, f32x4& c) {
-        if (!MU_XF_KSINGLE) { mma_row(a, b, c); return; }
         c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.lo, b.hi, c, 0, 0, 0);
         c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.hi, c, 0, 0, 0);
     }
     static __device__ __forceinline__ f32x4 mma_row_from_sa(const Frag& a, const Frag& b, const f32x4& c0) {
-        if (!MU_XF_KSINGLE) return mma_row_from(a, b, c0);
         f32x4 c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.lo, c0, 0, 0, 0);
         return __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.hi, c, 0, 0, 0);
     }
     static __device__ __forceinline__ f32x4 mma_row_from_sb(const Frag& a, const Frag& b, const f32x4& c0) {
-        if (!MU_XF_KSINGLE) return mma_row_from(a, b, c0);
         f32x4 c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.lo, b.hi, c0, 0, 0, 0);
         return __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.hi, c, 0, 0, 0);
     }
@@ -402,57 +261,31 @@ template <> struct AT<xf32> {
         c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, pack(p0, p1), c, 0, 0, 0);          // (the ones operand has no lo part)
     }
     // Round 6, BACKWARD sweeps only (the forward keeps the two-term products above: north_star's 1e-3 is a gate on OUTPUTS): dP = dO V^T
-    // (MU_XF_BWD_DP1) and the gradient products dV = P^T dO, dK = dS^T Q, dQ = dS K (MU_XF_BWD_G1) as ONE fp16 MFMA on the hi halves, i.e.
+    // (`_bp_`) and the gradient products dV = P^T dO, dK = dS^T Q, dQ = dS K (`mma_accb*`) as ONE fp16 MFMA on the hi halves, i.e.
     // the fp16 kernels' arithmetic on exactly scaled operands (dY carries its power-of-two scale, P its 2^pshift).  Each of these sums runs
     // over hundreds to thousands of keys / queries, and the 2^-12 operand roundings are random-signed: the sum carries ~2^-12 of the root-sum-square of its terms, below the single-term dS
     // noise these sweeps already have: the CPU sizing
     // (tests/aids/numerics_attn_single_term.py DP1 / DV1 / DK1 / DQ1 on the reference's golden) shows NO measurable change of any gradient
     // metric (worst parameter gradient 8.7e-3 with and without, gate 5e-2), and on the GPU the goldens' worst gradients did not move.
-    // The recomputed SCORES keep the forward's two terms (MU_XF_BWD_S1 = 0): with one term the backward's P is no longer the forward's
+    // The recomputed SCORES (`_bs_`) keep the forward's two terms: with one term the backward's P is no longer the forward's
     // (dQ / dK of the kernel-level check 6.4e-4 -> 1.1e-3 against its 1e-3 gate) for another 4.5 % of the step -- measured, not adopted.
-#ifndef MU_XF_BWD_S1
-#define MU_XF_BWD_S1 0
-#endif
-#ifndef MU_XF_BWD_DP1
-#define MU_XF_BWD_DP1 1
-#endif
-#ifndef MU_XF_BWD_G1
-#define MU_XF_BWD_G1 1
-#endif
-    static __device__ __forceinline__ void mma_row_bs_sa(const Frag& a, const Frag& b, f32x4& c) {
-        if (!MU_XF_BWD_S1) { mma_row_sa(a, b, c); return; }
-        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.hi, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ void mma_row_bs_sb(const Frag& a, const Frag& b, f32x4& c) {
-        if (!MU_XF_BWD_S1) { mma_row_sb(a, b, c); return; }
-        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.hi, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ f32x4 mma_row_from_bs_sa(const Frag& a, const Frag& b, const f32x4& c0) {
-        if (!MU_XF_BWD_S1) return mma_row_from_sa(a, b, c0);
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.hi, c0, 0, 0, 0);
-    }
-    static __device__ __forceinline__ f32x4 mma_row_from_bs_sb(const Frag& a, const Frag& b, const f32x4& c0) {
-        if (!MU_XF_BWD_S1) return mma_row_from_sb(a, b, c0);
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.hi, c0, 0, 0, 0);
-    }
+    static __device__ __forceinline__ void mma_row_bs_sa(const Frag& a, const Frag& b, f32x4& c) { mma_row_sa(a, b, c); }
+    static __device__ __forceinline__ void mma_row_bs_sb(const Frag& a, const Frag& b, f32x4& c) { mma_row_sb(a, b, c); }
+    static __device__ __forceinline__ f32x4 mma_row_from_bs_sa(const Frag& a, const Frag& b, const f32x4& c0) { return mma_row_from_sa(a, b, c0); }
+    static __device__ __forceinline__ f32x4 mma_row_from_bs_sb(const Frag& a, const Frag& b, const f32x4& c0) { return mma_row_from_sb(a, b, c0); }
     static __device__ __forceinline__ void mma_row_bp_sa(const Frag& a, const Frag& b, f32x4& c) {
-        if (!MU_XF_BWD_DP1) { mma_row_sa(a, b, c); return; }
         c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.hi, c, 0, 0, 0);
     }
     static __device__ __forceinline__ void mma_row_bp_sb(const Frag& a, const Frag& b, f32x4& c) {
-        if (!MU_XF_BWD_DP1) { mma_row_sb(a, b, c); return; }
         c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.hi, c, 0, 0, 0);
     }
     static __device__ __forceinline__ f32x4 mma_row_from_bp_sa(const Frag& a, const Frag& b, const f32x4& c0) {
-        if (!MU_XF_BWD_DP1) return mma_row_from_sa(a, b, c0);
         return __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.hi, c0, 0, 0, 0);
     }
     static __device__ __forceinline__ f32x4 mma_row_from_bp_sb(const Frag& a, const Frag& b, const f32x4& c0) {
-        if (!MU_XF_BWD_DP1) return mma_row_from_sb(a, b, c0);
         return __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.hi, c0, 0, 0, 0);
     }
     static __device__ __forceinline__ void mma_accb_pk(const AccA& a, const Packed& b, f32x4& c) {
-        if (!MU_XF_BWD_G1) { mma_acc_pk(a, b, c); return; }
         c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b, c, 0, 0, 0);
     }
     static __device__ __forceinline__ void mma_accb(const AccA& a, const f32x4& p0, const f32x4& p1, f32x4& c) { mma_accb_pk(a, pack(p0, p1), c); }
@@ -589,11 +422,7 @@ template <typename T, int D, int KT, int NW> struct KvStage {
             const int i = wave + NW * n;
             int j = j0 + i * Z::RPW + lrow;
             j = j < Nk ? j : Nk - 1;
-#ifdef MU_ATTN_ABL_NOIDX
-            idx[n] = j < 0 ? 0 : j;                          // timing-only ablation: contiguous rows instead of the kept-key gather
-#else
             idx[n] = kidx_b[j < 0 ? 0 : j];
-#endif
         }
     }
     // Rows past the end re-read a valid key row instead of a zero page: every consumer masks those keys through the score
@@ -687,8 +516,17 @@ template <int D> struct AccLd<xf32, D> {
     }
 };
 
+// Waves per SIMD the forward is bounded to (OCC = 0; measured in-process, B = 64).  fp16, C <= 64 (N = 16384): 2.  C = 128 (N = 4096):
+// without a bound the compiler takes ~320 registers (VGPR + AGPR) and runs ONE wave per SIMD; 0.624 -> 0.341 ms with a 2-waves bound and
+// 32-key tiles (168 VGPRs), 0.346 -> 0.301 ms with 3 once the 256-byte rows had their conflict-free swizzle.  C = 256 (N = 1024): the
+// 2-waves bound wins even with 26 spilled registers (0.134 -> 0.102 ms).  fp32x: 2 up to C = 128.  fp32 storage: one wave per SIMD.
+template <typename T, int D> constexpr int attn_fwd_occ() {
+    if (std::is_same<T, xf32>::value) return D <= 128 ? 2 : 1;
+    if (sizeof(T) == 2) return D == 128 ? 3 : 2;
+    return 1;
+}
 template <typename T, int D, int KT, int NW, int OCC = 0, int NQ = 2>
-__global__ __launch_bounds__(NW * 64, OCC ? OCC : ((NW == 4 && D <= 128 && std::is_same<T, xf32>::value) ? MU_XF_OCC : (NW == 4 && D <= 64 && sizeof(T) == 2) ? MU_FWD_OCC : ((NW == 4 && D == 128 && sizeof(T) == 2) ? MU_FWD_OCC128 : ((NW == 4 && D == 256 && sizeof(T) == 2) ? MU_FWD_OCC256 : 1)))) void attn_fwd2_kernel(const T* __restrict__ qkv, const T* __restrict__ x, const int* __restrict__ kidx,
+__global__ __launch_bounds__(NW * 64, (OCC ? OCC : attn_fwd_occ<T, D>())) void attn_fwd2_kernel(const T* __restrict__ qkv, const T* __restrict__ x, const int* __restrict__ kidx,
                                                         const int* __restrict__ kcnt, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, T* __restrict__ out, T* __restrict__ oattn,
                                                         float* __restrict__ lse2, float* __restrict__ ln_mean, float* __restrict__ ln_rstd,
@@ -697,7 +535,6 @@ __global__ __launch_bounds__(NW * 64, OCC ? OCC : ((NW == 4 && D <= 128 && std::
     using Frag = typename A::Frag;
     using Z = SwzTile<T, D>;
     constexpr int VN = A::VN, KR = A::KR, NKS = D / KR, NDT = D / 16, NKT = KT / 16, NH = KT / 32;
-    constexpr bool MU_PRIO_BWD = false;
     constexpr int TEK = Z::TE(KT);                                       // elements of one K (or V) tile image
     __shared__ __attribute__((aligned(16))) T lds[2 * 2 * TEK];          // [buf][K|V][tile image]
 
@@ -746,42 +583,25 @@ __global__ __launch_bounds__(NW * 64, OCC ? OCC : ((NW == 4 && D <= 128 && std::
         constexpr int BUF = decltype(BUFC)::value;
         constexpr bool EXACT = decltype(EXACTC)::value;
         const T* Kt = lds + BUF * 2 * TEK;
-        if constexpr (std::is_same<T, xf32>::value && MU_XF_OPAQUE) Kt = lds_opaque(Kt);
+        if constexpr (std::is_same<T, xf32>::value) Kt = lds_opaque(Kt);
         const T* Vt = Kt + TEK;
-#ifndef MU_FWD_ABL_NODMA
         if (j0 + KT < Nk) {
             T* Kn = lds + (BUF ^ 1) * 2 * TEK;
             stg.issue(Kn, Kn + TEK, qkv_b, wave, lane);
             stg.load_idx(kidx_b, j0 + 2 * KT, Nk, wave, lane);
         }
-#endif
         f32x4 s[NKT][NQ];
-        MU_PRIO(1);
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks)
 #pragma unroll
             for (int kt = 0; kt < NKT; ++kt) {
-#ifdef MU_FWD_ABL_NOS
-                // timing-only ablation: no K reads, no score MFMAs
-                if (ks == 0)
-                    for (int t = 0; t < NQ; ++t) { s[kt][t] = negm[t]; asm volatile("" : "+v"(s[kt][t])); }
-#else
                 Frag a = A::template ldt<Z>(Kt, kt * 16 + r16, ks * KR + g * A::GS);
 #pragma unroll
                 for (int t = 0; t < NQ; ++t) {
                     if (ks == 0) s[kt][t] = A::mma_row_from_sa(a, qf[t][0], negm[t]);     // -m rides in as the C operand
                     else A::mma_row_sa(a, qf[t][ks], s[kt][t]);
                 }
-#endif
             }
-        MU_PRIO(0);
-        constexpr int PREV = (MU_FWD_PREFETCH && sizeof(T) == 2) ? (MU_FWD_PREFETCH < NDT ? MU_FWD_PREFETCH : NDT) : 0;
-        typename A::AccA vap[PREV ? PREV : 1];
-        if constexpr (PREV > 0) {                    // transposed V operands of the first 32 keys: in flight during the softmax VALU
-#pragma unroll
-            for (int dt = 0; dt < PREV; ++dt) vap[dt] = AccLd<T, D>::ld(Vt, 0, dt * 16, g, r16);
-            __builtin_amdgcn_sched_barrier(0);
-        }
         const bool partial = j0 + KT > Nk;          // wave-uniform
 #pragma unroll
         for (int t = 0; t < NQ; ++t) {
@@ -826,46 +646,26 @@ __global__ __launch_bounds__(NW * 64, OCC ? OCC : ((NW == 4 && D <= 128 && std::
 #pragma unroll
             for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
-#ifdef MU_FWD_ABL_NOEXP
-                for (int r = 0; r < 4; ++r) s[kt][t][r] = s[kt][t][r] * 0.001f;          // timing-only ablation: no exponentials
-#else
                 for (int r = 0; r < 4; ++r) s[kt][t][r] = __builtin_amdgcn_exp2f(s[kt][t][r]);
-#endif
         }
-#ifdef MU_FWD_ABL_NOPV
-        // timing-only ablation: no V reads, no P.V / row-sum MFMAs (P kept live)
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-            for (int t = 0; t < NQ; ++t) asm volatile("" ::"v"(s[kt][t]));
-#else
-        MU_PRIO(1);
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
 #pragma unroll
             for (int t = 0; t < NQ; ++t) A::mma_ones(ones, s[2 * h][t], s[2 * h + 1][t], lacc[t]);
 #pragma unroll
             for (int dt = 0; dt < NDT; ++dt) {
-                typename A::AccA va;
-                if (h == 0 && dt < PREV) va = vap[dt];
-                else va = AccLd<T, D>::ld(Vt, 32 * h, dt * 16, g, r16);
+                const typename A::AccA va = AccLd<T, D>::ld(Vt, 32 * h, dt * 16, g, r16);
 #pragma unroll
                 for (int t = 0; t < NQ; ++t) A::mma_acc(va, s[2 * h][t], s[2 * h + 1][t], o[dt][t]);
             }
         }
-        MU_PRIO(0);
-#endif
-#ifdef MU_FWD_ABL_NOBAR
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
         MU_SYNC_DMA();        // tile j+1 landed (vmcnt(0)) and everyone is done reading tile j
-#endif
     };
     // Optimistic sweep first (wherever P is an fp16 operand: fp16 storage and fp32x): no per-tile running-max scan / cross-lane reduce / branch (13 % of the kernel at
     // N = 16384, C = 64: a serial dependent chain between the score MFMAs and the exponentials).  A row whose later scores exceed the
     // first tile's maximum by more than 16 (log2 units) overflows fp16 and leaves an infinite row sum: the whole block then repeats
     // the sweep with exact tracking (wave-uniform decision through the barrier; never taken on the model's data, forced in the tests).
-    constexpr bool OPTIMISTIC = MU_FWD_OPTIMISTIC && A::PK;
+    constexpr bool OPTIMISTIC = A::PK;
     bool redo = false;
     if (OPTIMISTIC) {
         for (int j0 = 0; j0 < Nk; j0 += 2 * KT) {
@@ -1174,10 +974,18 @@ extern "C" int mu_split_encode_h(const void* src, void* dst, long n_elems, void*
 // ------------------------------------------------------------------------------------------
 // backward v2 kernels: LDS-DMA double-buffered tiles, swizzled images (see attn_fwd2_kernel)
 // ------------------------------------------------------------------------------------------
-// NQT = 16-query tiles per wave (2 everywhere but C = 128: there one tile per wave halves the resident Q / dO fragments and the dQ
-// accumulators -- 222 -> ~130 registers in fp16, two -> three waves per SIMD)
+// NQT = 16-query tiles per wave
+// Waves per SIMD the dQ sweep is bounded to (OCCQ = 0; measured in-process, B = 64).  fp16, C <= 64 (N = 16384): 3 with 32-key tiles (152
+// VGPRs) 3.07 ms vs 64-key tiles (196 VGPRs) 3.22 ms; forcing 3 on the 64-key version spills into the loop: 10.97 ms.  C = 128 (N = 4096):
+// 0.520 -> 0.374 ms with a 2-waves bound (226 VGPRs, no spills); 3 spills.  C = 256 (N = 1024): a 2-waves bound LOSES (115 spills: 0.092 ->
+// 0.197 ms).  fp32x: 2 at C <= 64.  fp32 storage: one wave per SIMD.
+template <typename T, int D> constexpr int attn_dq_occ() {
+    if (std::is_same<T, xf32>::value) return D <= 64 ? 2 : 1;
+    if (sizeof(T) == 2) return D <= 64 ? 3 : (D == 128 ? 2 : 1);
+    return 1;
+}
 template <typename T, int D, int KT, int NW, int NQT = 2, int OCCQ = 0>
-__global__ __launch_bounds__(NW * 64, OCCQ ? OCCQ : (NW == 4 && D <= 64 && std::is_same<T, xf32>::value) ? MU_XF_DQ_OCC : (NW == 4 && D <= 64 && sizeof(T) == 2) ? MU_DQ_OCC : ((NW == 4 && D == 128 && sizeof(T) == 2) ? MU_DQ_OCC128 : ((NW == 4 && D == 256 && sizeof(T) == 2) ? MU_DQ_OCC256 : 1))) void attn_bwd_dq2_kernel(const T* __restrict__ qkv, const T* __restrict__ dY, const int* __restrict__ kidx,
+__global__ __launch_bounds__(NW * 64, (OCCQ ? OCCQ : attn_dq_occ<T, D>())) void attn_bwd_dq2_kernel(const T* __restrict__ qkv, const T* __restrict__ dY, const int* __restrict__ kidx,
                                                            const int* __restrict__ kcnt, const float* __restrict__ lse2,
                                                            const float* __restrict__ delta, T* __restrict__ dqkv, int N, int nkmax,
                                                            float scale, float scale_log2, const float* __restrict__ gsp, float pshift, int enc_out) {
@@ -1185,7 +993,6 @@ __global__ __launch_bounds__(NW * 64, OCCQ ? OCCQ : (NW == 4 && D <= 64 && std::
     using Frag = typename A::Frag;
     using Z = SwzTile<T, D>;
     constexpr int VN = A::VN, KR = A::KR, NKS = D / KR, NDT = D / 16, NKT = KT / 16, NH = KT / 32;
-    constexpr bool MU_PRIO_BWD = true;
     constexpr bool XF = std::is_same<T, xf32>::value;
     constexpr int TEK = Z::TE(KT);
     __shared__ __attribute__((aligned(16))) T lds[2 * 2 * TEK];
@@ -1239,7 +1046,7 @@ __global__ __launch_bounds__(NW * 64, OCCQ ? OCCQ : (NW == 4 && D <= 64 && std::
     auto tile = [&](auto BUFC, int j0) {
         constexpr int BUF = decltype(BUFC)::value;
         const T* Kt = lds + BUF * 2 * TEK;
-        if constexpr (XF && MU_XF_OPAQUE) Kt = lds_opaque(Kt);
+        if constexpr (XF) Kt = lds_opaque(Kt);
         const T* Vt = Kt + TEK;
         if (j0 + KT < Nk) {
             T* Kn = lds + (BUF ^ 1) * 2 * TEK;
@@ -1275,37 +1082,23 @@ __global__ __launch_bounds__(NW * 64, OCCQ ? OCCQ : (NW == 4 && D <= 64 && std::
                     for (int r = 0; r < 4; ++r)
                         if (j0 + kt * 16 + 4 * g + r >= Nk) { s[kt][t][r] = -INFINITY; dp[kt][t][r] = 0.f; }
         }
-        constexpr int PREQ = (MU_DQ_PREFETCH && sizeof(T) == 2 && NH == 1) ? (MU_DQ_PREFETCH < NDT ? MU_DQ_PREFETCH : NDT) : 0;
-        typename A::AccA kap[PREQ ? PREQ : 1];
-        if constexpr (PREQ > 0) {                    // transposed K operands of the dQ product: in flight during the exponentials
-#pragma unroll
-            for (int dt = 0; dt < PREQ; ++dt) kap[dt] = AccLd<T, D>::ld(Kt, 0, dt * 16, g, r16);
-            __builtin_amdgcn_sched_barrier(0);
-        }
 #pragma unroll
         for (int t = 0; t < NQT; ++t)
 #pragma unroll
             for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) s[kt][t][r] = __builtin_amdgcn_exp2f(s[kt][t][r]) * dp[kt][t][r];
-        if constexpr (PREQ > 0) __builtin_amdgcn_sched_barrier(0);
         MU_PRIO(1);
 #pragma unroll
         for (int h = 0; h < NH; ++h)
 #pragma unroll
             for (int dt = 0; dt < NDT; ++dt) {
-                typename A::AccA ka;
-                if (h == 0 && dt < PREQ) ka = kap[dt];
-                else ka = AccLd<T, D>::ld(Kt, 32 * h, dt * 16, g, r16);
+                const typename A::AccA ka = AccLd<T, D>::ld(Kt, 32 * h, dt * 16, g, r16);
 #pragma unroll
                 for (int t = 0; t < NQT; ++t) A::mma_accb(ka, s[2 * h][t], s[2 * h + 1][t], dq[dt][t]);
             }
         MU_PRIO(0);
-#ifdef MU_DQ_ABL_NOBAR
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
         MU_SYNC_DMA();
-#endif
     };
     for (int j0 = 0; j0 < Nk; j0 += 2 * KT) {
         tile(std::integral_constant<int, 0>{}, j0);
@@ -1347,8 +1140,15 @@ __global__ __launch_bounds__(NW * 64, OCCQ ? OCCQ : (NW == 4 && D <= 64 && std::
 // ------------------------------------------------------------------------------------------
 // NW = waves per block (16 * NKT keys each).  The Q / dO stream a block pulls through L2 -> LDS is shared by NW * NKT * 16 keys: at
 // C = 128 with 4 waves of 16 keys every launch moved 4.2 GB in 0.7 ms (6 TB/s, the L2 -> LDS ceiling) -- 8 waves halve that.
+// Waves per SIMD the sweep is bounded to (4-wave blocks; measured in-process, B = 64, N = 16384, C = 64 fp16): 3 waves/SIMD (168 VGPRs, 4 spilled)
+// 4.70 ms vs 2 waves/SIMD 5.24 ms; 1 wave/SIMD with 64 keys/wave 9 ms.  fp32x at C <= 64: 2.  C = 256 does not fit under any bound, and the
+// 8- and 12-wave blocks of C = 128 (attn_bwd_t) are alone on their CU.
+template <typename T, int D, int NW> constexpr int attn_dkv_occ() {
+    if (NW >= 8 || D > 64) return 1;
+    return std::is_same<T, xf32>::value ? 2 : (sizeof(T) == 2 ? 3 : 1);
+}
 template <typename T, int D, int NKT, int NW = 4>
-__global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : ((D <= 64 && std::is_same<T, xf32>::value) ? MU_XF_OCC : (D <= 64 && sizeof(T) == 2 && NKT <= 2) ? MU_DKV_OCC : ((D == 128 && sizeof(T) == 2 && NKT <= 2) ? MU_DKV_OCC128 : ((D == 256 && sizeof(T) == 2 && NKT == 1) ? MU_DKV_OCC256 : 1)))) void attn_bwd_dkv3_kernel(
+__global__ __launch_bounds__(NW * 64, (attn_dkv_occ<T, D, NW>())) void attn_bwd_dkv3_kernel(
     const T* __restrict__ qkv, const T* __restrict__ dY, const int* __restrict__ kidx, const int* __restrict__ kcnt,
     const float* __restrict__ rowc, T* __restrict__ dqkv, int N, int nkmax, float scale, float scale_log2, int zero_masked,
     const float* __restrict__ gsp, float pshift) {
@@ -1356,7 +1156,6 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : ((D <= 64 && std::is_same<T,
     using Frag = typename A::Frag;
     using Z = SwzTile<T, D>;
     constexpr int VN = A::VN, KR = A::KR, NKS = D / KR, NDT = D / 16, QT = 32;
-    constexpr bool MU_PRIO_BWD = true;
     constexpr int NI = QT / Z::RPW;                          // DMA wave-instructions per tensor per tile
     static_assert(NI == 4 || NI == 8 || NI == 16 || NI == 32 || NI == 2, "unexpected tile geometry");
     constexpr int NPW = (NI + NW - 1) / NW;                  // per wave (Q and dO each)
@@ -1433,13 +1232,8 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : ((D <= 64 && std::is_same<T,
         // row constants: 16 lanes x 16 B = the tile's 64 floats.  Every wave issues one DMA so that all waves count the same
         // number of vector-memory ops: wave 0's lanes >= 16 repeat the constants into the unused rest of the slot, waves 1-3
         // write theirs to a dump area
-#if MU_DKV_ROWC_ONE
-        // only wave 0 moves the row constants; the other waves count one DMA less per tile (wave-uniform branch on the waits below)
-        if (wave == 0) glds16s(rowc_b + (long)tile * 64, (uint32_t)((lane & 15) * 16), rcs + slot * 256);
-#else
         if (NW <= NI || wave < NI)
             glds16s(rowc_b + (long)tile * 64, (uint32_t)((lane & 15) * 16), rcs + (wave == 0 ? slot * 256 : DKV_RING * 256));
-#endif
     };
     constexpr int OPS = 2 * NPW + 1;
 
@@ -1447,9 +1241,6 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : ((D <= 64 && std::is_same<T,
     if (DKV_RING == 4) {
         if (ntile > 1) issue(1);
         if (ntile > 2) issue(2);
-#ifdef MU_DKV_ABL_NODMA
-        if (ntile > 3) issue(3);                             // timing-only ablation: all four slots hold real data, no DMA in the loop
-#endif
     }
 
     Frag kf[NKT][NKS], vf[NKT][NKS];
@@ -1485,31 +1276,12 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : ((D <= 64 && std::is_same<T,
         constexpr int SLOT = decltype(SLOTC)::value;
         // tile tl's DMAs were issued RING-1 issue-groups ago; newer groups still in flight: min(RING-2, tiles left after tl)
         const int newer = ntile - 1 - tl;
-#ifdef MU_DKV_ABL_NODMA
-        if (tl == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else
-#endif
-#if MU_DKV_ROWC_ONE
-        if (DKV_RING == 4 && newer >= 2) {
-            if (wave == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * OPS) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (OPS - 1)) : "memory");
-        } else if (DKV_RING == 4 && newer == 1) {
-            if (wave == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(OPS) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(OPS - 1) : "memory");
-        }
-#else
         if (DKV_RING == 4 && newer >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * OPS) : "memory");
         else if (DKV_RING == 4 && newer == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(OPS) : "memory");
-#endif
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifndef MU_DKV_ABL_NOBAR
         __builtin_amdgcn_s_barrier();                        // everyone's share of tile tl landed; tile tl-1 fully consumed
-#endif
-#ifdef MU_DKV_ISSUE_FIRST
-        if (tl + DKV_RING - 1 < ntile) issue(tl + DKV_RING - 1);
-#endif
         const T* Qt = lds + SLOT * STG;
-        if constexpr ((std::is_same<T, xf32>::value && MU_XF_OPAQUE) || (sizeof(T) == 2 && D >= 128 && MU_H16_OPAQUE)) Qt = lds_opaque(Qt);
+        if constexpr (std::is_same<T, xf32>::value) Qt = lds_opaque(Qt);
         const T* Ot = Qt + TEQ;
         const float* rc = rcs + SLOT * 256;
         f32x4 s[2][NKT], dp[2][NKT];
@@ -1536,7 +1308,6 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : ((D <= 64 && std::is_same<T,
                         A::mma_row_bp_sb(oa, vf[kt][ks], dp[qt][kt]);
                     }
                 }
-                if constexpr (std::is_same<T, xf32>::value && D >= 128 && MU_XF_DKV_SCHED2) { if (qt == 1) __builtin_amdgcn_sched_barrier(0); }
             }
         MU_PRIO(0);
         if (tl * QT + QT > N) {                              // last, partial tile: padded queries contribute nothing
@@ -1549,26 +1320,11 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : ((D <= 64 && std::is_same<T,
                         for (int kt = 0; kt < NKT; ++kt) { s[qt][kt][r] = -INFINITY; dp[qt][kt][r] = 0.f; }
                     }
         }
-        // The transposed dO / Q operands of the dV / dK products are read from LDS BEFORE the exponentials (PRE of the NDT column
-        // blocks): their latency then hides behind the VALU phase instead of standing, once per column block, between the MFMAs
-        // (the compiler otherwise issues each block's reads right in front of its MFMAs: ~60 idle cycles per block per wave).
-        constexpr int PFN = D == 128 ? MU_DKV_PREFETCH128 : MU_DKV_PREFETCH;
-        constexpr int PRE = (PFN && sizeof(T) == 2) ? (PFN < NDT ? PFN : NDT) : 0;
-        typename A::AccA oap[PRE ? PRE : 1], qap[PRE ? PRE : 1];
-        if constexpr (PRE > 0) {
-#pragma unroll
-            for (int dt = 0; dt < PRE; ++dt) {
-                oap[dt] = AccLd<T, D>::ld(Ot, 0, dt * 16, g, r16);
-                qap[dt] = AccLd<T, D>::ld(Qt, 0, dt * 16, g, r16);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // MU_DKV_PKMUL (fp16 storage): P and dP' are rounded to fp16 first -- both are fp16 MFMA operands' worth of precision anyway --
+        // fp16 storage: P and dP' are rounded to fp16 first -- both are fp16 MFMA operands' worth of precision anyway --
         // and dS = P * dP' is FOUR packed fp16 multiplies per 8 scores instead of 8 fp32 ones: 24 instead of 32 VALU instructions per
         // 32-query x 32-key tile behind the 16 exponentials (the sweep runs at MFMA + VALU issue time)
         // fp32x takes the same path (the row constants carry the power-of-two scales that keep P and dP' inside fp16's range: attn_bwd_t)
-        constexpr bool PKMUL = (MU_DKV_PKMUL && sizeof(T) == 2) || (std::is_same<T, xf32>::value && D < MU_XF_PK_MAXD);
-        if constexpr (PKMUL) {
+        if constexpr (A::PK) {
             typename A::Packed pb[NKT], db[NKT];
 #pragma unroll
             for (int qt = 0; qt < 2; ++qt)
@@ -1581,21 +1337,15 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : ((D <= 64 && std::is_same<T,
                 pb[kt] = A::pack(s[0][kt], s[1][kt]);
                 db[kt] = A::pack(dp[0][kt], dp[1][kt]) * pb[kt];
             }
-            if constexpr (PRE > 0) __builtin_amdgcn_sched_barrier(0);
             MU_PRIO(1);
 #pragma unroll
             for (int dt = 0; dt < NDT; ++dt) {
-                typename A::AccA oa, qa;
-                if (dt < PRE) { oa = oap[dt]; qa = qap[dt]; }
-                else { oa = AccLd<T, D>::ld(Ot, 0, dt * 16, g, r16); qa = AccLd<T, D>::ld(Qt, 0, dt * 16, g, r16); }
+                const typename A::AccA oa = AccLd<T, D>::ld(Ot, 0, dt * 16, g, r16), qa = AccLd<T, D>::ld(Qt, 0, dt * 16, g, r16);
 #pragma unroll
                 for (int kt = 0; kt < NKT; ++kt) {
                     A::mma_accb_pk(oa, pb[kt], dv[dt][kt]);
                     A::mma_accb_pk(qa, db[kt], dk[dt][kt]);
                 }
-                // fp32x at C >= 128: the resident K / V pairs and the accumulators alone are 128 registers; left alone the scheduler
-                // hoists the transposed reads of ALL column blocks (16 registers each) above the first MFMA and spills ~130 registers
-                if constexpr (std::is_same<T, xf32>::value && D >= 128 && MU_XF_DKV_SCHED) { if (dt % MU_XF_DKV_SCHED == MU_XF_DKV_SCHED - 1) __builtin_amdgcn_sched_barrier(0); }
             }
             MU_PRIO(0);
         } else {
@@ -1609,13 +1359,10 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : ((D <= 64 && std::is_same<T,
                     s[qt][kt][r] = p;
                     dp[qt][kt][r] *= p;
                 }
-        if constexpr (PRE > 0) __builtin_amdgcn_sched_barrier(0);
         MU_PRIO(1);
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt) {
-            typename A::AccA oa, qa;
-            if (dt < PRE) { oa = oap[dt]; qa = qap[dt]; }
-            else { oa = AccLd<T, D>::ld(Ot, 0, dt * 16, g, r16); qa = AccLd<T, D>::ld(Qt, 0, dt * 16, g, r16); }
+            const typename A::AccA oa = AccLd<T, D>::ld(Ot, 0, dt * 16, g, r16), qa = AccLd<T, D>::ld(Qt, 0, dt * 16, g, r16);
 #pragma unroll
             for (int kt = 0; kt < NKT; ++kt) {
                 A::mma_accb(oa, s[0][kt], s[1][kt], dv[dt][kt]);
@@ -1626,9 +1373,7 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : ((D <= 64 && std::is_same<T,
         }
         // Refill the slot tile tl-1 vacated -- issued LAST in the tile: LDS reads queue behind an in-flight LDS-DMA issue
         // (in-kernel s_memtime stamps: the row-constant reads right after the DMA cost ~980 cycles/tile, ~80 without it)
-#if !defined(MU_DKV_ISSUE_FIRST) && !defined(MU_DKV_ABL_NODMA)
         if (tl + DKV_RING - 1 < ntile) issue(tl + DKV_RING - 1);
-#endif
     };
     for (int tl = 0; tl < ntile; tl += DKV_RING) {
         tile(std::integral_constant<int, 0>{}, tl);
@@ -1680,17 +1425,11 @@ static int attn_fwd_t(const T* qkv, const T* x, const int* kidx, const int* kcnt
     switch (C) {
         case 32: LAUNCH_FWD(32, 64); break;
         case 64:
-            if constexpr (std::is_same<T, xf32>::value && MU_XF_FWD_KT32)       // 32-key tiles: 32 KB of LDS and <= 168 registers -> three waves per SIMD
+            if constexpr (std::is_same<T, xf32>::value)       // 32-key tiles: 32 KB of LDS and <= 168 registers -> three waves per SIMD
                 attn_fwd2_kernel<T, 64, 32, 4, 3><<<dim3(mu_cdiv(N, 128), B), 256, 0, st>>>(qkv, x, kidx, kcnt, gamma, beta, out, oattn, lse2, mean, rstd, N, nkmax, sl2, eps);
             else LAUNCH_FWD(64, 64);
             break;
-        case 128:
-#if MU_FWD_NW128 == 8
-            attn_fwd2_kernel<T, 128, MU_FWD_KT128, 8, 1><<<dim3(mu_cdiv(N, 256), B), 512, 0, st>>>(qkv, x, kidx, kcnt, gamma, beta, out, oattn, lse2, mean, rstd, N, nkmax, sl2, eps);
-#else
-            LAUNCH_FWD(128, MU_FWD_KT128);
-#endif
-            break;
+        case 128: LAUNCH_FWD(128, 32); break;
         case 256: LAUNCH_FWD(256, 32); break;
         default: return MU_ERR_SHAPE;
     }
@@ -1775,6 +1514,10 @@ static int attn_bwd_t(const T* qkv, const T* x, const T* oattn, const T* gout, c
     // lives in the workspace behind the row constants, and `dYs` is what the sweeps read
     const T* dYs = dY;
     if constexpr (XF) dYs = (const T*)((char*)ws + attn_ln_part_bytes(C) + attn_amax_bytes() + attn_rowc_bytes(B, N));
+    // dK/dV waves per block (16 * NKT keys each).  C = 128, fp16: 12-wave blocks = 3 waves/SIMD at 168 VGPRs (in-process, N = 4096: 4 waves
+    // x 2 blocks 0.68, 8 waves 0.67, 12 waves 0.58 ms) with 16 keys per wave (NKT = 1, 150 VGPRs: 1.174 -> 0.959 ms; the 32-key version spills).
+    // C = 128, fp32x: the 4-deep Q / dO ring takes 128 KB, so a 4-wave block is alone on its CU (one wave per SIMD: matrix pipe busy 25 %);
+    // 8 waves share the ring (two per SIMD, 16 keys each).  Everything else: 4 waves.
 #define LAUNCH_BWD(DD, NKT)                                                                                                     \
     if (phases & 1) {                                                                                                           \
         attn_ln_bwd_kernel<TS, DD><<<nblk, 256, 0, st>>>((const TS*)gout, (const TS*)oattn, (const TS*)x, mean, rstd, gamma, (TS*)dY, delta, (double*)ws, rows, lse2, rowc, N, scale, cv, pshift, XF ? amaxp : nullptr); \
@@ -1785,29 +1528,17 @@ static int attn_bwd_t(const T* qkv, const T* x, const T* oattn, const T* gout, c
             attn_dy_encode_kernel<<<(int)(gr < 1 ? 1 : (gr > 8192 ? 8192 : gr)), 256, 0, st>>>((const f32x4*)dY, (uint4*)dYs, rowc, gsc, ng, DD / 8, N); \
         }                                                                                                                       \
     }                                                                                                                           \
-    if (phases & 2) {                                                                                                           \
-        if constexpr (DD == 128 && MU_DQ_NQT128 == 1)                                                                           \
-            attn_bwd_dq2_kernel<T, DD, KTQ, 4, 1, MU_DQ_OCC128_Q1><<<dim3(mu_cdiv(N, 64), B), 256, 0, st>>>(qkv, dYs, kidx, kcnt, lse2, delta, dqkv, N, nkmax, scale, sl2, gsc, pshift, enc_out); \
-        else                                                                                                                    \
-            attn_bwd_dq2_kernel<T, DD, KTQ, 4><<<gq, 256, 0, st>>>(qkv, dYs, kidx, kcnt, lse2, delta, dqkv, N, nkmax, scale, sl2, gsc, pshift, enc_out); \
-    }                                                                                                                           \
+    if (phases & 2)                                                                                                             \
+        attn_bwd_dq2_kernel<T, DD, KTQ, 4><<<gq, 256, 0, st>>>(qkv, dYs, kidx, kcnt, lse2, delta, dqkv, N, nkmax, scale, sl2, gsc, pshift, enc_out); \
     if (phases & 4) {                                                                                                           \
-        if constexpr (sizeof(T) == 2 && DD == 64 && MU_DKV_NW64 != 4)                                                           \
-            attn_bwd_dkv3_kernel<T, DD, NKT, MU_DKV_NW64><<<dim3(mu_cdiv(nkmax, 16 * MU_DKV_NW64 * NKT), B), 64 * MU_DKV_NW64, 0, st>>>(qkv, dYs, kidx, kcnt, rowc, dqkv, N, nkmax, scale, sl2, zero_masked, gsc, pshift); \
-        else if constexpr (sizeof(T) == 2 && DD == 128 && MU_DKV_NW128 != 4)                                                         \
-            attn_bwd_dkv3_kernel<T, DD, NKT, MU_DKV_NW128><<<dim3(mu_cdiv(nkmax, 16 * MU_DKV_NW128 * NKT), B), 64 * MU_DKV_NW128, 0, st>>>(qkv, dYs, kidx, kcnt, rowc, dqkv, N, nkmax, scale, sl2, zero_masked, gsc, pshift); \
-        else if constexpr (std::is_same<T, xf32>::value && DD == 128 && MU_XF_DKV_NW128 != 4)                                    \
-            attn_bwd_dkv3_kernel<T, DD, NKT, MU_XF_DKV_NW128><<<dim3(mu_cdiv(nkmax, 16 * MU_XF_DKV_NW128 * NKT), B), 64 * MU_XF_DKV_NW128, 0, st>>>(qkv, dYs, kidx, kcnt, rowc, dqkv, N, nkmax, scale, sl2, zero_masked, gsc, pshift); \
-        else if constexpr (sizeof(T) == 2 && DD == 256 && MU_DKV_NW256 == 8)                                                    \
-            attn_bwd_dkv3_kernel<T, DD, NKT, 8><<<dim3(mu_cdiv(nkmax, 128 * NKT), B), 512, 0, st>>>(qkv, dYs, kidx, kcnt, rowc, dqkv, N, nkmax, scale, sl2, zero_masked, gsc, pshift); \
-        else                                                                                                                    \
-            attn_bwd_dkv3_kernel<T, DD, NKT><<<dim3(mu_cdiv(nkmax, 64 * NKT), B), 256, 0, st>>>(qkv, dYs, kidx, kcnt, rowc, dqkv, N, nkmax, scale, sl2, zero_masked, gsc, pshift); \
+        constexpr int NWK = DD != 128 ? 4 : (sizeof(T) == 2 ? 12 : (XF ? 8 : 4));                                               \
+        attn_bwd_dkv3_kernel<T, DD, NKT, NWK><<<dim3(mu_cdiv(nkmax, 16 * NWK * NKT), B), 64 * NWK, 0, st>>>(qkv, dYs, kidx, kcnt, rowc, dqkv, N, nkmax, scale, sl2, zero_masked, gsc, pshift); \
     }
     if (N % 4) return MU_ERR_SHAPE;
     switch (C) {
         case 32: { constexpr int KTQ = 64; LAUNCH_BWD(32, 2); } break;
-        case 64: { constexpr int KTQ = MU_DQ_KT; LAUNCH_BWD(64, 2); } break;
-        case 128: { constexpr int KTQ = 32; LAUNCH_BWD(128, MU_DKV_NKT128); } break;
+        case 64: { constexpr int KTQ = 32; LAUNCH_BWD(64, 2); } break;
+        case 128: { constexpr int KTQ = 32; LAUNCH_BWD(128, 1); } break;
         case 256: { constexpr int KTQ = 32; LAUNCH_BWD(256, 1); } break;
         default: return MU_ERR_SHAPE;
     }

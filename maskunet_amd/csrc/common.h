@@ -218,22 +218,6 @@ __device__ __forceinline__ float mu_act_grad(float x, int act) {
     return act == MU_ACT_GELU ? mu_gelu_grad(x) : (act == MU_ACT_RELU ? (x > 0.f ? 1.f : 0.f) : 1.f);
 }
 
-// Exact-GELU pieces for fp16 storage: Phi(x) = 0.5 erfc(-x/sqrt2) from the Abramowitz-Stegun 7.1.26 rational form
-// erfc(z) = t (a1 + t (a2 + ...)) exp(-z^2), t = 1/(1 + p z), |abs error| <= 1.5e-7 * exp(-z^2) -- three decimal orders
-// below the fp16 rounding of the result -- with one v_rcp and one v_exp instead of the ~40-instruction erff.  The
-// negative side is evaluated as erfc directly (no 1 - erf cancellation).  *pdf = exp(-x^2/2), shared with the gradient.
-__device__ __forceinline__ float mu_phi_fast(float x, float* e_out) {
-    const float z = fabsf(x) * 0.70710678118654752440f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
-    float p = fmaf(t, 1.061405429f, -1.453152027f);
-    p = fmaf(t, p, 1.421413741f);
-    p = fmaf(t, p, -0.284496736f);
-    p = fmaf(t, p, 0.254829592f);
-    const float e = __builtin_amdgcn_exp2f(x * x * -0.72134752044448170368f);      // exp(-x^2/2)
-    const float q = 0.5f * t * p * e;
-    *e_out = e;
-    return x < 0.f ? q : 1.0f - q;
-}
 // The BatchNorm passes are VALU-bound on GELU, not HBM-bound (30 instructions per element against 4-6 bytes: the backward statistics
 // sweep ran at 3.8 TB/s), so the fp16-storage path evaluates Phi and GELU' as odd minimax polynomials in fp32 -- no v_exp / v_rcp, 10-12
 // instructions instead of ~20 (two of them quarter-rate):
@@ -241,11 +225,7 @@ __device__ __forceinline__ float mu_phi_fast(float x, float* e_out) {
 //   GELU'(x) ~ 0.5 + xc R(xc^2),  xc = clamp(x, +-4.5),  deg R = 9:  |error| <= 2.05e-4 (fp32 Horner included)
 // i.e. below half an fp16 ulp of the stored results around |y| >= 0.25 and far inside the fp16 path's 3e-2 parity gate; fp32 storage
 // keeps erff (exact).  Beyond the clamp the polynomials are constants, not the exact limits: Phi~(-4.25) = 3e-7, so x Phi~(x) is
-// -3e-7 |x| instead of 0 for large negative x (-0.018 at x = -6e4, the edge of fp16), and GELU' saturates at 1.00007 / -7e-5.  Fitted against erf in fp64 (weighted least squares iterated to equi-ripple); MU_GELU_POLY=0 restores the
-// erfc rational form above (|error| < 2e-7).
-#ifndef MU_GELU_POLY
-#define MU_GELU_POLY 1
-#endif
+// -3e-7 |x| instead of 0 for large negative x (-0.018 at x = -6e4, the edge of fp16), and GELU' saturates at 1.00007 / -7e-5.  Fitted against erf in fp64 (weighted least squares iterated to equi-ripple).
 __device__ __forceinline__ float mu_phi_poly(float x) {
     const float xc = __builtin_amdgcn_fmed3f(x, -4.25f, 4.25f);
     const float t = xc * xc;
@@ -277,9 +257,6 @@ __device__ __forceinline__ float mu_gelu_grad_poly(float x) {
 }
 // Two elements per instruction: the Horner chains as packed fp32 FMAs (v_pk_fma_f32, twice the scalar rate in a VALU-bound kernel).
 // Same coefficients and operation order per element as the scalar forms above -> bit-identical results.
-#ifndef MU_GELU_PK
-#define MU_GELU_PK 1
-#endif
 typedef float mu_f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ mu_f32x2 mu_phi_poly2(mu_f32x2 x) {
     const mu_f32x2 xc = {__builtin_amdgcn_fmed3f(x[0], -4.25f, 4.25f), __builtin_amdgcn_fmed3f(x[1], -4.25f, 4.25f)};
@@ -313,11 +290,7 @@ __device__ __forceinline__ mu_f32x2 mu_gelu_grad_poly2(mu_f32x2 x) {
 template <bool FAST>
 __device__ __forceinline__ float mu_act_t(float x, int act) {
     if (act == MU_ACT_GELU) {
-        if (FAST) {
-            if (MU_GELU_POLY) return x * mu_phi_poly(x);
-            float e;
-            return x * mu_phi_fast(x, &e);
-        }
+        if (FAST) return x * mu_phi_poly(x);
         return mu_gelu(x);
     }
     return act == MU_ACT_RELU ? fmaxf(x, 0.f) : x;
@@ -325,12 +298,7 @@ __device__ __forceinline__ float mu_act_t(float x, int act) {
 template <bool FAST>
 __device__ __forceinline__ float mu_act_grad_t(float x, int act) {
     if (act == MU_ACT_GELU) {
-        if (FAST) {
-            if (MU_GELU_POLY) return mu_gelu_grad_poly(x);
-            float e;
-            const float phi = mu_phi_fast(x, &e);
-            return fmaf(x * 0.39894228040143267794f, e, phi);
-        }
+        if (FAST) return mu_gelu_grad_poly(x);
         return mu_gelu_grad(x);
     }
     return act == MU_ACT_RELU ? (x > 0.f ? 1.f : 0.f) : 1.f;
@@ -339,7 +307,7 @@ __device__ __forceinline__ float mu_act_grad_t(float x, int act) {
 // act / act' of two elements: the packed polynomials on the fp16-storage GELU path, the scalar forms otherwise
 template <bool FAST>
 __device__ __forceinline__ void mu_act2_t(float x0, float x1, int act, float& o0, float& o1) {
-    if (FAST && MU_GELU_POLY && MU_GELU_PK && act == MU_ACT_GELU) {
+    if (FAST && act == MU_ACT_GELU) {
         const mu_f32x2 x = {x0, x1};
         const mu_f32x2 r = x * mu_phi_poly2(x);
         o0 = r[0];
@@ -351,7 +319,7 @@ __device__ __forceinline__ void mu_act2_t(float x0, float x1, int act, float& o0
 }
 template <bool FAST>
 __device__ __forceinline__ void mu_act_grad2_t(float x0, float x1, int act, float& o0, float& o1) {
-    if (FAST && MU_GELU_POLY && MU_GELU_PK && act == MU_ACT_GELU) {
+    if (FAST && act == MU_ACT_GELU) {
         const mu_f32x2 r = mu_gelu_grad_poly2(mu_f32x2{x0, x1});
         o0 = r[0];
         o1 = r[1];

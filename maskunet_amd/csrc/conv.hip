@@ -122,8 +122,7 @@ __device__ __forceinline__ float epi_act(float v, int act) { return mu_act_t<siz
 // HL (round 6, T = h16 only: the two-term data gradient of the fp32x 3x3 layers, mu_conv_dgrad_h): x is the ONE-term fp16 dy, w the "HL"
 // weight rows [Cin lo | Cin hi] of 2 * Cin halves (elementwise.hip mu_prep_weight), the K loop walks every input chunk twice -- against
 // the lo halves, then against the hi halves -- and the result leaves as fp32 rows yf, multiplied by oscale[1] / 2^MU_XH_WSHIFT.
-// HL = 2: both halves (two MFMAs per product); HL = 1: the hi halves only -- the weights of the data gradient as ONE fp16 term (one MFMA
-// per product: sized on the oracle like everything else, NOTES_r06 §2b); HL = 0: the ordinary kernel.
+// HL = 2: both halves (two MFMAs per product); HL = 0: the ordinary kernel.
 template <typename T, int TM, int TN, int WR, int TAPS, bool FEPI = false, int HL = 0>
 __global__ __launch_bounds__(256) void conv_nt_kernel(const T* __restrict__ x, const T* __restrict__ w, const float* __restrict__ bias,
                                                       T* __restrict__ y, int B, int H, int W, int Cin, int Cout, long x_ld, long y_ld,
@@ -176,7 +175,7 @@ __global__ __launch_bounds__(256) void conv_nt_kernel(const T* __restrict__ x, c
     uint4 ra[NA], rb[NB];
 
     auto gload = [&](int s) {
-        const int tap = s / kchunks, ciw = (s % kchunks) * KC + (HL == 1 ? Cin : 0);
+        const int tap = s / kchunks, ciw = (s % kchunks) * KC;
         const int ci0 = HL ? (ciw >= Cin ? ciw - Cin : ciw) : ciw;
         const int dh = TAPS == 9 ? tap / 3 - 1 : 0, dw = TAPS == 9 ? tap % 3 - 1 : 0;
 #pragma unroll
@@ -359,23 +358,11 @@ __device__ __forceinline__ void glds16a(const void* gsrc, void* lds_wave_base) {
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(l), "v"(gsrc) : "memory");
 }
 
-#ifndef MU_NT2_SB_OCC
-#define MU_NT2_SB_OCC 3
-#endif
-#ifndef MU_NT2_OCC
-#define MU_NT2_OCC 2
-#endif
-#ifndef MU_NT2_EPI
-#define MU_NT2_EPI 1        // fp16: stage the output tile in LDS and store whole rows
-#endif
 // SB: the whole reduction is ONE stage (1x1, Cin == one 128-byte row): a single LDS buffer, so more blocks fit a CU -- the block is
 // load -> multiply -> store with nothing to pipeline inside it, only other resident blocks hide its latencies.
-#ifndef MU_NT2_SB
-#define MU_NT2_SB 1
-#endif
 #define MU_NT2_ENC_H (-1)       // `act` of the fp32x training instantiation: write y in the attention operand encoding (mu_conv1x1_fwd_enc_h)
 template <typename T, int TM, int TN, int WR, int TAPS, bool SB = false, bool FEPI = false>
-__global__ __launch_bounds__(256, SB ? MU_NT2_SB_OCC : MU_NT2_OCC) void conv_nt2_kernel(const T* __restrict__ x, const T* __restrict__ w, const float* __restrict__ bias,
+__global__ __launch_bounds__(256, SB ? 3 : 2) void conv_nt2_kernel(const T* __restrict__ x, const T* __restrict__ w, const float* __restrict__ bias,
                                                        T* __restrict__ y, int B, int H, int W, int Cin, int Cout, long x_ld, long y_ld,
                                                        const T* __restrict__ addend = nullptr, const float* __restrict__ scale = nullptr,
                                                        int act = 0) {
@@ -390,7 +377,7 @@ __global__ __launch_bounds__(256, SB ? MU_NT2_SB_OCC : MU_NT2_OCC) void conv_nt2
     constexpr int STAGE = (BCO + BPX) * 128;
 
     constexpr int OPITCH = BCO * 2 + 16;                    // fp16 epilogue: the block's output tile staged as [pixel][channel] rows
-    constexpr bool EPI = sizeof(T) == 2 && (SB || MU_NT2_EPI);
+    constexpr bool EPI = sizeof(T) == 2;                    // fp16: stage the output tile in LDS and store whole rows
     constexpr int LDS0 = (SB ? 1 : 2) * STAGE;
     constexpr int LDSB = EPI && BPX * OPITCH > LDS0 ? BPX * OPITCH : LDS0;
 
@@ -588,15 +575,6 @@ __global__ __launch_bounds__(256, SB ? MU_NT2_SB_OCC : MU_NT2_OCC) void conv_nt2
 // activation L2->LDS traffic 9x (v2 is pinned at the ~10 TB/s L2->LDS ceiling on the Cin<=256 layers).
 // The next chunk's halo is streamed in 1/6 pieces behind the first six tap steps.
 // ------------------------------------------------------------------------------------------
-#ifndef MU_NT3_RING
-#define MU_NT3_RING 1
-#endif
-#ifndef MU_NT3_ABL_WONCE
-#define MU_NT3_ABL_WONCE 0
-#endif
-#ifndef MU_NT3_STATS
-#define MU_NT3_STATS 1          // BatchNorm-statistics epilogue of the halo-tile kernel (fp16 and fp32x training launches)
-#endif
 // Per-channel (sum, sum of squares) of a wave's staged 64-pixel x 64-channel output tile, taken from the SAME fp16-rounded
 // values that were just stored (what BatchNorm will read): lane = (pixel sub-index lane>>3, 8-channel group q), 8 pixels per lane,
 // then the eight lanes of a channel group are folded with xor-shuffles and lanes 0-7 write 8 channels x {sum, sumsq} each.
@@ -654,7 +632,7 @@ __device__ __forceinline__ void conv_nt3_body(const T* __restrict__ x, const T* 
     // parked 48 %, MFMA pipe 26 % busy).  Exactly PA + 1 DMAs per wave per tap (dummies to a dump page keep the counts uniform).
     // In-process A/B: 128 -> 64 @128^2 0.226 -> 0.203 ms; with a single 64-channel chunk (9 taps per tile) the longer prologue
     // costs more than the waits it removes (64 -> 64 @128^2 0.110 -> 0.116 ms), so the launcher picks RINGP for Cin >= 128 only.
-    constexpr bool RING = RINGP && MU_NT3_RING && sizeof(T) == 2 && BCO == 64;
+    constexpr bool RING = RINGP && sizeof(T) == 2 && BCO == 64;
     constexpr int NWS = RING ? 3 : 2;
 
     __shared__ __attribute__((aligned(16))) char lds[2 * HBYTES + NWS * WBYTES + (RING ? 1024 : 0)];
@@ -702,7 +680,7 @@ __device__ __forceinline__ void conv_nt3_body(const T* __restrict__ x, const T* 
 
     auto stage_w = [&](int s, int buf) {
         const int tap = s % 9, c_ = s / 9;
-        const int ci0 = HL2 ? ((c_ & 1) ? Cin : 0) + (c_ >> 1) * KC : (HL == 1 ? Cin : 0) + c_ * KC;
+        const int ci0 = HL2 ? ((c_ & 1) ? Cin : 0) + (c_ >> 1) * KC : c_ * KC;
         const T* wb = w + (long)tap * Cout * Cw + ci0;       // wave-uniform
         char* Wb = Ws + buf * WBYTES;
 #pragma unroll
@@ -759,15 +737,11 @@ __device__ __forceinline__ void conv_nt3_body(const T* __restrict__ x, const T* 
                     if (t < HPW && next_h(c) && t * NWV + wave < HINST) stage_h(t, hchunk(c + 1) * KC, hchunk(c + 1) & 1);
                     else glds16(mu_zero_page, dump);
                 } else {
-#if MU_NT3_ABL_WONCE            // timing-only ablation (wrong results): weights staged once, no per-tap wait -- upper bound of a weights-resident kernel
-                if (false) stage_w(s + 1, (s + 1) & 1);
-#else
                 if (s + 1 < nsteps) stage_w(s + 1, (s + 1) & 1);
-#endif
                 if (t < HPW && next_h(c) && t * NWV + wave < HINST)        // one halo piece of the next chunk per tap step
                     stage_h(t, hchunk(c + 1) * KC, hchunk(c + 1) & 1);
                 }
-                const char* Wb = Ws + (RING ? wslot : (MU_NT3_ABL_WONCE ? 0 : (s & 1))) * WBYTES;
+                const char* Wb = Ws + (RING ? wslot : (s & 1)) * WBYTES;
                 const char* Hb = Hs + hbuf + dh * (HW_ * 128);
                 if constexpr (M_::PAIR) {
                     typename M_::Frag2 a[TM], b[TN];
@@ -804,9 +778,7 @@ __device__ __forceinline__ void conv_nt3_body(const T* __restrict__ x, const T* 
                     __builtin_amdgcn_sched_barrier(0);
                     wslot = wslot == 2 ? 0 : wslot + 1;
                 } else {
-#if !MU_NT3_ABL_WONCE
                     __syncthreads();
-#endif
                 }
             }
         }
@@ -816,9 +788,6 @@ __device__ __forceinline__ void conv_nt3_body(const T* __restrict__ x, const T* 
         __builtin_amdgcn_s_barrier();
     }
 
-#ifndef MU_NT3_EPI
-#define MU_NT3_EPI 1
-#endif
     mma_unshift<T>(acc);
     if constexpr (HL) {
         // two-term data gradient: fp32 rows, un-scaled (the dy scale and the weight shift are powers of two); a lane's four channels of
@@ -835,7 +804,7 @@ __device__ __forceinline__ void conv_nt3_body(const T* __restrict__ x, const T* 
         }
         return;
     }
-    if constexpr (sizeof(T) == 2 && TM == 4 && MU_NT3_EPI) {
+    if constexpr (sizeof(T) == 2 && TM == 4) {
         // wave-private staged epilogue (as conv_nt4_kernel): the wave's (TN x 16) px x 64 co tile goes through its own LDS slice
         // (every fragment read and DMA of the loop is behind its last barrier) and leaves as whole 128-byte rows
         char* Os = lds + wave * (TN * 16 * 128);
@@ -983,19 +952,6 @@ __global__ __launch_bounds__(256, 2) void conv_nt3f_kernel(const T* __restrict__
 // Versus v3 the weight tile is shared by 256 instead of 128 pixels (half the L2->LDS bytes per flop) and the DMA
 // lookahead grows from one tap (~0.25 us, less than an L2 hit under load) to three phases.
 // ------------------------------------------------------------------------------------------
-#ifndef MU_CONV_NT4
-#define MU_CONV_NT4 1
-#endif
-
-#ifndef MU_CONV_NT4P
-#define MU_CONV_NT4P 1
-#endif
-#ifndef MU_NT4_MINBLK
-#define MU_NT4_MINBLK 0         // (round 5 probe: grids below this many blocks fall back to the 8 x 16-pixel-tile kernel)
-#endif
-#ifndef MU_CONV_WIDE1X1
-#define MU_CONV_WIDE1X1 1
-#endif
 // (body shared by the training kernel, whose signature and code are exactly what they were without the inference epilogue, and the
 //  FEPI kernel below: three more kernel arguments on the hot kernel shifted its code enough to cost 0.1 ms per training step)
 // HL (round 6): the two-term data gradient of the fp32x 3x3 layers on this pipeline (see conv_nt_kernel / conv_nt3_body): x = the one-term
@@ -1058,7 +1014,7 @@ __device__ __forceinline__ void conv_nt4_body(const h16* __restrict__ x, const h
     auto stage_w = [&](int s) {                              // W(s) -> ring slot s & 3 (dummy beyond the last step)
         if (s < nsteps) {
             const int tap = s % 9, c_ = s / 9;
-            const int ci0 = HL2 ? ((c_ & 1) ? Cin : 0) + (c_ >> 1) * KC : (HL == 1 ? Cin : 0) + c_ * KC;
+            const int ci0 = HL2 ? ((c_ & 1) ? Cin : 0) + (c_ >> 1) * KC : c_ * KC;
             const h16* wb = w + (long)tap * Cout * Cw + ci0;
             char* Wb = Ws + (s & 3) * WBYTES;
 #pragma unroll
@@ -1072,11 +1028,7 @@ __device__ __forceinline__ void conv_nt4_body(const h16* __restrict__ x, const h
         const int off = hl[k];
         const int hc = HL2 ? (c >> 1) : c;                   // HL = 2: instances 2 hc and 2 hc + 1 share a halo, staged for the even one
         if (c < kchunks && (!HL2 || (c & 1) == 0) && k * NWV + wave < HINST) {       // wave-uniform
-#ifdef MU_NT4_ABL_NOHALO
-            const void* src = (const void*)mu_zero_page;
-#else
             const void* src = off >= 0 ? (const void*)(xb + off + hc * KC) : (const void*)mu_zero_page;
-#endif
             glds16(src, Hs + (hc & 1) * HBYTES + (k * NWV + wave) * 1024);
         } else {
             glds16(mu_zero_page, dump);
@@ -1103,13 +1055,6 @@ __device__ __forceinline__ void conv_nt4_body(const h16* __restrict__ x, const h
     stage_w(0);
     stage_w(1);
     stage_w(2);
-#ifdef MU_NT4_ABL_NODMA_REAL
-    // timing-only ablation (wrong results): every ring slot and both halo buffers hold REAL data from here on and the tap loop issues no
-    // DMA and waits for none -- the upper bound of what loader waves that own all DMA issue could give the consumer waves
-#pragma unroll
-    for (int k = 0; k < HPW; ++k) stage_h(k, 1);
-    stage_w(3);
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     if (wr == 1) __builtin_amdgcn_s_barrier();
@@ -1133,37 +1078,25 @@ __device__ __forceinline__ void conv_nt4_body(const h16* __restrict__ x, const h
                 for (int j = 0; j < TN; ++j) b[j] = M_::ld(hb + j * (HW_ * 128));
                 // exactly three DMAs per wave per tap: the halo piece in the first phase (tap 0: in the second -- the buffer it
                 // refills was read until the previous chunk's last phase), the two weight pieces in the second
-#ifndef MU_NT4_ABL_NODMA_REAL
                 if ((kk == 0) == (t != 0)) {
                     if (t < HPW) stage_h(t, c + 1); else glds16(mu_zero_page, dump);
                 }
                 if (kk == 1) stage_w(s + 3);
-#endif
-#ifndef MU_NT4_ABL_NOBAR1
                 __builtin_amdgcn_s_barrier();
-#endif
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
-#ifndef MU_NT4_ABL_NOPRIO
                 __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j) M_::mma(a[i], b[j], acc[i][j]);
-#ifndef MU_NT4_ABL_NOPRIO
                 __builtin_amdgcn_s_setprio(0);
-#endif
-#if !defined(MU_NT4_ABL_NOWAIT) && !defined(MU_NT4_ABL_NODMA_REAL)
                 if (kk == 0) {
                     if (t == 0) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");      // younger: H(8), W(s+2) x2
                     else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");             // younger: H(t-1), W(s+2) x2, H(t)
                 }
-#endif
                 __builtin_amdgcn_sched_barrier(0);
-#ifndef MU_NT4_ABL_NOBAR2
                 __builtin_amdgcn_s_barrier();
-#endif
             }
         }
     }
@@ -1228,9 +1161,6 @@ __device__ __forceinline__ void conv_nt4_body(const h16* __restrict__ x, const h
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = (h16)epi_act<h16>((float)o[e] + (float)rv[e], act);
         }
-#ifdef MU_NT4_ABL_NOSTORE
-        if (B < 0)
-#endif
         *reinterpret_cast<h16x8*>(y + gp * y_ld + co0 + wr * 64 + q * 8) = o;
         if (stat_part) tile_stats_accum(o, ssum, ssq);
     }
@@ -1265,9 +1195,6 @@ __global__ __launch_bounds__(512, 1) void conv_nt4f_kernel(const h16* __restrict
 // 64 px x 64 co tile staged in 16 KB of LDS, XOR-swizzled 16-byte slots, whole 256-byte rows per store) and, like the fp16 kernel, the
 // per-tile BatchNorm statistics of the values it stores.
 // ------------------------------------------------------------------------------------------
-#ifndef MU_CONV_NT4X
-#define MU_CONV_NT4X 1
-#endif
 template <typename XT>           // xf32 (bf16 pairs) or xh32 (fp16 pairs, round 6: what the 3x3 layers of the fp32x mode run on)
 __global__ __launch_bounds__(512, 1) void conv_nt4x_kernel(const XT* __restrict__ x, const XT* __restrict__ w, const float* __restrict__ bias,
                                                            XT* __restrict__ y, int B, int H, int W, int Cin, int Cout, long x_ld, long y_ld,
@@ -1665,9 +1592,6 @@ __global__ __launch_bounds__(512, 1) void conv_nt4p_kernel(const h16* __restrict
                 const int p = it * 8 + (lane >> 3);             // pixel inside the wave tile: image row wc*4 + (p >> 4), column p & 15
                 const h16x8 o = *reinterpret_cast<const h16x8*>(Os + p * 128 + ((q ^ ((p >> 1) & 7)) << 4));
                 const long gp = ((long)bimg * H + h0 + wc * TN + (p >> 4)) * W + w0 + (p & 15);
-#ifdef MU_NT4_ABL_NOSTORE
-                if (B < 0)
-#endif
                 *reinterpret_cast<h16x8*>(y + gp * y_ld + co0 + wr * 64 + q * 8) = o;
                 if (stat_part) tile_stats_accum(o, ssum, ssq);
             }
@@ -1691,12 +1615,6 @@ __global__ __launch_bounds__(512, 1) void conv_nt4p_kernel(const h16* __restrict
 // First form (all 8 waves in lockstep on one tile, double-buffered halo, staged epilogue): 120 -> 88 us at 128^2, B = 64; ablations:
 // without MFMAs 40 us, without stores 80, without halo DMAs 71 -- data movement and arithmetic were not overlapping.
 // ------------------------------------------------------------------------------------------
-#ifndef MU_CONV_NT5
-#define MU_CONV_NT5 1
-#endif
-#ifndef MU_NT5_MINTILES
-#define MU_NT5_MINTILES 512          // two tiles per block at least: below, one of the two wave groups would idle
-#endif
 // Cout_total = 128 (grid.y = 2; launches without a statistics epilogue, i.e. the data-gradient of a 128 -> 64 layer): blockIdx.y picks a
 // 64-channel half of the output -- two independent 64 -> 64 problems on the same input, each with its half of the weights resident.
 __global__ __launch_bounds__(512, 1) void conv_nt5_kernel(const h16* __restrict__ x, const h16* __restrict__ w, const float* __restrict__ bias,
@@ -1860,12 +1778,6 @@ __global__ __launch_bounds__(512, 1) void conv_nt5_kernel(const h16* __restrict_
         __builtin_amdgcn_sched_barrier(0);
     }
 }
-#ifndef MU_NT5_SPLIT128
-#define MU_NT5_SPLIT128 1
-#endif
-#ifndef MU_NT5_SPLIT_MINTILES
-#define MU_NT5_SPLIT_MINTILES 1024
-#endif
 
 // The 3x3 forward plan: which halo-tile kernel of conv_fwd_launch<T, 9> serves the shape (K3_NONE: the shape is not on the halo-tile
 // path), and how many rows of per-tile BatchNorm statistics its epilogue writes when it is handed stat_part (0: no statistics epilogue).
@@ -1881,25 +1793,26 @@ static Conv3x3Plan conv3x3_pick(int B, int H, int W, int Cin, int Cout, int dtyp
     const long t16 = (long)B * (H / 16) * (W / 16);          // 16 x 16 tiles: the ping-pong kernels write one row per tile and wave group
     const int rows16 = (int)(t16 * 4);
     if (dtype == MU_F16) {
-        const bool nt5 = MU_CONV_NT5 && Cin == 64 && H % 16 == 0 && t16 >= MU_NT5_MINTILES;
+        // (two tiles per block at least: below 512 tiles, one of the two wave groups would idle)
+        const bool nt5 = Cin == 64 && H % 16 == 0 && t16 >= 512;
         if (nt5 && Cout == 64) return {K3_NT5, rows16};
         // 64 -> 128 without a statistics epilogue (the data-gradient of the 128 -> 64 layers) as two resident 64 -> 64 halves
-        if (nt5 && MU_NT5_SPLIT128 && !with_stats && Cout == 128 && t16 >= MU_NT5_SPLIT_MINTILES) return {K3_NT5_HALVES, 0};
-        if (MU_CONV_NT4 && Cout % 128 == 0 && H % 16 == 0 && Cin % 64 == 0 && t16 * (Cout / 128) >= MU_NT4_MINBLK) {
+        if (nt5 && !with_stats && Cout == 128 && t16 >= 1024) return {K3_NT5_HALVES, 0};
+        if (Cout % 128 == 0 && H % 16 == 0 && Cin % 64 == 0) {
             // measured (in-process A/B): 128->128 @128^2 322 -> 307 us, 64->128 @128^2 205 -> 176 us, 256->256 @64^2 equal,
             // 512->512 @32^2 and two-tile blocks 1-3 % slower -> persistent only for >= 4 tiles per block and short K loops
-            if (MU_CONV_NT4P && t16 * (Cout / 128) >= 1024 && Cin <= 256 && 256 % (Cout / 128) == 0) return {K3_NT4P, rows16};
+            if (t16 * (Cout / 128) >= 1024 && Cin <= 256 && 256 % (Cout / 128) == 0) return {K3_NT4P, rows16};
             return {K3_NT4, rows16};
         }
     }
     // fp32x: one 512-thread block per CU: a grid of fewer than ~200 blocks (16^2 256 -> 256 at B = 64: 128) leaves half of the chip
     // idle, where the generic kernel's 8 x 16 pixel tiles still fill it (61 vs 72 us in-process)
-    if (dtype == MU_F32X && MU_CONV_NT4X && Cout % 128 == 0 && H % 16 == 0 && t16 * (Cout / 128) >= 192) return {K3_NT4X, rows16};
+    if (dtype == MU_F32X && Cout % 128 == 0 && H % 16 == 0 && t16 * (Cout / 128) >= 192) return {K3_NT4X, rows16};
     if (H % 8) return {K3_NONE, 0};
     const int t8 = B * (H / 8) * (W / 16);                  // 8 x 16 tiles: one row per tile and wave row
-    if (Cout % 128 == 0) return {K3_NT3_128, MU_NT3_STATS ? t8 * 2 : 0};
+    if (Cout % 128 == 0) return {K3_NT3_128, t8 * 2};
     // the three-slot weight ring pays for its longer prologue from two 64-channel chunks on (see conv_nt3_body)
-    if (Cout % 64 == 0) return {Cin * es >= 256 ? K3_NT3_64_RING : K3_NT3_64, MU_NT3_STATS ? t8 * 4 : 0};
+    if (Cout % 64 == 0) return {Cin * es >= 256 ? K3_NT3_64_RING : K3_NT3_64, t8 * 4};
     return {K3_NONE, 0};
 }
 
@@ -1921,11 +1834,11 @@ static int conv_fwd_pick(int B, int H, int W, int Cin, int Cout, int taps, int d
         const Conv3x3Kernel k3 = conv3x3_pick(B, H, W, Cin, Cout, dtype, with_stats).kernel;
         if (k3 != K3_NONE) return k3;
     }
-    if (taps == 1 && dtype == MU_F16 && MU_CONV_WIDE1X1) {
-        if ((Cin * 2) % 128 == 0 && Cout % 192 == 0) return Cin == 64 && MU_NT2_SB ? KF_WIDE192_SB : KF_WIDE192;
-        if ((Cin * 2) % 128 == 0 && Cout == 160) return Cin == 64 && MU_NT2_SB ? KF_HEAD160_SB : KF_HEAD160;
+    if (taps == 1 && dtype == MU_F16) {
+        if ((Cin * 2) % 128 == 0 && Cout % 192 == 0) return Cin == 64 ? KF_WIDE192_SB : KF_WIDE192;
+        if ((Cin * 2) % 128 == 0 && Cout == 160) return Cin == 64 ? KF_HEAD160_SB : KF_HEAD160;
     }
-    if (taps == 1 && dtype == MU_F32X && MU_CONV_WIDE1X1) {
+    if (taps == 1 && dtype == MU_F32X) {
         if ((Cin * 4) % 128 == 0 && Cout == 160) return KF_HEAD160;
     }
     if ((Cin * es) % 128 == 0 && Cout % 64 == 0) return Cout % 128 == 0 ? KF_DMA128 : KF_DMA64;
@@ -1938,7 +1851,7 @@ static ConvFusedKernel conv_fused_pick(int B, int H, int W, int Cin, int Cout, i
     (void)B;
     const int es = dtype == MU_F16 ? 2 : 4;
     if (taps == 9 && (Cin * es) % 128 == 0 && W % 16 == 0) {
-        if (dtype == MU_F16 && MU_CONV_NT4 && Cout % 128 == 0 && H % 16 == 0 && Cin % 64 == 0) return FF_NT4F;
+        if (dtype == MU_F16 && Cout % 128 == 0 && H % 16 == 0 && Cin % 64 == 0) return FF_NT4F;
         if (Cout % 128 == 0 && H % 8 == 0) return FF_NT3F_128;
         if (Cout % 64 == 0 && H % 8 == 0) return FF_NT3F_64;
     }
@@ -2148,18 +2061,13 @@ extern "C" int mu_conv_fwd(const void* x, const void* w, const float* bias, void
 // of the weights (the HL data-gradient block of mu_prep_weight / mu_prep_weights_multi with MU_F32X: [9][Cout][2 * Cin] halves): two fp16
 // MFMAs per product instead of the forward's three.  dx: plain fp32 rows (row stride dx_ld floats), multiplied by dy_scale[1] = 1 / S and by
 // 2^-MU_XH_WSHIFT in the epilogue (exact: powers of two).  Cin = channels of dy (the layer's output), Cout = channels of dx (its input).
-// Weight terms (MU_DGRAD_H_TERMS, compile time): 2 = lo + hi halves; 1 = the hi halves only, one MFMA per product: step -1.5 ms same-box,
-// but the small-module goldens' parameter gradients land at 1.06e-3 .. 1.17e-3 against their 1e-3 gate -- 9 * Cout = 72 .. 288 terms
-// average too little --, so the default keeps both halves.
-#ifndef MU_DGRAD_H_TERMS
-#define MU_DGRAD_H_TERMS 2
-#endif
-static_assert(MU_DGRAD_H_TERMS == 1 || MU_DGRAD_H_TERMS == 2, "MU_DGRAD_H_TERMS: 1 or 2 weight terms");
+// Weight terms: both halves (HL = 2).  With the hi halves only -- one MFMA per product -- the step was 1.5 ms shorter same-box, but the
+// small-module goldens' parameter gradients landed at 1.06e-3 .. 1.17e-3 against their 1e-3 gate: 9 * Cout = 72 .. 288 terms average too little.
 enum ConvDgradHKernel { DH_NONE, DH_NT4HL, DH_NT3HL_128, DH_NT3HL_64, DH_GEN128, DH_GEN64, DH_GEN32, DH_COUNT };
 static ConvDgradHKernel conv_dgrad_h_pick(int B, int H, int W, int Cin, int Cout) {
     (void)B;
     if (Cin % 64 == 0 && W % 16 == 0 && H % 8 == 0 && Cout % 64 == 0) {
-        if (Cout % 128 == 0 && H % 16 == 0 && MU_CONV_NT4) return DH_NT4HL;
+        if (Cout % 128 == 0 && H % 16 == 0) return DH_NT4HL;
         return Cout % 128 == 0 ? DH_NT3HL_128 : DH_NT3HL_64;
     }
     return Cout % 128 == 0 ? DH_GEN128 : Cout % 64 == 0 ? DH_GEN64 : DH_GEN32;
@@ -2179,7 +2087,7 @@ extern "C" int mu_conv_dgrad_h(const void* dy_h, const void* w_hl, const float* 
     float* y = (float*)dx;
     const long M = (long)B * H * W;
     const int npb = (int)((M + 127) / 128);
-    constexpr int HL = MU_DGRAD_H_TERMS;
+    constexpr int HL = 2;
     switch (conv_dgrad_h_pick(B, H, W, Cin, Cout)) {
     case DH_NT4HL:
         conv_nt4hl_kernel<HL><<<B * (H / 16) * (W / 16) * (Cout / 128), 512, 0, st>>>(x, w, y, B, H, W, Cin, Cout, dy_ld, dx_ld, dy_scale);
@@ -2265,9 +2173,6 @@ template <> struct WgTile<h16> { static constexpr int PAD = 0; static constexpr 
 // fp32: row pad (elements) puts the g=0/1 pixel rows of a ds_read_b32 on different banks
 template <> struct WgTile<float> { static constexpr int PAD = 16; static constexpr int KP = 16; };
 template <> struct WgTile<xf32> { static constexpr int PAD = 16; static constexpr int KP = 32; };     // K = 32 per stage: v_mfma_f32_16x16x32_bf16 triples (1x1 layers)
-#ifndef MU_WG_XSWAP
-#define MU_WG_XSWAP 1
-#endif
 
 typedef __fp16 fp16x4v __attribute__((__vector_size__(4 * sizeof(__fp16))));
 
@@ -2327,11 +2232,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const T* __restrict__ x
             else rb[i] = make_uint4(0, 0, 0, 0);
         }
     };
-    // fp32x (MU_WG_XSWAP): the transposed reads below fetch ONLY the hi (or only the lo) halves of the 16-byte chunks, i.e. banks
+    // fp32x: the transposed reads below fetch ONLY the hi (or only the lo) halves of the 16-byte chunks, i.e. banks
     // = 0,1 (mod 4) -- a 32-lane group (pixel rows 8g + q, g in {0,1}) can then reach 32 of the 64 banks: 2-way conflicts whatever the
     // row padding.  Rows with bit 3 set are therefore stored with their halves swapped ([lo | hi]): the two row quartets of a lane group
     // use complementary banks.  Two 8-byte stores per chunk (as fast as one 16-byte store, MI355X_MICROARCH LDS table).
-    constexpr bool XSWAP = std::is_same<T, xf32>::value && MU_WG_XSWAP;
+    constexpr bool XSWAP = std::is_same<T, xf32>::value;
     auto put = [&](T* dst, int row, const uint4& v) {
         if constexpr (XSWAP) {
             const int sw = ((row >> 3) & 1) * 8;
@@ -2529,32 +2434,14 @@ template <int N> __device__ __forceinline__ void wait_vmcnt_c() {
 // The pixel stream comes straight from HBM (every block sweeps its own pixel range once), so the stage ring is NS deep with
 // NS-1 stages in flight: counted s_waitcnt vmcnt + ONE raw s_barrier per 32-pixel stage (the former double buffer prefetched
 // a single stage, ~0.2 us of MFMA work, far less than an HBM round trip).
-#ifndef MU_WG_NS
-#define MU_WG_NS 6
-#endif
-#ifndef MU_WG_SPS2
-#define MU_WG_SPS2 1
-#endif
-#ifndef MU_WG_SPS2_64
-#define MU_WG_SPS2_64 1
-#endif
 // ping-pong schedule of the weight-grad kernel (W % 64 == 0 layers, 128 x 128 tiles).  With the whole stage's DMAs in the first
 // k-step's load section it was neutral to slower (that section ran 1.6x as long as the 24-MFMA section it hides behind); with the dy
 // pieces in the first and the x pieces in the second load section: 128->128 @128^2 0.330 -> 0.307 ms, 256->256 @64^2 0.297 -> 0.277 ms.
 // (Timing builds with real data: no DMA in the loop -23 %, the same DMA instructions on L1-resident data -4 % -- it is the
 // ISSUE of the LDS-DMA instructions, not the bytes, that the lockstep schedule exposed.)
-#ifndef MU_WG_PP
-#define MU_WG_PP 1
-#endif
 // Lockstep schedule (non-ping-pong 8-wave kernels: W = 32 and W = 16 layers): the two waves of a SIMD issue their LDS-DMAs at different
 // points of the stage -- waves 0-3 in front of the first k-step's MFMAs, waves 4-7 one k-step later (W = 16, one k-step per stage: behind
 // their MFMAs) -- so that one wave's DMA issue overlaps the other's matrix section: 512->512 @32^2 0.307 -> 0.295 ms, @16^2 0.107 -> 0.105.
-#ifndef MU_WG_STAGGER
-#define MU_WG_STAGGER 2
-#endif
-#ifndef MU_WG_SPLIT_DMA
-#define MU_WG_SPLIT_DMA 1
-#endif
 // SPS = 32-pixel k-steps per DMA stage.  SPS = 2 (W % 64 == 0): one barrier / DMA batch / ring step per 64 pixels -- the two
 // waves of a SIMD run in lockstep behind the per-stage barrier, so the ~500 cycles of scalar + address work per ring step sit
 // in front of both waves' MFMA bursts (PMC: SQ_ACTIVE_INST_SCA 18 % of wave cycles, MFMA pipe 44 % busy at SPS = 1).
@@ -2584,7 +2471,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv_wgrad3_kernel(const T* __res
     constexpr int STAGE = SP * BCO + PADA + XR * BCI + PADB;   // elements per stage
 
     static_assert(!PP || (SPS == 2 && NWV == 8 && WR == 2), "ping-pong needs two 4-wave groups and two k-steps per stage");
-    constexpr int NS = SPS == 1 ? MU_WG_NS : 4;
+    constexpr int NS = SPS == 1 ? 6 : 4;
     __shared__ __attribute__((aligned(16))) T lds[NS * STAGE];
 
     const long Mtot = (long)B * H * W;
@@ -2593,9 +2480,6 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv_wgrad3_kernel(const T* __res
     // logical ids inside one XCD, so they run side by side on that XCD and all but the first find the x / dy rows in its
     // L2: without this every block streams its operands from HBM (3.4-3.8 TB/s measured on every layer shape = the bound).
     int bid = xcd_remap(blockIdx.x, gridDim.x);
-#ifdef MU_WG_NO_XCD
-    bid = blockIdx.x;
-#endif
     const int cib = bid % nci; bid /= nci;
     const int cob = bid % nco; bid /= nco;
     const int dh = bid % 3 - 1; bid /= 3;                   // kernel row: taps 3*(dh+1) + {0,1,2}
@@ -2808,23 +2692,17 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv_wgrad3_kernel(const T* __res
         if (HALF == 0) {
             wait_ring();
             __builtin_amdgcn_s_barrier();
-#if MU_WG_STAGGER
-            // half the waves (one of each SIMD's two) issue their whole share now, the other half one k-step later
-            if (SPS == 2 && NWV == 8) { if (wr == 0) stage(buf == 0 ? NS - 1 : buf - 1); }
-            else if (SPS == 1 && NWV == 8 && MU_WG_STAGGER == 2) { if (wr == 0) stage(buf == 0 ? NS - 1 : buf - 1); }
-            else
-#endif
-            if (SPS == 2 && MU_WG_SPLIT_DMA) stage_a(buf == 0 ? NS - 1 : buf - 1);
+            // 8 waves: half of them (one of each SIMD's two) issue their whole share now, the other half one k-step later
+            if (NWV == 8) { if (wr == 0) stage(buf == 0 ? NS - 1 : buf - 1); }
+            else if (SPS == 2) stage_a(buf == 0 ? NS - 1 : buf - 1);
             else stage(buf == 0 ? NS - 1 : buf - 1);
-        } else if (SPS == 2 && MU_WG_STAGGER && NWV == 8) {
+        } else if (NWV == 8) {
             if (wr == 1) stage(buf == 0 ? NS - 1 : buf - 1);
-        } else if (SPS == 2 && MU_WG_SPLIT_DMA) {
+        } else if (SPS == 2) {
             stage_b(buf == 0 ? NS - 1 : buf - 1);
         }
         compute(cur);
-#if MU_WG_STAGGER == 2
         if (SPS == 1 && NWV == 8 && wr == 1) stage(buf == 0 ? NS - 1 : buf - 1);      // one-k-step stages: the second group issues behind its MFMAs
-#endif
         if (s + 1 < nsteps) {
             if (HALF + 1 < SPS) {
                 load_frags(buf, HALF + 1, nxt);
@@ -2947,12 +2825,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_pair_kernel(const float* __r
     }
 }
 
-#ifndef MU_WG1_WIDE
-#define MU_WG1_WIDE 1           // fp16 1x1 layers: tiles that span all (or 192) output channels, both operands read once
-#endif
-#ifndef MU_WG1_SPLITS
-#define MU_WG1_SPLITS 512       // pixel ranges per wide tile: these launches are HBM streams and want ~2 blocks per CU in flight
-#endif
 static inline bool wgrad_is_wide(int bco) { return bco == 192 || bco == 160; }
 
 static inline void wgrad_plan(long M, int Cin, int Cout, int taps, int bco, int bci, int* nsplit, long* pps) {
@@ -2961,7 +2833,8 @@ static inline void wgrad_plan(long M, int Cin, int Cout, int taps, int bco, int 
     if (want < 1) want = 1;
     long max_split = (M + 255) / 256;           // at least 256 pixels per split
     if (want > max_split) want = max_split;
-    const long cap = wgrad_is_wide(bco) ? MU_WG1_SPLITS / tiles > 64 ? MU_WG1_SPLITS / tiles : 64 : 256;
+    // wide tiles: 512 pixel ranges per tile -- these launches are HBM streams and want ~2 blocks per CU in flight
+    const long cap = wgrad_is_wide(bco) ? 512 / tiles > 64 ? 512 / tiles : 64 : 256;
     if (want > cap) want = cap;
     long p = (M + want - 1) / want;
     p = (p + 31) / 32 * 32;                    // multiple of both stage depths (32 / 16)
@@ -2972,8 +2845,8 @@ static inline void wgrad_plan(long M, int Cin, int Cout, int taps, int bco, int 
 static inline void wgrad_tile(int Cin, int Cout, int* bco, int* bci, int taps = 9, bool fp16 = false) {
     *bco = (Cout % 128 == 0) ? 128 : (Cout % 64 == 0 ? 64 : 32);
     *bci = (Cin % 128 == 0) ? 128 : (Cin % 64 == 0 ? 64 : 32);
-    if (MU_WG1_WIDE && fp16 && taps == 1 && *bci >= 64 && (Cout % 192 == 0 || Cout == 160)) {
-        // q/k/v projection (Cout = 3C) and the 150 -> 160 class head: with square tiles the narrow operand was re-read per
+    if (fp16 && taps == 1 && *bci >= 64 && (Cout % 192 == 0 || Cout == 160)) {
+        // fp16 1x1 layers: tiles that span all (or 192) output channels, both operands read once.  q/k/v projection (Cout = 3C) and the 150 -> 160 class head: with square tiles the narrow operand was re-read per
         // output-channel tile (64 -> 192: 804 MB instead of 537; 64 -> 160 with 32x32 tiles: 1.34 GB instead of 470 MB)
         *bco = Cout == 160 ? 160 : 192;
         return;
@@ -2984,33 +2857,23 @@ static inline void wgrad_tile(int Cin, int Cout, int* bco, int* bci, int taps = 
 }
 
 // v2 (3 taps per block) applies to fp16 3x3 layers with W % 32 == 0 (or W == 16) and 64/128-wide channel tiles.
-// Tile choice: 128x128 (8 waves) or 64x64 (4 waves).  The kernel also runs 128x64 / 64x128 tiles (MU_WG_MIXED=1: layers with one
-// 64-channel side, dy or x tile twice as wide), parity-clean but measured SLOWER in-process (64->128 @128^2: 333 vs 252 us,
-// 128->64: 356 vs 250 us): at 4 waves they need ~256 VGPRs and only the 32-pixel stages fit twice into the LDS.
-#ifndef MU_WG_MIXED
-#define MU_WG_MIXED 0
-#endif
+// Tile choice: 128x128 (8 waves) or 64x64 (4 waves).  128x64 / 64x128 tiles for the layers with one 64-channel side (dy or x tile twice
+// as wide) were parity-clean but measured SLOWER in-process (64->128 @128^2: 333 vs 252 us, 128->64: 356 vs 250 us): at 4 waves they
+// need ~256 VGPRs and only the 32-pixel stages fit twice into the LDS.  Those layers take the 64x64 tiles.
 // Blocks per launch = exactly what is resident at once (8-wave tiles: one per CU; 4-wave tiles: two per CU): every block does the
 // same work, so one whole round has no tail, and the fp32 slab traffic (write + reduce: 2.4 GB/step at 512 / 1536 blocks, the reduce
 // kernel at HBM rate) shrinks with the split count.  In-process A/B: 128->128 @128^2 341 -> 324 us, 512->512 @16^2 123 -> 105 us,
 // 64->64 @128^2 147 -> 125 us; 768 blocks (1.5 rounds) for the 4-wave tiles is 10 % WORSE than 512.
-#ifndef MU_WG_BLOCKS128
-#define MU_WG_BLOCKS128 256
-#endif
-#ifndef MU_WG_BLOCKS64
-#define MU_WG_BLOCKS64 512
-#endif
 static inline bool wgrad3_choose(int H, int W, int Cin, int Cout, int taps, int dtype, int* tco, int* tci) {
     if (dtype != MU_F16 || taps != 9 || !(W % 32 == 0 || (W == 16 && H % 2 == 0))) return false;
     const int a = Cout % 128 == 0 ? 128 : (Cout % 64 == 0 ? 64 : 0), b = Cin % 128 == 0 ? 128 : (Cin % 64 == 0 ? 64 : 0);
     if (!a || !b) return false;
-    if (a == b || MU_WG_MIXED) { *tco = a; *tci = b; }
-    else { *tco = 64; *tci = 64; }
+    *tco = *tci = a == b ? a : 64;
     return true;
 }
 static inline void wgrad3_plan(long M, int Cin, int Cout, int tco, int tci, int* nsplit, long* pps) {
     long tiles = 3L * (Cout / tco) * (Cin / tci);
-    long want = ((tco == 128 && tci == 128) ? MU_WG_BLOCKS128 : MU_WG_BLOCKS64) / tiles;
+    long want = (tco == 128 ? 256 : 512) / tiles;
     if (want < 1) want = 1;
     long max_split = (M + 511) / 512;
     if (want > max_split) want = max_split;
@@ -3029,9 +2892,6 @@ static inline void wgrad3_plan(long M, int Cin, int Cout, int tco, int tci, int*
 // Partial slab layout [block][tap][Cout][4] feeds the same deterministic reduce as the other kernels.
 // ------------------------------------------------------------------------------------------
 #define MU_RGB_MAXW 256
-#ifndef MU_RGB2
-#define MU_RGB2 1              // fp16, W % 32 == 0: the matrix-core form below (0 = the plain-FMA kernel everywhere)
-#endif
 // Round 3: the sweep was latency-bound (157 us against ~40 us of HBM time for the 200 MB of dy / x): every 4-pixel step loaded its dy
 // values and then ran 108 dependent FMAs, with two block barriers per image row around a scalar-load staging of the three input
 // rows.  Now a lane fetches the dy values of a whole 128-pixel chunk (8 steps) one chunk AHEAD of the FMAs that consume them, the
@@ -3330,28 +3190,8 @@ __global__ __launch_bounds__(256, 3) void wgrad_rgb2_kernel(const h16* __restric
 // reads and 36 MFMAs per 32 pixels, 144 accumulators, no cross-wave fold; 145 KB of LDS at W = 128.  dy and x are read from HBM once per channel tile.
 // Slab layout [band][tap][Cout][Cin] = the ring kernel's, same deterministic reduce.
 // ------------------------------------------------------------------------------------------
-#ifndef MU_WG9
-#define MU_WG9 1
-#endif
-#ifndef MU_WG9_S
 #define MU_WG9_S 80            // halves per staged pixel row: 64 channels + 16 pad = 160 bytes = 32 x 5 -- the 8 pixel rows a 32-lane half of a transposing
-#endif                         // read touches (4 pieces of 8 bytes each) then start on 8 distinct multiples of 32 bytes modulo the 256-byte bank row
-
-#ifndef MU_WG9_BLOCKS
-#define MU_WG9_BLOCKS 256
-#endif
-#ifndef MU_WG9_BLOCKS_W64
-#define MU_WG9_BLOCKS_W64 256  // (W <= 64: 66 KB of LDS, two blocks fit a CU)
-#endif
-#ifndef MU_WG9_MAXC
-#define MU_WG9_MAXC 128
-#endif
-#ifndef MU_WG9_MAXC32
-#define MU_WG9_MAXC32 128
-#endif
-#ifndef MU_WG9_NEED64
-#define MU_WG9_NEED64 1
-#endif
+                               // read touches (4 pieces of 8 bytes each) then start on 8 distinct multiples of 32 bytes modulo the 256-byte bank row
 template <int NPT>             // NPT = W / 32
 __global__ __launch_bounds__(256, 1) void conv_wgrad9_kernel(const h16* __restrict__ x, const h16* __restrict__ dy, float* __restrict__ part,
                                                           int B, int H, int W, int Cin, int Cout, long x_ld, long dy_ld, int rows_per_blk) {
@@ -3533,19 +3373,13 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad9_w16_kernel(const h16* __re
             for (int i = 0; i < 4; ++i)
                 slab[((long)t * Cout + co0 + 16 * a + 4 * g + i) * Cin + ci0 + 16 * wave + r16] = acc[a][t][i];
 }
-#ifndef MU_WG9_W16
-#define MU_WG9_W16 1
-#endif
-#ifndef MU_WG9_MAXC16
-#define MU_WG9_MAXC16 512
-#endif
 // `pair` (mu_conv_wgrad_h, round 6): Cin counts the 16-bit COLUMNS of a chunk-encoded fp32x input -- two per channel -- and the layer-size
 // limits below, which were measured on real channel counts, apply to Cin / 2
 static inline int wg9_pair_div(bool pair) { return pair ? 2 : 1; }
 static inline bool wgrad9_w16_choose(int B, int H, int W, int Cin, int Cout, int taps, int dtype, int* nb, int* rpb, bool pair = false) {
-    if (!MU_WG9_W16 || dtype != MU_F16 || taps != 9 || W != 16 || H % 2 || Cin % 64 || Cout % 64 || Cin / wg9_pair_div(pair) > MU_WG9_MAXC16 || Cout > MU_WG9_MAXC16) return false;
+    if (dtype != MU_F16 || taps != 9 || W != 16 || H % 2 || Cin % 64 || Cout % 64 || Cin / wg9_pair_div(pair) > 512 || Cout > 512) return false;
     const long rows = (long)B * H;
-    long want = MU_WG9_BLOCKS / ((Cin / 64) * (Cout / 64));
+    long want = 256 / ((Cin / 64) * (Cout / 64));
     if (want < 1) want = 1;
     long r = (rows + want - 1) / want;
     r = (r + 1) / 2 * 2;                                       // whole row pairs
@@ -3555,15 +3389,14 @@ static inline bool wgrad9_w16_choose(int B, int H, int W, int Cin, int Cout, int
 }
 
 static inline bool wgrad9_choose(int B, int H, int W, int Cin, int Cout, int taps, int dtype, int* nb, int* rpb, bool pair = false) {
-    // which layers: one of the two channel counts 64 (the ring kernel's 64-wide tiles), or both <= MU_WG9_MAXC32 at W = 32 -- in-process A/B, B = 64:
+    // which layers: one of the two channel counts 64 (the ring kernel's 64-wide tiles), or both <= 128 at W = 32 -- in-process A/B, B = 64:
     // 32^2 128->128 40.9 -> 36.1 us; the 128-wide layers at 64^2 / 128^2 are 5-7 % SLOWER here than on the ring kernel's 128 x 128 tiles
-    const int maxc = W <= 32 ? MU_WG9_MAXC32 : MU_WG9_MAXC;
-    const bool need64 = MU_WG9_NEED64 && W > 32;
+    const bool need64 = W > 32;
     const int creal = Cin / wg9_pair_div(pair);
-    if (!MU_WG9 || dtype != MU_F16 || taps != 9 || W % 32 || W > 128 || Cin % 64 || Cout % 64 || (need64 && !(creal == 64 || Cout == 64)) ||
-        creal > maxc || Cout > maxc) return false;
+    if (dtype != MU_F16 || taps != 9 || W % 32 || W > 128 || Cin % 64 || Cout % 64 || (need64 && !(creal == 64 || Cout == 64)) ||
+        creal > 128 || Cout > 128) return false;
     const long rows = (long)B * H;
-    long want = (W <= 64 ? MU_WG9_BLOCKS_W64 : MU_WG9_BLOCKS) / ((Cin / 64) * (Cout / 64));
+    long want = 256 / ((Cin / 64) * (Cout / 64));          // one block per CU (W <= 64: 66 KB of LDS, two would fit)
     if (want > rows) want = rows;
     if (want < 1) want = 1;
     *rpb = (int)((rows + want - 1) / want);
@@ -3646,7 +3479,6 @@ enum ConvWgradKernel {
     WG_WG9_NPT1, WG_WG9_NPT2, WG_WG9_NPT3, WG_WG9_NPT4,
     WG_WG9_W16,
     WG_WG3_128_W16, WG_WG3_128_ROWS2, WG_WG3_128_FLAT64, WG_WG3_128,
-    WG_WG3_128X64_W16, WG_WG3_128X64, WG_WG3_64X128_W16, WG_WG3_64X128,        // (MU_WG_MIXED builds only)
     WG_WG3_64_W16, WG_WG3_64_ROWS2, WG_WG3_64_FLAT64, WG_WG3_64,
     WG_WIDE192_CI64, WG_WIDE192_CI128, WG_WIDE160_CI64, WG_WIDE160_CI128,
     WG_WIDE192_CI64_BIAS, WG_WIDE192_CI128_BIAS, WG_WIDE160_CI64_BIAS, WG_WIDE160_CI128_BIAS,
@@ -3669,7 +3501,7 @@ static ConvWgradPlan conv_wgrad_pick(int B, int H, int W, int Cin, int Cout, int
     wgrad_tile(Cin, Cout, &p.bco, &p.bci, taps, dtype == MU_F16 || (dtype == MU_F32X && Cout == 160));
     wgrad_plan((long)B * H * W, Cin, Cout, taps, p.bco, p.bci, &p.nsplit, &p.pps);
     if (taps == 9 && cin_valid <= 3 && Cout % 64 == 0 && W <= MU_RGB_MAXW && (dtype == MU_F16 || dtype == MU_F32 || dtype == MU_F32X)) {
-        if (dtype == MU_F16 && MU_RGB2 && W % 32 == 0) p.id = WG_RGB2_NPT1 + (W / 32 > 8 ? 8 : W / 32) - 1;
+        if (dtype == MU_F16 && W % 32 == 0) p.id = WG_RGB2_NPT1 + (W / 32 > 8 ? 8 : W / 32) - 1;
         else p.id = WG_RGB_FMA;
         return p;
     }
@@ -3686,11 +3518,9 @@ static ConvWgradPlan conv_wgrad_pick(int B, int H, int W, int Cin, int Cout, int
     if (wgrad3_choose(H, W, Cin, Cout, taps, dtype, &p.tco, &p.tci)) {
         wgrad3_plan((long)B * H * W, Cin, Cout, p.tco, p.tci, &p.nsplit, &p.pps);
         const bool two_row32 = W == 32 && H % 2 == 0, flat64 = W % 64 == 0;
-        if (p.tco == 128 && p.tci == 128)
-            p.id = W == 16 ? WG_WG3_128_W16 : two_row32 && MU_WG_SPS2 ? WG_WG3_128_ROWS2 : flat64 && MU_WG_SPS2 ? WG_WG3_128_FLAT64 : WG_WG3_128;
-        else if (p.tco == 128) p.id = W == 16 ? WG_WG3_128X64_W16 : WG_WG3_128X64;
-        else if (p.tci == 128) p.id = W == 16 ? WG_WG3_64X128_W16 : WG_WG3_64X128;
-        else p.id = W == 16 ? WG_WG3_64_W16 : two_row32 && MU_WG_SPS2_64 ? WG_WG3_64_ROWS2 : flat64 && MU_WG_SPS2_64 ? WG_WG3_64_FLAT64 : WG_WG3_64;
+        if (p.tco == 128)
+            p.id = W == 16 ? WG_WG3_128_W16 : two_row32 ? WG_WG3_128_ROWS2 : flat64 ? WG_WG3_128_FLAT64 : WG_WG3_128;
+        else p.id = W == 16 ? WG_WG3_64_W16 : two_row32 ? WG_WG3_64_ROWS2 : flat64 ? WG_WG3_64_FLAT64 : WG_WG3_64;
         return p;
     }
     if (dtype != MU_F16 && dtype != MU_F32 && dtype != MU_F32X) return p;
@@ -3773,29 +3603,16 @@ static int conv_wgrad_impl(const void* x, const void* dy, float* dw_oihw, float*
         conv_wgrad9_w16_kernel<<<dim3(nb9, Cout / 64, Cin / 64), 256, 0, st>>>(xh, dyh, part, B, H, Cin, Cout, x_ld, dy_ld, rpb9);
         break;
     case WG_WG3_128_W16: case WG_WG3_128_ROWS2: case WG_WG3_128_FLAT64: case WG_WG3_128:
-    case WG_WG3_128X64_W16: case WG_WG3_128X64: case WG_WG3_64X128_W16: case WG_WG3_64X128:
     case WG_WG3_64_W16: case WG_WG3_64_ROWS2: case WG_WG3_64_FLAT64: case WG_WG3_64: {
         if (ws_bytes < (long)nsplit * taps * Cout * Cin * (long)sizeof(float)) return MU_ERR_WORKSPACE;
         const int grid = 3 * (Cout / tco) * (Cin / tci) * nsplit;
-#define WG3(...) conv_wgrad3_kernel<h16, __VA_ARGS__><<<grid, (tco == 128 && tci == 128) ? 512 : 256, 0, st>>>(xh, dyh, part, B, H, W, Cin, Cout, x_ld, dy_ld, nsplit, pps)
+#define WG3(...) conv_wgrad3_kernel<h16, __VA_ARGS__><<<grid, tco == 128 ? 512 : 256, 0, st>>>(xh, dyh, part, B, H, W, Cin, Cout, x_ld, dy_ld, nsplit, pps)
         switch (plan.id) {
         // 128 x 128: 8 waves, 64x32 tile x 3 taps per wave (96 accumulators): 2 waves/SIMD
         case WG_WG3_128_W16: WG3(4, 2, 2, 8, true); break;
-        case WG_WG3_128_ROWS2:
-            if (MU_WG_PP == 2) WG3(4, 2, 2, 8, true, 2, true);      // (W = 32: +2.6 % slower, opt-in)
-            else WG3(4, 2, 2, 8, true, 2);
-            break;
-        case WG_WG3_128_FLAT64:
-            if (MU_WG_PP) WG3(4, 2, 2, 8, false, 2, true);
-            else WG3(4, 2, 2, 8, false, 2);
-            break;
+        case WG_WG3_128_ROWS2: WG3(4, 2, 2, 8, true, 2); break;             // (the ping-pong schedule at W = 32: +2.6 % slower)
+        case WG_WG3_128_FLAT64: WG3(4, 2, 2, 8, false, 2, true); break;
         case WG_WG3_128: WG3(4, 2, 2, 8); break;
-        // 128 x 64: 4 waves, 64x32 per wave
-        case WG_WG3_128X64_W16: WG3(4, 2, 2, 4, true); break;
-        case WG_WG3_128X64: WG3(4, 2, 2, 4); break;
-        // 64 x 128: 4 waves, 32x64 per wave
-        case WG_WG3_64X128_W16: WG3(2, 4, 2, 4, true); break;
-        case WG_WG3_64X128: WG3(2, 4, 2, 4); break;
         case WG_WG3_64_W16: WG3(2, 2, 2, 4, true); break;
         case WG_WG3_64_ROWS2: WG3(2, 2, 2, 4, true, 2); break;
         case WG_WG3_64_FLAT64: WG3(2, 2, 2, 4, false, 2); break;
@@ -3868,8 +3685,7 @@ extern "C" int mu_conv_wgrad_bias_plan(int B, int H, int W, int Cin, int Cout, i
 }
 
 // One table of plan names: op 0 = mu_conv_fwd_plan, 1 = mu_conv_fwd_fused_plan, 2 = mu_conv_dgrad_h_plan, 3 = mu_conv_wgrad_plan /
-// mu_conv_wgrad_bias_plan.  mu_conv_plan_count(op): ids run from 1 to count - 1; mu_conv_plan_name: NULL for an id outside that range and
-// for an id this build cannot reach (the mixed three-tap tiles without MU_WG_MIXED).
+// mu_conv_wgrad_bias_plan.  mu_conv_plan_count(op): ids run from 1 to count - 1; mu_conv_plan_name: NULL for an id outside that range.
 static const char* const conv_fwd_names[KF_COUNT] = {
     nullptr, "nt5", "nt5_halves", "nt4p", "nt4", "nt4x", "nt3_128", "nt3_64_ring", "nt3_64",
     "wide192_sb", "wide192", "head160_sb", "head160", "dma128", "dma64", "gen128", "gen64", "gen32"};
@@ -3880,7 +3696,6 @@ static const char* const conv_wgrad_names[WG_COUNT] = {
     nullptr, "rgb_fma", "rgb2_npt1", "rgb2_npt2", "rgb2_npt3", "rgb2_npt4", "rgb2_npt5", "rgb2_npt6", "rgb2_npt7", "rgb2_npt8",
     "wgrad9_npt1", "wgrad9_npt2", "wgrad9_npt3", "wgrad9_npt4", "wgrad9_w16",
     "wgrad3_128_w16", "wgrad3_128_rows2", "wgrad3_128_flat64", "wgrad3_128",
-    "wgrad3_128x64_w16", "wgrad3_128x64", "wgrad3_64x128_w16", "wgrad3_64x128",
     "wgrad3_64_w16", "wgrad3_64_rows2", "wgrad3_64_flat64", "wgrad3_64",
     "wide192_ci64", "wide192_ci128", "wide160_ci64", "wide160_ci128",
     "wide192_ci64_bias", "wide192_ci128_bias", "wide160_ci64_bias", "wide160_ci128_bias",
@@ -3890,7 +3705,6 @@ extern "C" int mu_conv_plan_count(int op) {
 }
 extern "C" const char* mu_conv_plan_name(int op, int id) {
     if (id <= 0 || id >= mu_conv_plan_count(op)) return nullptr;
-    if (op == 3 && !MU_WG_MIXED && id >= WG_WG3_128X64_W16 && id <= WG_WG3_64X128) return nullptr;
     return op == 0 ? conv_fwd_names[id] : op == 1 ? conv_fused_names[id] : op == 2 ? conv_dgrad_h_names[id] : conv_wgrad_names[id];
 }
 

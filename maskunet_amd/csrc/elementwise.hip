@@ -3,11 +3,7 @@
 // nn.MaxPool2d(2) (:216), nn.Upsample(bilinear, align_corners=True) + torch.cat (:235,250-253),
 // nn.Dropout(0.3) (:273,304,307), and the OIHW<->tap-major weight re-layouts of this build.
 #include "common.h"
-// Nontemporal loads for operands a kernel reads exactly once (`nt`: past the CU's L1, L2-served): see norm.hip MU_BN_NT.
-#ifndef MU_EW_NT
-#define MU_EW_NT 1
-#endif
-#define EW_LD(vec, ptr_) do { if (MU_EW_NT) (vec).load_nt(ptr_); else (vec).load(ptr_); } while (0)
+// Operands a kernel reads exactly once are loaded nontemporally (`load_nt`: past the CU's L1, L2-served): see the head of norm.hip.
 #include "../../include/maskunet_hip.h"
 
 // ------------------------------------------------------------------------------------------
@@ -467,7 +463,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const T* __restrict__ 
         int wo = p % Wo, ho = (p / Wo) % Ho, b = p / ((long)Wo * Ho);
         const T* base = x + (((long)b * H + 2 * ho) * W + 2 * wo) * C + c;
         Vec16<T> v00, v01, v10, v11, o;
-        EW_LD(v00, base); EW_LD(v01, base + C); EW_LD(v10, base + (long)W * C); EW_LD(v11, base + (long)W * C + C);
+        v00.load_nt(base); v01.load_nt(base + C); v10.load_nt(base + (long)W * C); v11.load_nt(base + (long)W * C + C);
 #pragma unroll
         for (int i = 0; i < N; ++i) o.set(i, fmaxf(fmaxf(v00.get(i), v01.get(i)), fmaxf(v10.get(i), v11.get(i))));
         o.store(y + p * C + c);
@@ -491,10 +487,10 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ 
         long off = (((long)b * H + 2 * ho) * W + 2 * wo) * C + c;
         const long offs[4] = {off, off + C, off + (long)W * C, off + (long)W * C + C};
         Vec16<T> v[4], g, g2, a[4], o[4];
-        EW_LD(v[0], x + offs[0]); EW_LD(v[1], x + offs[1]); EW_LD(v[2], x + offs[2]); EW_LD(v[3], x + offs[3]);
-        EW_LD(g, dy + p * C + c);
-        if (dy2) EW_LD(g2, dy2 + p * C + c);
-        if (dx_add) { EW_LD(a[0], dx_add + offs[0]); EW_LD(a[1], dx_add + offs[1]); EW_LD(a[2], dx_add + offs[2]); EW_LD(a[3], dx_add + offs[3]); }
+        v[0].load_nt(x + offs[0]); v[1].load_nt(x + offs[1]); v[2].load_nt(x + offs[2]); v[3].load_nt(x + offs[3]);
+        g.load_nt(dy + p * C + c);
+        if (dy2) g2.load_nt(dy2 + p * C + c);
+        if (dx_add) { a[0].load_nt(dx_add + offs[0]); a[1].load_nt(dx_add + offs[1]); a[2].load_nt(dx_add + offs[2]); a[3].load_nt(dx_add + offs[3]); }
 #pragma unroll
         for (int i = 0; i < N; ++i) {
             int best = 0;
@@ -706,9 +702,6 @@ __global__ __launch_bounds__(256) void upcat_bwd_kernel(const T* __restrict__ dy
 // gradient gather walking its 6 x 6 candidate window with a divergent `continue` per tap).  Here a block owns one output row (forward, skip
 // gradient) or one input row (upsample gradient): the row interpolation is block-uniform, a lane's channel vector is fixed, pixels advance
 // by a constant, and every load of an iteration is issued before the first use.  Same arithmetic per element -> bit-identical results.
-#ifndef MU_UPCAT_ROWS
-#define MU_UPCAT_ROWS 1
-#endif
 template <typename T, int U>
 __global__ __launch_bounds__(256) void upcat_fwd_rows_kernel(const T* __restrict__ x, const T* __restrict__ skip, T* __restrict__ y,
                                                              int B, int h, int w, int Cx, int Cs) {
@@ -729,7 +722,7 @@ __global__ __launch_bounds__(256) void upcat_fwd_rows_kernel(const T* __restrict
             if (c < Cs) {
                 Vec16<T> v[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u) if (wb + u * ppi < Wo) EW_LD(v[u], srow + (long)(wb + u * ppi) * Cs);
+                for (int u = 0; u < U; ++u) if (wb + u * ppi < Wo) v[u].load_nt(srow + (long)(wb + u * ppi) * Cs);
 #pragma unroll
                 for (int u = 0; u < U; ++u) if (wb + u * ppi < Wo) v[u].store(yrow + (long)(wb + u * ppi) * Ct);
             } else {
@@ -782,8 +775,8 @@ __global__ __launch_bounds__(256) void upcat_bwd_rows_kernel(const T* __restrict
 #pragma unroll
             for (int u = 0; u < U; ++u)
                 if (wb + u * ppi < Wo) {
-                    EW_LD(v[u], g1 + (long)(wb + u * ppi) * Ct);
-                    if (g2) EW_LD(v2[u], g2 + (long)(wb + u * ppi) * Ct);
+                    v[u].load_nt(g1 + (long)(wb + u * ppi) * Ct);
+                    if (g2) v2[u].load_nt(g2 + (long)(wb + u * ppi) * Ct);
                 }
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -973,7 +966,7 @@ extern "C" int mu_upcat_fwd(const void* x, const void* skip, void* y, int B, int
     } else if (dtype == MU_F16) {
         long total = (long)B * 4 * h * w * ((Cx + Cs) / 8);
         const int cv = (Cx + Cs) / 8;
-        if (MU_UPCAT_ROWS && cv <= 256 && 256 % cv == 0 && (long)B * 2 * h < (1 << 30))
+        if (cv <= 256 && 256 % cv == 0 && (long)B * 2 * h < (1 << 30))
             upcat_fwd_rows_kernel<h16, 4><<<B * 2 * h < 16384 ? B * 2 * h : 16384, 256, 0, st>>>((const h16*)x, (const h16*)skip, (h16*)y, B, h, w, Cx, Cs);
         else
             upcat_fwd_kernel<h16><<<ew_grid(total), 256, 0, st>>>((const h16*)x, (const h16*)skip, (h16*)y, B, h, w, Cx, Cs);
@@ -992,7 +985,7 @@ extern "C" int mu_upcat_bwd_acc(const void* dy, const void* dy2, void* dx, void*
     } else if (dtype == MU_F16) {
         long total = (long)B * 4 * h * w * (Cs / 8) + (long)B * h * w * (Cx / 8);
         const int cvs = Cs / 8, cvx = Cx / 8;
-        if (MU_UPCAT_ROWS && cvs <= 256 && 256 % cvs == 0 && cvx <= 256 && 256 % cvx == 0 && (long)B * 3 * h < (1 << 30))
+        if (cvs <= 256 && 256 % cvs == 0 && cvx <= 256 && 256 % cvx == 0 && (long)B * 3 * h < (1 << 30))
             upcat_bwd_rows_kernel<h16><<<B * 3 * h, 256, 0, st>>>((const h16*)dy, (const h16*)dy2, (h16*)dx, (h16*)dskip, B, h, w, Cx, Cs);
         else
             upcat_bwd_kernel<h16><<<ew_grid(total), 256, 0, st>>>((const h16*)dy, (const h16*)dy2, (h16*)dx, (h16*)dskip, B, h, w, Cx, Cs);
@@ -1026,7 +1019,7 @@ __global__ __launch_bounds__(256) void dropout_kernel(const T* __restrict__ x, T
     if (seed_step) seed ^= splitmix64(0x9E3779B97F4A7C15ull * (uint64_t)seed_step[0]);     // per-replay stream of a captured step
     for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += (long)gridDim.x * 256) {
         Vec16<T> a, o;
-        EW_LD(a, x + v * N);
+        a.load_nt(x + v * N);
         uint64_t r0 = 0, r1 = 0;
         if (!mask) {
             r0 = splitmix64(seed ^ (uint64_t)(2 * v) * 0xD6E8FEB86659FD93ull);
@@ -1079,7 +1072,7 @@ __global__ __launch_bounds__(256) void add_kernel(const T* __restrict__ a, const
     constexpr int N = Vec16<T>::N;
     for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += (long)gridDim.x * 256) {
         Vec16<T> x, y, z;
-        EW_LD(x, a + v * N); EW_LD(y, b + v * N);
+        x.load_nt(a + v * N); y.load_nt(b + v * N);
 #pragma unroll
         for (int i = 0; i < N; ++i) z.set(i, x.get(i) + y.get(i));
         z.store(o + v * N);

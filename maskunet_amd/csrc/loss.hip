@@ -11,9 +11,6 @@
 // backward: dlogits = (softmax - onehot) * gscale / count  (0 for ignored rows and for the channel padding).
 // ------------------------------------------------------------------------------------------
 #define CE_MAXBLK 1024
-#ifndef MU_CE_U2
-#define MU_CE_U2 4
-#endif
 
 // Rows of up to 3 * 128 channels are held in registers (one read of the logits; the two-pass form re-reads every row from L2 with a
 // single load in flight per lane and ran at 1.5 TB/s); several rows per lane group per iteration keep more loads in flight.  Branch-free:
@@ -89,7 +86,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logit
     const int nv = (Cp + 16 * VN - 1) / (16 * VN);
     // U rows per 16-lane group and iteration: the bytes in flight per wave (one exposed memory round trip per iteration)
     if (nv == 1) ce_rows_in_regs<T, 1, 4>(logits, labels, M, Cp, C, ignore_index, lse_out, loss, cnt, l16, rowl);
-    else if (nv == 2) ce_rows_in_regs<T, 2, MU_CE_U2>(logits, labels, M, Cp, C, ignore_index, lse_out, loss, cnt, l16, rowl);
+    else if (nv == 2) ce_rows_in_regs<T, 2, 4>(logits, labels, M, Cp, C, ignore_index, lse_out, loss, cnt, l16, rowl);
     else if (nv == 3) ce_rows_in_regs<T, 3, 2>(logits, labels, M, Cp, C, ignore_index, lse_out, loss, cnt, l16, rowl);
     else
     for (long r0 = (long)blockIdx.x * 16; r0 < M; r0 += (long)gridDim.x * 16) {

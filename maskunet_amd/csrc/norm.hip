@@ -5,36 +5,12 @@
 // Statistics are accumulated in fp64 (sum, sum of squares) so the biased variance is exact to
 // fp32 rounding regardless of mean/variance ratio; everything else is fp32 math on T storage.
 #include "common.h"
-// Nontemporal loads of the streamed operands (bits: 1 bn_act_fwd x, 4 statistics sweeps, 8 bn_bwd_apply, 16 residual operand, 32 per-sample LayerNorm apply passes): the passes
-// touch every byte once per launch; `nt` loads bypass the CU's L1 (MI355X_MICROARCH: L2-served).
-#ifndef MU_BN_NT
-#define MU_BN_NT 57              // whole step 29.88 -> 29.70 ms; with the statistics sweeps too (29): 29.77
-#endif
-#define MU_LD(bit, vec, ptr_) do { if (MU_BN_NT & (bit)) (vec).load_nt(ptr_); else (vec).load(ptr_); } while (0)
+// Nontemporal loads of the streamed operands of bn_act_fwd (x), bn_bwd_apply, the residual operand and the per-sample LayerNorm apply
+// passes: the passes touch every byte once per launch; `nt` loads bypass the CU's L1 (MI355X_MICROARCH: L2-served).  Whole step
+// 29.88 -> 29.70 ms; with the statistics sweeps' x / g loads nontemporal too: 29.77, so those stay plain loads.
 #include "../../include/maskunet_hip.h"
 
 #define MU_STAT_MAXBLK 1024
-#ifndef MU_BN_BLK1
-#define MU_BN_BLK1 768
-#endif
-#ifndef MU_BN_U1
-#define MU_BN_U1 2
-#endif
-#ifndef MU_BN_UF
-#define MU_BN_UF 2
-#endif
-#ifndef MU_BN_UA
-#define MU_BN_UA 2
-#endif
-#ifndef MU_BN_STRIDED
-#define MU_BN_STRIDED 1            // whole step 28.80 -> 28.71 ms, the backward sweep 0.275 -> 0.268 ms on a 256 MiB tensor
-#endif
-#ifndef MU_BN_FROWS
-#define MU_BN_FROWS 1
-#endif
-#ifndef MU_BN_OCC1
-#define MU_BN_OCC1 1
-#endif
 
 // ------------------------------------------------------------------------------------------
 // per-channel partial sums over a block of rows.
@@ -44,7 +20,7 @@
 // Each thread keeps U independent 16-byte loads per operand in flight (the sweep is latency-bound otherwise: one load
 // per wave covers 1 KB and a CU needs ~64 KB outstanding to saturate HBM), sums the U rows in fp32 and folds that
 // short sum into the fp64 accumulators -- U-fold fewer fp64 instructions, same final precision (fp32 sum of <= 8 terms).
-// FAST = the fp16-storage GELU (common.h mu_phi_fast); fp32 storage keeps erff.
+// FAST = the fp16-storage GELU (common.h mu_phi_poly); fp32 storage keeps erff.
 // ------------------------------------------------------------------------------------------
 // ACT / RES (round 5): the activation and the presence of a residual operand as COMPILE-TIME constants (-1 = read the runtime argument).
 // With `act` a kernel argument every element pair sat in its own basic block behind two scalar branches (GELU / ReLU / none), the
@@ -54,13 +30,13 @@
 // pmax[(block * C + c) * 2 + {0, 1}] -- the finalize kernel turns them into a per-channel bound of |dx|, the apply pass into the power-of-two
 // scale under which it writes dx as ONE fp16 operand (see bn_bwd_final_kernel / bn_bwd_apply_kernel).
 template <typename T, int MODE, int ACT = -1, int RES = -1, bool MAXT = false>
-__global__ __launch_bounds__(256, MODE == 1 ? MU_BN_OCC1 : 1) void bn_partial_kernel(const T* __restrict__ x, const T* __restrict__ g, const T* __restrict__ res,
+__global__ __launch_bounds__(256, 1) void bn_partial_kernel(const T* __restrict__ x, const T* __restrict__ g, const T* __restrict__ res,
                                                          T* __restrict__ dzbuf, long M, int C, long ld,
                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta, int act_arg,
                                                          double* __restrict__ part, float* __restrict__ pmax = nullptr) {
     constexpr int N = Vec16<T>::N;
-    constexpr int U = MODE == 0 ? 8 : MU_BN_U1;
+    constexpr int U = MODE == 0 ? 8 : 2;
     constexpr bool FAST = sizeof(T) == 2;
     const int act = ACT >= 0 ? ACT : act_arg;
     const bool has_res = RES >= 0 ? (RES != 0) : (res != nullptr);
@@ -68,16 +44,11 @@ __global__ __launch_bounds__(256, MODE == 1 ? MU_BN_OCC1 : 1) void bn_partial_ke
     const int cv = C / N;
     const int rpi = 256 / cv;
     const int tc = threadIdx.x % cv, tr = threadIdx.x / cv;
-#if MU_BN_STRIDED
     // chunks of U * rpi rows dealt round-robin: at any moment the resident blocks read ONE front of the tensor (as the grid-stride apply
-    // passes do) instead of gridDim.x separate sequential streams
+    // passes do) instead of gridDim.x separate sequential streams (whole step 28.80 -> 28.71 ms, the backward sweep 0.275 -> 0.268 ms
+    // on a 256 MiB tensor)
     const long r0 = (long)blockIdx.x * (U * rpi), r1 = M;
     const long rstride = (long)gridDim.x * (U * rpi);
-#else
-    const long rows_per_blk = (M + gridDim.x - 1) / gridDim.x;
-    const long r0 = (long)blockIdx.x * rows_per_blk, r1 = (r0 + rows_per_blk < M ? r0 + rows_per_blk : M);
-    const long rstride = (long)U * rpi;
-#endif
     double s0[N], s1[N];
     float mxg[N], mxx[N];                                       // MAXT: running max|dz|, max|xhat| of this thread's channels
 #pragma unroll
@@ -97,10 +68,10 @@ __global__ __launch_bounds__(256, MODE == 1 ? MU_BN_OCC1 : 1) void bn_partial_ke
             for (int u = 0; u < U; ++u) {
                 const long rr = r + (long)u * rpi;
                 if (rr < r1) {
-                    MU_LD(4, xv[u], x + rr * ld + c);
+                    xv[u].load(x + rr * ld + c);
                     if (MODE == 1) {
-                        MU_LD(4, gv[u], g + rr * ld + c);
-                        if (has_res) MU_LD(16, rv[u], res + rr * ld + c);
+                        gv[u].load(g + rr * ld + c);
+                        if (has_res) rv[u].load_nt(res + rr * ld + c);
                     }
                 } else {
                     xv[u].zero();
@@ -302,7 +273,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const T* __restrict__ x
                                                          const float* __restrict__ gamma, const float* __restrict__ beta, int act_arg,
                                                          h16* __restrict__ y16 = nullptr) {
     constexpr int N = Vec16<T>::N;
-    constexpr int U = MU_BN_UF;
+    constexpr int U = 2;
     constexpr bool FAST = sizeof(T) == 2;
     const int act = ACT >= 0 ? ACT : act_arg;
     const bool has_res = RES >= 0 ? (RES != 0) : (res != nullptr);
@@ -324,8 +295,8 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const T* __restrict__ x
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (idx + u * stride < total) {
-                MU_LD(1, xv[u], x + (r + u * rstep) * ld + c);
-                if (has_res) MU_LD(16, rv[u], res + (r + u * rstep) * ld + c);
+                xv[u].load_nt(x + (r + u * rstep) * ld + c);
+                if (has_res) rv[u].load_nt(res + (r + u * rstep) * ld + c);
             }
         }
 #pragma unroll
@@ -346,11 +317,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const T* __restrict__ x
                     *reinterpret_cast<uint4*>(y + (r + u * rstep) * ld + c) = e4;
                     if (y16) *reinterpret_cast<uint2*>(y16 + (r + u * rstep) * (long)C + c) = make_uint2(e4.x, e4.y);
                 } else {
-#if MU_BN_NT & 2
-                o.store_nt(y + (r + u * rstep) * ld + c);
-#else
-                o.store(y + (r + u * rstep) * ld + c);
-#endif
+                    o.store(y + (r + u * rstep) * ld + c);
                 }
             }
         }
@@ -370,7 +337,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
                                                            const float* __restrict__ s1, const float* __restrict__ s2,
                                                            const float* __restrict__ bound = nullptr, float* __restrict__ dy_scale = nullptr) {
     constexpr int N = Vec16<T>::N;
-    constexpr int U = MU_BN_UA;
+    constexpr int U = 2;
     constexpr bool FAST = sizeof(T) == 2;
     const int act = ACT >= 0 ? ACT : act_arg;
     const int cv = C / N;
@@ -411,8 +378,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (idx + u * stride < total) {
-                MU_LD(8, xv[u], x + (r + u * rstep) * ld + c);
-                MU_LD(8, dz[u], dzbuf + (r + u * rstep) * ld + c);
+                xv[u].load_nt(x + (r + u * rstep) * ld + c);
+                dz[u].load_nt(dzbuf + (r + u * rstep) * ld + c);
             }
         }
 #pragma unroll
@@ -604,7 +571,7 @@ extern "C" int mu_bn_train_stats_rows(const float* stat_part, int rows, long M, 
     const int nblk = (rows + rpb - 1) / rpb;
     if (ws_bytes < mu_bn_workspace_bytes(C)) return MU_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    if (MU_BN_FROWS && rows <= MU_STAT_MAXBLK) {        // few rows: the finalize kernel sums them itself (one launch less)
+    if (rows <= MU_STAT_MAXBLK) {        // few rows: the finalize kernel sums them itself (one launch less)
         bn_fwd_final_kernel<true><<<mu_cdiv(C, 4), 256, 0, st>>>(stat_part, rows, C, M, eps, momentum, mean, rstd, running_mean, running_var,
                                                                  c_valid, num_batches_tracked);
         MU_CHECK_LAUNCH();
@@ -712,7 +679,7 @@ static int bn_act_bwd_t(const T* x, const T* res, const T* g, T* dx, T* dres, lo
     // the backward statistics kernel holds 3 blocks per CU (136 VGPRs): 768 resident blocks = one whole round (1024 would leave a
     // second round one third full)
     int nblk = stat_blocks(M);
-    if (nblk > MU_BN_BLK1) nblk = MU_BN_BLK1;
+    if (nblk > 768) nblk = 768;
     size_t lds = (size_t)rpi * C * 2 * sizeof(double);
     double* part = (double*)ws;
     float* s1 = (float*)((char*)ws + (size_t)MU_STAT_MAXBLK * C * 2 * sizeof(double));
@@ -973,7 +940,7 @@ __global__ __launch_bounds__(256) void lns_fwd_apply_kernel(const T* __restrict_
         for (int b = 0; b < B; ++b) {
             const float mu = mean[b], rs = rstd[b];
             Vec16<T> xv, o;
-            MU_LD(32, xv, x + (long)b * L + v * N);
+            xv.load_nt(x + (long)b * L + v * N);
 #pragma unroll
             for (int i = 0; i < N; ++i) o.set(i, (xv.get(i) - mu) * rs * wv[i] + bv[i]);
             o.store(y + (long)b * L + v * N);
@@ -996,8 +963,8 @@ __global__ __launch_bounds__(256) void lns_bwd_apply_kernel(const T* __restrict_
         for (int b = 0; b < B; ++b) {
             const float mu = mean[b], rs = rstd[b], a1 = m1[b], a2 = m2[b];
             Vec16<T> xv, gv, o;
-            MU_LD(32, xv, x + (long)b * L + v * N);
-            MU_LD(32, gv, dy + (long)b * L + v * N);
+            xv.load_nt(x + (long)b * L + v * N);
+            gv.load_nt(dy + (long)b * L + v * N);
 #pragma unroll
             for (int i = 0; i < N; ++i) {
                 float xh = (xv.get(i) - mu) * rs, g = gv.get(i);

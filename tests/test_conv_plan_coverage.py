@@ -58,6 +58,8 @@ def test_names_are_stable_and_ids_outside_the_table_have_none():
     assert C.plan_name("fwd", 1) == "nt5" and C.plan_name("fwd", 8) == "nt3_64"          # the Conv3x3Kernel values
     for op, code in C.OPS.items():
         assert lib.mu_conv_plan_name(code, 0) is None and lib.mu_conv_plan_name(code, lib.mu_conv_plan_count(code)) is None
+        names = [lib.mu_conv_plan_name(code, i) for i in range(1, lib.mu_conv_plan_count(code))]
+        assert all(names) and len(set(names)) == len(names), (op, names)                   # every id of the table is a reachable kernel
     assert lib.mu_conv_plan_name(7, 1) is None
     # arguments no entry point accepts have no plan
     assert lib.mu_conv_fwd_plan(1, 8, 8, 48, 32, 9, 1, 0) == 0 and lib.mu_conv_fwd_plan(1, 8, 8, 32, 32, 4, 1, 0) == 0

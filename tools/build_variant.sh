@@ -1,19 +1,15 @@
 #!/bin/bash
-# Build a variant of the HIP library for in-process A/B timing: tools/build_variant.sh NAME "-DMU_FLAG=1 ..."
+# A second build of the HIP library for A/B timing against the in-tree one (MU_LIB_PATH): tools/build_variant.sh NAME [SOURCE_DIR]
 # -> gpurun_variants/libmu_NAME.so (used by tools/ab_bench.py).  Debug aid, not part of the product build.
+# SOURCE_DIR: a checkout of this repository (default: this tree), e.g. `git worktree add ../parent HEAD~1`.  The library is built by
+# that checkout's own maskunet_amd/csrc/Makefile -- its file list and flags -- with the objects and the library redirected here.
+# (A checkout whose Makefile has no OBJDIR yet leaves its objects in its own csrc/; the library still lands here.)
 set -e
-NAME=$1; shift
-EXTRA="$*"
+NAME=${1:?usage: tools/build_variant.sh NAME [SOURCE_DIR]}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-SRC=${MU_SRC:-$ROOT/maskunet_amd/csrc}      # MU_SRC=<dir> builds another checkout's sources (e.g. a git worktree of HEAD)
+SRC=$(cd "${2:-$ROOT}" && pwd)
 OUT=$ROOT/gpurun_variants
-mkdir -p $OUT/obj_$NAME
-for f in elementwise norm conv attn attn_wide loss probe version; do
-  FL=""; [ $f = attn ] && FL="-fno-slp-vectorize"      # as the Makefile builds attn.hip (FLAGS_attn)
-  [ $f = conv ] && [ -z "$MU_CONV_SLP" ] && FL="-fno-slp-vectorize"      # FLAGS_conv (MU_CONV_SLP=1: the former build)
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-value -Wno-pass-failed $FL $EXTRA -c $SRC/$f.hip -o $OUT/obj_$NAME/$f.o &
-done
-wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OUT/obj_$NAME/*.o -o $OUT/libmu_$NAME.so
-rm -rf $OUT/obj_$NAME
-echo built $OUT/libmu_$NAME.so
+mkdir -p "$OUT"
+make -C "$SRC/maskunet_amd/csrc" -j8 OBJDIR="$OUT/obj_$NAME" LIB="$OUT/libmu_$NAME.so"
+rm -rf "$OUT/obj_$NAME"
+echo built "$OUT/libmu_$NAME.so"
