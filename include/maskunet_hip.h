@@ -432,6 +432,26 @@ long mu_instances_workspace_bytes(int B, int H, int W, int max_inst);
 int mu_instances_supported(int H, int W, int max_inst);
 int mu_instances(const int* cls, const float* prob_or_null, int B, int H, int W, int max_inst, int* ids, int* table, float* score,
                  int* count, int* order, void* workspace, long ws_bytes, void* stream);
+/* Instances of the 3-head model from its embedding head: get_instances_from_embeddings + get_instance_annotations
+ * (city_instance.py:405-449), i.e. per image and per class 1 <= c < num_classes (ascending; every other value is background)
+ * sklearn's DBSCAN(eps, min_samples) over the embeddings of the class's pixels, restated:
+ *   points     the pixels of class c in raster order, D coordinates each;
+ *   neighbours i ~ j iff sum_k (double(a_k) - double(b_k))^2 <= double(eps)^2, decided in fp64 for fp32 and fp16 input alike (i ~ i);
+ *   core       at least min_samples neighbours, itself included;
+ *   clusters   connected components of the core points under ~, ordered by their lowest core point (not their lowest pixel);
+ *   border     a non-core point with a core neighbour joins the first such cluster that has one; other non-core points are noise (id 0);
+ *   ids        1..count per image over (class ascending, cluster order).
+ * cls: int32 [B,H,W].  emb element (pixel r of B*H*W, channel k) at emb[(r / inner) * outer_stride + k * c_stride + (r % inner) * p_stride]
+ * (the addressing of mu_argmax_prob: NCHW, or the NHWC rows of a module output), dtype MU_F32 / MU_F16, values finite.
+ * ids / table / score / count / order as for mu_instances (also past max_inst); every score is 1.0, so order is ascending id;
+ * first_pixel is the instance's lowest pixel, which may be a border pixel.  Bit-identical from run to run.
+ * H*W <= 65536, 1 <= D <= 64, 1 <= num_classes <= 1024, 1 <= max_inst <= 4096, min_samples >= 1, eps > 0, else MU_ERR_SHAPE
+ * (mu_dbscan_supported and mu_dbscan_workspace_bytes: host only; the latter is 0 for unsupported shapes). */
+long mu_dbscan_workspace_bytes(int B, int H, int W, int num_classes, int max_inst);
+int mu_dbscan_supported(int H, int W, int D, int num_classes, int max_inst);
+int mu_dbscan_instances(const int* cls, const void* emb, int B, int H, int W, int D, long inner, long outer_stride, long c_stride,
+                        long p_stride, int dtype, int num_classes, float eps, int min_samples, int max_inst, int* ids, int* table,
+                        float* score, int* count, int* order, void* workspace, long ws_bytes, void* stream);
 /* f4: uint8 HWC image bytes [npix, C] -> [0,1] floats in the NHWC compute layout [npix, Cp] (ToTensor, ade_semantic.py:85) */
 int mu_u8_to_nhwc(const unsigned char* src, void* dst, long npix, int C, int Cp, int dtype, void* stream);
 /* f4, resize half: the sample preparation of the reference datasets on the device.  src: decoded image bytes [B][Hs][Ws][C] (C <= 4, as

@@ -442,3 +442,422 @@ extern "C" int mu_instances(const int* cls, const float* prob_or_null, int B, in
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
+
+// ------------------------------------------------------------------------------------------
+// mu_dbscan_instances: instances of the 3-head model from its embedding head, get_instances_from_embeddings + get_instance_annotations
+// (city_instance.py:405-449): per image and class c >= 1, sklearn's DBSCAN(eps, min_samples) over the class's pixel embeddings.
+// Contract: points of a class in raster order; i ~ j iff sum_k (double(a_k) - double(b_k))^2 <= double(eps)^2; core =
+// at least min_samples neighbours (itself included); a cluster = a connected component of core points, ordered by its lowest core
+// point; a non-core point joins the first cluster that holds a core neighbour of it, else it is noise (id 0).
+//
+// The neighbour decision is plain fp64 VALU (sub + fma per dimension): fp32 and fp16 values widen exactly, so the decision is the
+// contract's for both and for every layout.  Kernels, all stream-ordered, nothing read back:
+//   group   one workgroup per image: stable counting sort of the pixels by class -> perm (class ascending, raster within a class),
+//           pos_of (its inverse, -1 = background), seg[c] (start of class c in perm), one tile descriptor per DB_TR points of a class;
+//   sweep   grid (worst-case tiles, B), early exit past ntiles[b].  A workgroup keeps DB_TR points of one class in registers (one per
+//           lane) and streams the class's points through LDS in chunks of DB_TC; every lane reads the same column value (broadcast).
+//             COUNT   neighbours per row point -> link[pos] = pos (core) or -1;
+//             UNION   core x core, column < row: union-find on link[] in global memory.  Only roots are re-linked, by CAS, always to the
+//                     smaller index (the discipline of inst_label_kernel), so a cluster's root is its lowest core point whatever the
+//                     order; every access to link[] that can race is an agent-scope atomic.  A pair is skipped when the column's link
+//                     (snapshot in LDS) equals the row's last known root: both are ancestors, so the two are already joined;
+//             BORDER  lab[pos] = root (core), min root over the core neighbours (border) or -1 (noise); link[] is only read here;
+//   number  one workgroup per image: ids = exclusive scan of the root flags in perm order, scattered through pos_of; first pixel of
+//           each id by integer atomicMin in LDS (a border pixel may precede the root); then inst_stats_kernel as for mu_instances.
+// Tile sizes.  DB_TR = 256: one row point per lane holds DP doubles in registers (DP = D padded to 4 / 16 / 32 / 64: up to 128
+// VGPRs), four waves share one LDS chunk.  DB_TC = 64: 64 x DP doubles = 8 KiB at DP = 16, 32 KiB at DP = 64, so at least four
+// workgroups fit a CU's 160 KiB; per column the inner loop is one broadcast LDS read of 16 bytes per two dimensions against four
+// fp64 VALU instructions, i.e. VALU-bound (fp64 runs at a quarter of a wave per cycle, the LDS serves a broadcast read in one).
+// ------------------------------------------------------------------------------------------
+#define DB_TR 256
+#define DB_TC 64
+#define DB_GROUP_THREADS 512
+#define DB_GROUP_WAVES (DB_GROUP_THREADS / 64)
+#define DB_MAX_CLASSES 1024
+#define DB_MAX_D 64
+
+struct DbParams {
+    const void* emb;
+    int N, D, nc, max_tiles, min_samples;
+    long inner, outer_stride, c_stride, p_stride;
+    double eps2;
+    int *perm, *pos_of, *link, *lab, *seg, *tiles, *ntiles;      // per image: N, N, N, N, nc + 1, 2 * max_tiles, 1 ints
+};
+
+// Dynamic LDS: int wcnt[DB_GROUP_WAVES][nc], start[nc], cnt[nc], toff[nc]   (44 KiB at 1024 classes)
+__global__ __launch_bounds__(DB_GROUP_THREADS) void db_group_kernel(const int* __restrict__ cls_all, DbParams P) {
+    extern __shared__ unsigned inst_lds[];
+    const int N = P.N, nc = P.nc;
+    int* wcnt = (int*)inst_lds;
+    int* start = wcnt + DB_GROUP_WAVES * nc;
+    int* cnt = start + nc;
+    int* toff = cnt + nc;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int* cls = cls_all + (long)b * N;
+    int* perm = P.perm + (long)b * N;
+    int* pos_of = P.pos_of + (long)b * N;
+    int* seg = P.seg + (long)b * (nc + 1);
+    int* tiles = P.tiles + (long)b * P.max_tiles * 2;
+
+    for (int k = tid; k < DB_GROUP_WAVES * nc; k += DB_GROUP_THREADS) wcnt[k] = 0;
+    __syncthreads();
+
+    // 1. per wave and class: pixels of the wave's raster range [lo, hi).  The counters of a wave are its own: no atomics.
+    const int span = ((N + DB_GROUP_THREADS - 1) / DB_GROUP_THREADS) * 64;
+    const int lo = wave * span, hi = min(N, lo + span);
+    int* mine = wcnt + wave * nc;
+    for (int base = lo; base < hi; base += 64) {
+        const int i = base + lane;
+        const int c = i < hi ? cls[i] : 0;
+        const bool fg = c >= 1 && c < nc;
+        unsigned long long rem = __ballot(fg);
+        while (rem) {
+            const int leader = __ffsll((long long)rem) - 1;
+            const int c0 = __shfl(c, leader);
+            const unsigned long long m = __ballot(fg && c == c0);
+            if (lane == leader) mine[c0] += __popcll(m);
+            rem &= ~m;
+        }
+    }
+    __syncthreads();
+
+    // 2. per class: exclusive prefix over the waves, total
+    for (int c = tid; c < nc; c += DB_GROUP_THREADS) {
+        int run = 0;
+        for (int v = 0; v < DB_GROUP_WAVES; ++v) {
+            const int t = wcnt[v * nc + c];
+            wcnt[v * nc + c] = run;
+            run += t;
+        }
+        cnt[c] = run;
+    }
+    __syncthreads();
+
+    // 3. wave 0: exclusive scans over the classes of the point counts (segment starts) and of the tile counts
+    if (wave == 0) {
+        int carry_n = 0, carry_t = 0;
+        for (int base = 0; base < nc; base += 64) {
+            const int c = base + lane;
+            const int n = c < nc ? cnt[c] : 0;
+            const int t = (n + DB_TR - 1) / DB_TR;
+            int sn = n, st = t;
+            for (int o = 1; o < 64; o <<= 1) {
+                const int un = __shfl_up(sn, o), ut = __shfl_up(st, o);
+                if (lane >= o) { sn += un; st += ut; }
+            }
+            if (c < nc) {
+                start[c] = carry_n + sn - n;
+                toff[c] = carry_t + st - t;
+                seg[c] = carry_n + sn - n;
+            }
+            carry_n += __shfl(sn, 63);
+            carry_t += __shfl(st, 63);
+        }
+        if (lane == 0) {
+            seg[nc] = carry_n;
+            P.ntiles[b] = carry_t;
+        }
+    }
+    __syncthreads();
+
+    // 4. tile descriptors (class, first point); the waves' counters become absolute positions.
+    //    sum_c ceil(n_c / DB_TR) <= N / DB_TR + (classes with points) <= max_tiles
+    for (int c = tid; c < nc; c += DB_GROUP_THREADS) {
+        const int n = cnt[c], s = start[c], t0 = toff[c];
+        for (int k = 0; k * DB_TR < n; ++k) {
+            tiles[2 * (t0 + k)] = c;
+            tiles[2 * (t0 + k) + 1] = s + k * DB_TR;
+        }
+        for (int v = 0; v < DB_GROUP_WAVES; ++v) wcnt[v * nc + c] += s;
+    }
+    __syncthreads();
+
+    // 5. placement, stable: the same walk as step 1
+    for (int base = lo; base < hi; base += 64) {
+        const int i = base + lane;
+        const int c = i < hi ? cls[i] : 0;
+        const bool fg = c >= 1 && c < nc;
+        if (i < hi && !fg) pos_of[i] = -1;
+        unsigned long long rem = __ballot(fg);
+        while (rem) {
+            const int leader = __ffsll((long long)rem) - 1;
+            const int c0 = __shfl(c, leader);
+            const unsigned long long m = __ballot(fg && c == c0);
+            const int at = mine[c0];
+            if (fg && c == c0) {
+                const int pos = at + __popcll(m & ((1ull << lane) - 1ull));
+                perm[pos] = i;
+                pos_of[i] = pos;
+            }
+            if (lane == leader) mine[c0] = at + __popcll(m);
+            rem &= ~m;
+        }
+    }
+}
+
+__device__ __forceinline__ int db_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int db_find(const int* p, int x) {
+    for (;;) {
+        const int q = db_ld(p + x);
+        if (q == x) return x;
+        x = q;                               // links strictly decrease along a chain
+    }
+}
+// joins the sets of a and b; returns a common ancestor of both (the root at the time of the call)
+__device__ __forceinline__ int db_unite(int* p, int a, int b) {
+    for (;;) {
+        a = db_find(p, a);
+        b = db_find(p, b);
+        if (a == b) return a;
+        if (a < b) { const int t = a; a = b; b = t; }
+        const int old = atomicCAS(p + a, a, b);         // agent scope; fails only if someone else re-linked the root a: progress
+        if (old == a) return b;
+        a = old;
+    }
+}
+__device__ __forceinline__ int db_find_plain(const int* p, int x) {      // no writer in the same kernel
+    for (;;) {
+        const int q = p[x];
+        if (q == x) return x;
+        x = q;
+    }
+}
+
+enum { DB_COUNT = 0, DB_UNION = 1, DB_BORDER = 2 };
+
+template <typename T, int DP, int MODE>
+__global__ __launch_bounds__(DB_TR) void db_sweep_kernel(DbParams P) {
+    __shared__ double cols[DB_TC * DP];
+    __shared__ long poff[DB_TC];
+    __shared__ int lk[DB_TC];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    if ((int)blockIdx.x >= P.ntiles[b]) return;
+    const int N = P.N, D = P.D;
+    const int* td = P.tiles + ((long)b * P.max_tiles + blockIdx.x) * 2;
+    const int c = td[0], row0 = td[1];
+    const int* seg = P.seg + (long)b * (P.nc + 1);
+    const int s0 = seg[c], s1 = seg[c + 1];
+    const int* perm = P.perm + (long)b * N;
+    int* link = P.link + (long)b * N;
+    const T* emb = (const T*)P.emb;
+    const long cs = P.c_stride;
+
+    const int gi = row0 + tid;
+    const bool rvalid = gi < s1;
+    int mylink = 0;
+    if (MODE != DB_COUNT) mylink = rvalid ? link[gi] : 0;
+    bool active = rvalid;
+    if (MODE == DB_UNION) active = rvalid && mylink >= 0;
+    if (MODE == DB_BORDER) {
+        active = rvalid && mylink < 0;
+        if (rvalid && mylink >= 0) P.lab[(long)b * N + gi] = db_find_plain(link, gi);
+    }
+    if (MODE != DB_COUNT && !__syncthreads_or(active)) return;
+
+    double r[DP];
+    {
+        long off = 0;
+        if (rvalid) {
+            const long g = (long)b * N + perm[gi];
+            off = (g / P.inner) * P.outer_stride + (g % P.inner) * P.p_stride;
+        }
+#pragma unroll
+        for (int k = 0; k < DP; ++k) r[k] = (rvalid && k < D) ? (double)(float)emb[off + k * cs] : 0.0;
+    }
+
+    int acc_i = MODE == DB_BORDER ? 0x7fffffff : (MODE == DB_UNION ? gi : 0);      // neighbour count / last known root / min root
+    const int c_end = MODE == DB_UNION ? min(s1, row0 + DB_TR) : s1;                // UNION: only columns below the rows
+    for (int c0 = s0; c0 < c_end; c0 += DB_TC) {
+        const int jn = min(DB_TC, c_end - c0);
+        __syncthreads();                        // the previous chunk has been consumed
+        if (tid < DB_TC) {
+            long off = 0;
+            int l = -1;
+            if (tid < jn) {
+                const long g = (long)b * N + perm[c0 + tid];
+                off = (g / P.inner) * P.outer_stride + (g % P.inner) * P.p_stride;
+                if (MODE == DB_UNION) l = link[c0 + tid];              // a hint: any value seen here is an ancestor (or -1: not core)
+                if (MODE == DB_BORDER) {
+                    l = link[c0 + tid];
+                    if (l >= 0) l = db_find_plain(link, l);
+                }
+            }
+            poff[tid] = off;
+            lk[tid] = l;
+        }
+        __syncthreads();
+        for (int e = tid; e < DB_TC * DP; e += DB_TR) {
+            int j, k;
+            if (cs == 1) { k = e % DP; j = e / DP; }                   // channels contiguous (NHWC)
+            else { j = e % DB_TC; k = e / DB_TC; }                     // pixels contiguous (NCHW)
+            cols[j * DP + k] = (j < jn && k < D) ? (double)(float)emb[poff[j] + k * cs] : 0.0;
+        }
+        __syncthreads();
+        for (int j = 0; j < jn; ++j) {
+            if (MODE != DB_COUNT && lk[j] < 0) continue;               // uniform: the column is not a core point
+            const double* cj = cols + j * DP;
+            double d2 = 0.0;
+#pragma unroll
+            for (int k = 0; k < DP; ++k) {
+                const double d = r[k] - cj[k];
+                d2 = fma(d, d, d2);
+            }
+            const bool near = d2 <= P.eps2;
+            if (MODE == DB_COUNT) {
+                acc_i += near ? 1 : 0;
+            } else if (MODE == DB_UNION) {
+                const int gj = c0 + j;
+                if (active && near && gj < gi && lk[j] != acc_i) {
+                    const int root = db_unite(link, gi, gj);
+                    // shorten both chains: root < x makes x a non-root for good, and non-roots are never the target of a CAS
+                    if (root < gi) __hip_atomic_store(link + gi, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (root < gj) __hip_atomic_store(link + gj, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    acc_i = root;
+                }
+            } else {
+                if (active && near) acc_i = min(acc_i, lk[j]);
+            }
+        }
+    }
+    if (MODE == DB_COUNT) {
+        if (rvalid) link[gi] = acc_i >= P.min_samples ? gi : -1;
+    } else if (MODE == DB_BORDER) {
+        if (active) P.lab[(long)b * N + gi] = acc_i == 0x7fffffff ? -1 : acc_i;
+    }
+}
+
+// Dynamic LDS: int first[max_inst], unsigned wave_total[INST_WAVES].  link[] is dead after the border sweep and takes the roots' ids.
+__global__ __launch_bounds__(INST_THREADS) void db_number_kernel(DbParams P, int max_inst, int* __restrict__ ids_all,
+                                                                  int* __restrict__ count, int* __restrict__ first_all) {
+    extern __shared__ unsigned inst_lds[];
+    int* first = (int*)inst_lds;
+    unsigned* wave_total = inst_lds + max_inst;
+    const int N = P.N;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int* lab = P.lab + (long)b * N;
+    const int* pos_of = P.pos_of + (long)b * N;
+    int* rid = P.link + (long)b * N;
+    int* ids = ids_all + (long)b * N;
+    const int nfg = P.seg[(long)b * (P.nc + 1) + P.nc];
+
+    for (int k = tid; k < max_inst; k += INST_THREADS) first[k] = 0x7fffffff;
+    const int span = ((nfg + INST_WAVES * 64 - 1) / (INST_WAVES * 64)) * 64;
+    const int lo = wave * span, hi = min(nfg, lo + span);
+    unsigned mine = 0;
+    for (int base = lo; base < hi; base += 64) {
+        const int i = base + lane;
+        mine += __popcll(__ballot(i < hi && lab[i] == i));
+    }
+    if (lane == 0) wave_total[wave] = mine;
+    __syncthreads();
+    unsigned running = 0, total = 0;
+    for (int v = 0; v < INST_WAVES; ++v) {
+        const unsigned t = wave_total[v];
+        if (v < wave) running += t;
+        total += t;
+    }
+    if (tid == 0) count[b] = (int)total;
+    for (int base = lo; base < hi; base += 64) {
+        const int i = base + lane;
+        const bool root = i < hi && lab[i] == i;
+        const unsigned long long mask = __ballot(root);
+        if (root) rid[i] = (int)(running + __popcll(mask & ((1ull << lane) - 1ull)) + 1u);
+        running += __popcll(mask);
+    }
+    __syncthreads();                 // the roots' ids (global memory, same workgroup) are visible past this barrier
+    for (int i = tid; i < N; i += INST_THREADS) {
+        const int pos = pos_of[i];
+        int id = 0;
+        if (pos >= 0) {
+            const int l = lab[pos];
+            if (l >= 0) id = rid[l];
+        }
+        ids[i] = id;
+        if (id > 0 && id <= max_inst) atomicMin(&first[id - 1], i);
+    }
+    __syncthreads();
+    for (int k = tid; k < max_inst; k += INST_THREADS) first_all[(long)b * max_inst + k] = first[k];
+}
+
+extern "C" int mu_dbscan_supported(int H, int W, int D, int num_classes, int max_inst) {
+    if (H <= 0 || W <= 0 || (long)H * W > INST_MAX_PIXELS) return MU_ERR_SHAPE;
+    if (D < 1 || D > DB_MAX_D || num_classes < 1 || num_classes > DB_MAX_CLASSES) return MU_ERR_SHAPE;
+    if (max_inst < 1 || max_inst > INST_MAX_INSTANCES) return MU_ERR_SHAPE;
+    return MU_OK;
+}
+
+static int db_max_tiles(int N, int num_classes) { return N / DB_TR + num_classes; }
+
+// ints per image: perm, pos_of, link, lab [N each]; seg [num_classes + 1]; tiles [2 * max_tiles]; ntiles [1]; first [max_inst]
+extern "C" long mu_dbscan_workspace_bytes(int B, int H, int W, int num_classes, int max_inst) {
+    if (B <= 0 || mu_dbscan_supported(H, W, 1, num_classes, max_inst) != MU_OK) return 0;
+    const long N = (long)H * W;
+    return (long)B * (4 * N + num_classes + 1 + 2 * db_max_tiles((int)N, num_classes) + 1 + max_inst) * (long)sizeof(int);
+}
+
+template <typename T, int DP>
+static int db_sweeps(const DbParams& P, int B, hipStream_t st) {
+    const dim3 grid(P.max_tiles, B);
+    db_sweep_kernel<T, DP, DB_COUNT><<<grid, DB_TR, 0, st>>>(P);
+    MU_CHECK_LAUNCH();
+    db_sweep_kernel<T, DP, DB_UNION><<<grid, DB_TR, 0, st>>>(P);
+    MU_CHECK_LAUNCH();
+    db_sweep_kernel<T, DP, DB_BORDER><<<grid, DB_TR, 0, st>>>(P);
+    MU_CHECK_LAUNCH();
+    return MU_OK;
+}
+
+template <typename T>
+static int db_sweeps_d(const DbParams& P, int B, hipStream_t st) {
+    if (P.D <= 4) return db_sweeps<T, 4>(P, B, st);
+    if (P.D <= 16) return db_sweeps<T, 16>(P, B, st);
+    if (P.D <= 32) return db_sweeps<T, 32>(P, B, st);
+    return db_sweeps<T, 64>(P, B, st);
+}
+
+extern "C" int mu_dbscan_instances(const int* cls, const void* emb, int B, int H, int W, int D, long inner, long outer_stride,
+                                   long c_stride, long p_stride, int dtype, int num_classes, float eps, int min_samples, int max_inst,
+                                   int* ids, int* table, float* score, int* count, int* order, void* workspace, long ws_bytes,
+                                   void* stream) {
+    if (!cls || !emb || !ids || !table || !score || !count || !order || !workspace || B <= 0 || H <= 0 || W <= 0 || inner <= 0)
+        return MU_ERR_ARG;
+    if (dtype != MU_F32 && dtype != MU_F16) return MU_ERR_ARG;
+    if (mu_dbscan_supported(H, W, D, num_classes, max_inst) != MU_OK || min_samples < 1 || !(eps > 0.f) || B > 65535) return MU_ERR_SHAPE;
+    if (ws_bytes < mu_dbscan_workspace_bytes(B, H, W, num_classes, max_inst)) return MU_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int N = H * W, PW = inst_pow2(max_inst);
+    DbParams P;
+    P.emb = emb;
+    P.N = N;
+    P.D = D;
+    P.nc = num_classes;
+    P.max_tiles = db_max_tiles(N, num_classes);
+    P.min_samples = min_samples;
+    P.inner = inner;
+    P.outer_stride = outer_stride;
+    P.c_stride = c_stride;
+    P.p_stride = p_stride;
+    P.eps2 = (double)eps * (double)eps;
+    int* w = (int*)workspace;
+    P.perm = w;
+    P.pos_of = P.perm + (long)B * N;
+    P.link = P.pos_of + (long)B * N;
+    P.lab = P.link + (long)B * N;
+    P.seg = P.lab + (long)B * N;
+    P.tiles = P.seg + (long)B * (num_classes + 1);
+    P.ntiles = P.tiles + (long)B * P.max_tiles * 2;
+    int* first = P.ntiles + B;
+    if (!inst_lds_granted()) return MU_ERR_LAUNCH;
+    const size_t lds_group = (size_t)(DB_GROUP_WAVES + 3) * num_classes * sizeof(int);
+    db_group_kernel<<<B, DB_GROUP_THREADS, lds_group, st>>>(cls, P);
+    MU_CHECK_LAUNCH();
+    const int rc = dtype == MU_F16 ? db_sweeps_d<h16>(P, B, st) : db_sweeps_d<float>(P, B, st);
+    if (rc != MU_OK) return rc;
+    const size_t lds_number = (size_t)(max_inst + INST_WAVES) * sizeof(int);
+    db_number_kernel<<<B, INST_THREADS, lds_number, st>>>(P, max_inst, ids, count, first);
+    MU_CHECK_LAUNCH();
+    const size_t lds_stats = (size_t)PW * (5 * sizeof(unsigned) + sizeof(unsigned long long));
+    inst_stats_kernel<<<B, INST_THREADS, lds_stats, st>>>(cls, nullptr, ids, count, first, N, W, max_inst, PW, table, score, order);
+    MU_CHECK_LAUNCH();
+    return MU_OK;
+}

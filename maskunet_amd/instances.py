@@ -7,6 +7,10 @@ map, gathers the per-instance statistics and sorts the scores (mu_instances); no
 
 Class 0 is background, and so is every negative value.  An instance is a maximal 8-connected set of pixels of one non-zero class;
 ids run 1..count within an image, ordered by each instance's first pixel in raster order.
+
+The 3-head model (`UNet(c_in, c_out, embed_dim=16)`) is evaluated differently: evaluate_instances (city_instance.py:451-482) clusters
+the embedding head per predicted class with sklearn's DBSCAN (get_instances_from_embeddings / get_instance_annotations,
+city_instance.py:405-449).  instances_from_embeddings does that on the device (mu_dbscan_instances) and returns the same `Instances`.
 """
 from __future__ import annotations
 
@@ -28,7 +32,7 @@ class Instances:
     classes: torch.Tensor        # int32 [B,H,W]   class map (arg-max of the logits, or the labels)
     ids: torch.Tensor            # int32 [B,H,W]   0 = background, else the instance id
     table: torch.Tensor          # int32 [B,max_instances,8]   TABLE_COLUMNS; row k-1 describes id k
-    scores: torch.Tensor         # fp32  [B,max_instances]     mean probability of the instance's class over its pixels
+    scores: torch.Tensor         # fp32  [B,max_instances]     mean probability of the instance's class over its pixels (1.0: labels, embeddings)
     count: torch.Tensor          # int32 [B]
     order: torch.Tensor          # int32 [B,max_instances]     ids by descending score (ties: ascending id), padded with 0
     prob: torch.Tensor | None = None     # fp32 [B,H,W] probability of the arg-max class (None for label input)
@@ -122,3 +126,64 @@ def generate_instance_mask(semantic_mask, max_instances=1024):
     out = torch.gather(lut, 1, ids.clamp(max=max_instances))
     out = torch.where(over, torch.full_like(out, -1), out).view_as(r.ids)
     return out[0] if squeeze else out
+
+
+def instances_from_embeddings(semantic, embeddings, eps=0.5, min_samples=5, temperature=0.5, max_instances=1024, num_classes=None):
+    """evaluate_instances' post-processing of the 3-head model (city_instance.py:459-475): per image and per class c >= 1,
+    DBSCAN(eps, min_samples) over the embeddings of the class's pixels; ids run over (class ascending, clusters by their lowest core
+    point), noise is 0, every score is 1.0 (so `top()` is ascending id, as the reference's stable sort).
+    `semantic`: the logits [B,C,H,W] (class = first arg-max, `prob` = softmax(logits / temperature) of it, num_classes defaults to C)
+    or an int32 / int64 class map [B,H,W] (num_classes required).  `embeddings`: [B,D,H,W], fp32 or fp16, finite.  Untouched module
+    outputs are read through the NHWC tensors they were converted from.  Never synchronises."""
+    if embeddings.dim() != 4 or not embeddings.is_cuda or not semantic.is_cuda:
+        raise RuntimeError("instances_from_embeddings expects the module outputs on the GPU: semantic [B,C,H,W] or [B,H,W], embeddings [B,D,H,W]")
+    B, D, H, W = embeddings.shape
+    prob = None
+    if semantic.dim() == 4:
+        if not temperature > 0:
+            raise ValueError("temperature must be positive")
+        if tuple(semantic.shape[0:1] + semantic.shape[2:]) != (B, H, W):
+            raise RuntimeError("semantic and embeddings differ in batch or image size")
+        C = semantic.shape[1]
+        num_classes = C if num_classes is None else int(num_classes)
+        M = B * H * W
+        src = _nhwc_source(semantic)
+        if src is not None and src[0].is_contiguous():
+            x = src[0].detach()
+            inner, outer, cs, ps = M, 0, 1, x.shape[-1]
+        else:
+            x = semantic.detach().contiguous()
+            inner, outer, cs, ps = H * W, C * H * W, H * W, 1
+        classes = torch.empty((B, H, W), dtype=torch.int32, device=x.device)
+        prob = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
+        call("mu_argmax_prob", ptr(x), M, C, inner, outer, cs, ps, 1.0 / float(temperature), ptr(classes), ptr(prob), dt(x), stream())
+    else:
+        if semantic.dim() != 3 or semantic.dtype not in (torch.int64, torch.int32) or tuple(semantic.shape) != (B, H, W):
+            raise RuntimeError("semantic must be the logits [B,C,H,W] or an int64 / int32 class map [B,H,W] of the embeddings' size")
+        if num_classes is None:
+            raise ValueError("num_classes is required with a class map")
+        num_classes = int(num_classes)
+        classes = semantic.to(torch.int32).contiguous()
+    lib = _lib.load()
+    max_instances, min_samples = int(max_instances), int(min_samples)
+    if lib.mu_dbscan_supported(H, W, D, num_classes, max_instances) != 0 or min_samples < 1 or not eps > 0:
+        raise RuntimeError("maskunet_amd: embedding instances need H*W <= 65536, 1 <= D <= 64, 1 <= num_classes <= 1024, "
+                           f"1 <= max_instances <= 4096, min_samples >= 1, eps > 0; got {H}x{W}, D={D}, {num_classes} classes, "
+                           f"{max_instances}, {min_samples}, {eps}")
+    src = _nhwc_source(embeddings)
+    if src is not None and src[0].is_contiguous():
+        e = src[0].detach()
+        inner, outer, cs, ps = B * H * W, 0, 1, e.shape[-1]
+    else:
+        e = embeddings.detach().contiguous()
+        inner, outer, cs, ps = H * W, D * H * W, H * W, 1
+    dev = e.device
+    ids = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    table = torch.empty((B, max_instances, 8), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, max_instances), dtype=torch.float32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    order = torch.empty((B, max_instances), dtype=torch.int32, device=dev)
+    ws = torch.empty(lib.mu_dbscan_workspace_bytes(B, H, W, num_classes, max_instances), dtype=torch.uint8, device=dev)
+    call("mu_dbscan_instances", ptr(classes), ptr(e), B, H, W, D, inner, outer, cs, ps, dt(e), num_classes, float(eps), min_samples,
+         max_instances, ptr(ids), ptr(table), ptr(scores), ptr(count), ptr(order), ptr(ws), ws.numel(), stream())
+    return Instances(classes, ids, table, scores, count, order, prob)
