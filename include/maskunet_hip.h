@@ -452,6 +452,38 @@ int mu_dbscan_supported(int H, int W, int D, int num_classes, int max_inst);
 int mu_dbscan_instances(const int* cls, const void* emb, int B, int H, int W, int D, long inner, long outer_stride, long c_stride,
                         long p_stride, int dtype, int num_classes, float eps, int min_samples, int max_inst, int* ids, int* table,
                         float* score, int* count, int* order, void* workspace, long ws_bytes, void* stream);
+/* Instance matching: what evaluate_instances / evaluate_panoptic_metrics (ade_panoptic.py:520-586, city_instance.py:451-500) hand to
+ * pycocotools and panopticapi, restated from the published algorithms (COCOeval.evaluateImg, maskUtils.iou, panopticapi's
+ * pq_compute_single_core) on id maps; no RLE.  Not pinned to those packages.
+ * mu_instance_pairs: pred_ids, gt_ids int32 [B,H,W] (the `ids` of mu_instances / mu_dbscan_instances, or any id maps: regions need not
+ * be connected); ids outside 1..max_inst_* count as 0.  pairs int32 [B,H*W,3]: every (p, g, intersection) with p >= 1, g >= 0 (g = 0:
+ * the pixels of p on no ground truth) and intersection > 0, sorted by (p, g); n_pairs [B] rows are used, the rest is zero.  H*W rows can
+ * never overflow.  Integer arithmetic only: bit-identical from run to run. */
+int mu_instance_pairs_supported(int H, int W, int max_inst_pred, int max_inst_gt);
+long mu_instance_pairs_workspace_bytes(int B, int H, int W, int max_inst_pred, int max_inst_gt);
+int mu_instance_pairs(const int* pred_ids, const int* gt_ids, int B, int H, int W, int max_inst_pred, int max_inst_gt, int* pairs,
+                      int* n_pairs, void* workspace, long ws_bytes, void* stream);
+/* mu_instance_match: pred_table / pred_score / pred_order / pred_count and gt_table / gt_count as mu_instances writes them
+ * ([B,max_inst,8], [B,max_inst], [B]).  Row k < K of the outputs is the detection pred_order[b][k] (K <= max_inst_pred: the reference's
+ * [:max_queries]).  It is evaluated iff its id is in 1..min(count, max_inst_pred), its class in 1..num_classes-1 and fewer than max_dets
+ * earlier rows of the image have that class; a ground truth takes part iff its id is in 1..min(count, max_inst_gt) and its class in
+ * 1..num_classes-1, every other ground-truth pixel is void.  thr: T thresholds in (0, 1], fp64, on the HOST (copied into the launch).
+ *   det_valid, det_class int32 [B,K], det_score fp32 [B,K];  gt_per_class int32 [B,num_classes];
+ *   det_gt int32 [B,T,K], det_iou fp64 [B,T,K]: COCO's greedy matching per (image, class, threshold): for each detection in order, of the
+ *     ground truths of its class not yet matched at this threshold the one with the largest iou >= min(t, 1 - 1e-10), the later
+ *     (higher id) of equal ones; iou = double(i) / double(a_p + a_g - i), one correctly rounded division.  0 = no match;
+ *   pq_gt int32, pq_iou fp64, pq_fp int32 [B,K]: the ground truth of the same class with double(i) / double(a_p + a_g - i - v_p) > 0.5,
+ *     v_p = the detection's overlap with void (at most one exists); pq_fp = 1 for an unmatched detection unless v_p / a_p > 0.5;
+ *   overflow int32 [B]: a count exceeds its max_inst, the results of that image are unspecified.
+ * Rows that are not evaluated are zero; every output byte is written.  H*W <= 65536, 1 <= max_inst_* <= 4096, 1 <= num_classes <= 1024,
+ * 1 <= K <= max_inst_pred, max_dets >= 1, 1 <= T <= 32, else MU_ERR_SHAPE.  The *_supported / *_workspace_bytes queries are host only. */
+int mu_instance_match_supported(int H, int W, int max_inst_pred, int max_inst_gt, int num_classes, int K, int max_dets, int T);
+long mu_instance_match_workspace_bytes(int B, int K);
+int mu_instance_match(const int* pairs, const int* n_pairs, const int* pred_table, const float* pred_score, const int* pred_order,
+                      const int* pred_count, const int* gt_table, const int* gt_count, int B, int H, int W, int max_inst_pred,
+                      int max_inst_gt, int num_classes, int K, int max_dets, const double* thr, int T, int* det_valid, int* det_class,
+                      float* det_score, int* det_gt, double* det_iou, int* gt_per_class, int* pq_gt, double* pq_iou, int* pq_fp,
+                      int* overflow, void* workspace, long ws_bytes, void* stream);
 /* f4: uint8 HWC image bytes [npix, C] -> [0,1] floats in the NHWC compute layout [npix, Cp] (ToTensor, ade_semantic.py:85) */
 int mu_u8_to_nhwc(const unsigned char* src, void* dst, long npix, int C, int Cp, int dtype, void* stream);
 /* f4, resize half: the sample preparation of the reference datasets on the device.  src: decoded image bytes [B][Hs][Ws][C] (C <= 4, as

@@ -9,6 +9,7 @@ from .modules import (ConvBlock, DoubleConv, Down, DownSample, InstanceUNet, Mas
 from .dp import DataParallel, shard_batch
 from .losses import CrossEntropyLoss, InstanceContrastiveLoss, cross_entropy, mean_iou, pixel_cross_entropy_nhwc
 from .instances import Instances, generate_instance_mask, instances_from_embeddings, instances_from_labels, predict_instances
+from .matching import InstanceAP, Matches, PanopticQuality, match_instances
 from .ops import resize_labels_u8, resize_u8_to_nhwc
 from .optim import FusedAdamW
 from .graph import GraphedStep
@@ -18,5 +19,6 @@ __all__ = ["ConvBlock", "DownSample", "UpSample", "Mask2FormerAttention", "UNet"
            "MaskAttention", "OutConv", "set_default_compute_dtype", "DataParallel", "shard_batch", "pixel_cross_entropy_nhwc",
            "mean_iou", "InstanceContrastiveLoss", "FusedAdamW", "CrossEntropyLoss", "cross_entropy", "GraphedStep",
            "resize_u8_to_nhwc", "resize_labels_u8", "set_float32_matmul_precision", "get_float32_matmul_precision", "predict_instances",
-           "instances_from_labels", "generate_instance_mask", "Instances", "instances_from_embeddings"]
+           "instances_from_labels", "generate_instance_mask", "Instances", "instances_from_embeddings", "match_instances", "Matches",
+           "InstanceAP", "PanopticQuality"]
 __version__ = "0.1.0"

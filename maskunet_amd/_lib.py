@@ -103,6 +103,12 @@ SIGNATURES = {
     "mu_dbscan_workspace_bytes": (L, [I, I, I, I, I]),
     "mu_dbscan_supported": (I, [I, I, I, I, I]),
     "mu_dbscan_instances": (I, [P, P, I, I, I, I, L, L, L, L, I, I, F, I, I, P, P, P, P, P, P, L, P]),
+    "mu_instance_pairs_supported": (I, [I, I, I, I]),
+    "mu_instance_pairs_workspace_bytes": (L, [I, I, I, I, I]),
+    "mu_instance_pairs": (I, [P, P, I, I, I, I, I, P, P, P, L, P]),
+    "mu_instance_match_supported": (I, [I, I, I, I, I, I, I, I]),
+    "mu_instance_match_workspace_bytes": (L, [I, I]),
+    "mu_instance_match": (I, [P] * 8 + [I] * 8 + [P, I] + [P] * 10 + [P, L, P]),
     "mu_u8_to_nhwc": (I, [P, P, L, I, I, I, P]),
     "mu_adamw_chunk": (I, []),
     "mu_adamw_multi": (I, [P, P, P, I, I, F, F, F, F, F, F, P, P, I, P, P]),

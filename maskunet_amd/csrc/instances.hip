@@ -861,3 +861,385 @@ extern "C" int mu_dbscan_instances(const int* cls, const void* emb, int B, int H
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
+
+// ------------------------------------------------------------------------------------------
+// Instance matching: the second half of evaluate_instances / evaluate_panoptic_metrics, restated from the published
+// algorithms (COCOeval.evaluateImg, maskUtils.iou, panopticapi's pq_compute_single_core) on id maps instead of RLE masks.
+//   mu_instance_pairs   the intersection counts of two id maps as a table sorted by (pred id, gt id);
+//   mu_instance_match   COCO's greedy matching per (image, class, threshold) and the panoptic IoU > 0.5 matching over that table.
+//
+// Pair table: one workgroup per image, no sort and no hash.  A bitmap over (pred id, gt id) IS the sorted set: bit g of row p - 1 says
+// that the pair occurs, and the number of set bits before it is the pair's row in the output.
+//   1. zero the bitmap; every run of equal (p, g) inside a 64-pixel chunk (one ballot, as inst_stats_kernel) sets its bit: atomicOr;
+//   2. exclusive scan of the words' popcounts -> pre[]; every set bit writes its (p, g, 0) row; rows past the total are zeroed;
+//   3. the runs again: row = pre[word] + popcount(bits below), atomicAdd of the run length.
+// Integer atomics only, and neither the set of bits nor the sums depend on their order: bit-identical from run to run.  At most one
+// new pair per pixel, so H*W rows always suffice.
+// ------------------------------------------------------------------------------------------
+#define MATCH_MAX_CLASSES 1024
+#define MATCH_MAX_T 32
+
+__device__ __forceinline__ unsigned pair_ld(const unsigned* p) {      // written by atomics of other waves: read at the L2
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// key of pixel i: (p << 13) | g with ids outside 1..max folded to 0; 0 past the image
+__device__ __forceinline__ unsigned pair_key(const int* __restrict__ pred, const int* __restrict__ gt, int i, int N, int mp, int mg) {
+    if (i >= N) return 0u;
+    int p = pred[i], g = gt[i];
+    if (p < 1 || p > mp) p = 0;
+    if (g < 1 || g > mg) g = 0;
+    return ((unsigned)p << 13) | (unsigned)g;
+}
+
+__global__ __launch_bounds__(INST_THREADS) void inst_pairs_kernel(const int* __restrict__ pred_all, const int* __restrict__ gt_all, int N,
+                                                                   int mp, int mg, int GW, unsigned* __restrict__ bits_all,
+                                                                   unsigned* __restrict__ pre_all, int* __restrict__ pairs_all,
+                                                                   int* __restrict__ n_pairs) {
+    __shared__ unsigned wave_total[INST_WAVES];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int* pred = pred_all + (long)b * N;
+    const int* gt = gt_all + (long)b * N;
+    const int NW = mp * GW;                           // at most 4096 * 129 words
+    unsigned* bits = bits_all + (long)b * NW;
+    unsigned* pre = pre_all + (long)b * NW;
+    int* pairs = pairs_all + (long)b * N * 3;
+
+    for (int w = tid; w < NW; w += INST_THREADS) bits[w] = 0u;
+    __syncthreads();
+
+    // 1. which pairs occur
+    for (int base = wave * 64; base < N; base += INST_THREADS) {
+        const unsigned key = pair_key(pred, gt, base + lane, N, mp, mg);
+        const unsigned prev = (unsigned)__shfl_up((int)key, 1);
+        if ((key >> 13) != 0u && (lane == 0 || key != prev)) {
+            const unsigned g = key & 0x1fffu;
+            atomicOr(&bits[((key >> 13) - 1u) * GW + (g >> 5)], 1u << (g & 31u));
+        }
+    }
+    __syncthreads();
+
+    // 2. rows: wave v owns the words [v * seg, (v + 1) * seg)
+    const int seg = ((NW + INST_WAVES * 64 - 1) / (INST_WAVES * 64)) * 64;
+    const int lo = min(NW, wave * seg), hi = min(NW, lo + seg);
+    unsigned mine = 0;
+    for (int base = lo; base < hi; base += 64) {
+        const int w = base + lane;
+        mine += w < hi ? __popc(pair_ld(bits + w)) : 0;
+    }
+    for (int o = 32; o > 0; o >>= 1) mine += (unsigned)__shfl_xor((int)mine, o);
+    if (lane == 0) wave_total[wave] = mine;
+    __syncthreads();
+    unsigned running = 0, total = 0;
+    for (int v = 0; v < INST_WAVES; ++v) {
+        const unsigned t = wave_total[v];
+        if (v < wave) running += t;
+        total += t;
+    }
+    if (tid == 0) n_pairs[b] = (int)total;
+    for (int base = lo; base < hi; base += 64) {
+        const int w = base + lane;
+        unsigned word = w < hi ? pair_ld(bits + w) : 0u;
+        const unsigned cnt = __popc(word);
+        unsigned incl = cnt;
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned u = (unsigned)__shfl_up((int)incl, o);
+            if (lane >= o) incl += u;
+        }
+        unsigned row = running + incl - cnt;
+        if (w < hi) pre[w] = row;
+        const int p = w / GW + 1, g0 = (w % GW) * 32;
+        while (word) {
+            const int bit = __ffs((int)word) - 1;
+            word &= word - 1u;
+            int* r = pairs + (long)row * 3;
+            r[0] = p;
+            r[1] = g0 + bit;
+            r[2] = 0;
+            ++row;
+        }
+        running += (unsigned)__shfl((int)incl, 63);
+    }
+    for (long e = (long)total * 3 + tid; e < (long)N * 3; e += INST_THREADS) pairs[e] = 0;
+    __syncthreads();
+
+    // 3. the counts
+    for (int base = wave * 64; base < N; base += INST_THREADS) {
+        const unsigned key = pair_key(pred, gt, base + lane, N, mp, mg);
+        const unsigned prev = (unsigned)__shfl_up((int)key, 1);
+        const bool edge = lane == 0 || key != prev;
+        const unsigned long long edges = __ballot(edge);
+        if (edge && (key >> 13) != 0u) {
+            const unsigned long long higher = lane == 63 ? 0ull : (edges >> (lane + 1));
+            const int len = higher ? __ffsll((long long)higher) : 64 - lane;
+            const unsigned g = key & 0x1fffu;
+            const unsigned w = ((key >> 13) - 1u) * GW + (g >> 5);
+            const unsigned row = pair_ld(pre + w) + __popc(pair_ld(bits + w) & ((1u << (g & 31u)) - 1u));
+            atomicAdd(&pairs[(long)row * 3 + 2], len);
+        }
+    }
+}
+
+static int pair_row_words(int max_inst_gt) { return (max_inst_gt + 1 + 31) >> 5; }      // bits 0..max_inst_gt
+
+extern "C" int mu_instance_pairs_supported(int H, int W, int max_inst_pred, int max_inst_gt) {
+    if (H <= 0 || W <= 0 || (long)H * W > INST_MAX_PIXELS) return MU_ERR_SHAPE;
+    if (max_inst_pred < 1 || max_inst_pred > INST_MAX_INSTANCES || max_inst_gt < 1 || max_inst_gt > INST_MAX_INSTANCES) return MU_ERR_SHAPE;
+    return MU_OK;
+}
+
+// per image: unsigned bits[max_inst_pred][words], unsigned pre[max_inst_pred][words]
+extern "C" long mu_instance_pairs_workspace_bytes(int B, int H, int W, int max_inst_pred, int max_inst_gt) {
+    if (B <= 0 || mu_instance_pairs_supported(H, W, max_inst_pred, max_inst_gt) != MU_OK) return 0;
+    return (long)B * max_inst_pred * pair_row_words(max_inst_gt) * 2 * (long)sizeof(unsigned);
+}
+
+extern "C" int mu_instance_pairs(const int* pred_ids, const int* gt_ids, int B, int H, int W, int max_inst_pred, int max_inst_gt,
+                                 int* pairs, int* n_pairs, void* workspace, long ws_bytes, void* stream) {
+    if (!pred_ids || !gt_ids || !pairs || !n_pairs || !workspace || B <= 0 || H <= 0 || W <= 0) return MU_ERR_ARG;
+    if (mu_instance_pairs_supported(H, W, max_inst_pred, max_inst_gt) != MU_OK) return MU_ERR_SHAPE;
+    if (ws_bytes < mu_instance_pairs_workspace_bytes(B, H, W, max_inst_pred, max_inst_gt)) return MU_ERR_WORKSPACE;
+    const int GW = pair_row_words(max_inst_gt);
+    unsigned* bits = (unsigned*)workspace;
+    unsigned* pre = bits + (long)B * max_inst_pred * GW;
+    inst_pairs_kernel<<<B, INST_THREADS, 0, (hipStream_t)stream>>>(pred_ids, gt_ids, H * W, max_inst_pred, max_inst_gt, GW, bits, pre,
+                                                                    pairs, n_pairs);
+    MU_CHECK_LAUNCH();
+    return MU_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Matching: one workgroup per image.  Row k of every [B,K] output is the detection order[b][k]; it is evaluated (det_valid) iff its id
+// is one of 1..min(count, max_inst_pred), its class one of 1..num_classes-1 and fewer than max_dets rows before it have that class.
+// A ground truth takes part iff its id is one of 1..min(count, max_inst_gt) and its class one of 1..num_classes-1; the pixels of every
+// other ground-truth id are void.
+//   COCO      one thread per (class, threshold) walks the class's detections in order -- the greedy chain is sequential -- and for each
+//             the detection's rows of the pair table (ascending gt id): iou = double(i) / double(a_p + a_g - i), one correctly rounded
+//             division; a row is skipped if matched at this threshold or iou < best so far (which starts at min(t, 1 - 1e-10)), so of
+//             equal IoUs the later gt wins.  matched[g] holds one bit per threshold: chains of one class share the words, not the bits.
+//   panoptic  one thread per detection: v = its overlap with void, match iff double(i) / double(a_p + a_g - i - v) > 0.5 (at most one),
+//             else a false positive unless double(v) / double(a_p) > 0.5.
+// Dynamic LDS (ints): info[K] (class | rank << 16), list[K] (rows by class, in order), matched[max_inst_gt], ccnt[nc], cstart[nc + 1]:
+// 56 KiB at the limits.
+// ------------------------------------------------------------------------------------------
+struct MatchParams {
+    const int *pairs, *n_pairs, *ptable, *porder, *pcount, *gtable, *gcount;
+    const float* pscore;
+    int N, mp, mg, nc, K, max_dets, T;
+    int *det_valid, *det_class, *det_gt, *gt_per_class, *pq_gt, *pq_fp, *overflow, *dstart;
+    float* det_score;
+    double *det_iou, *pq_iou;
+    double thr[MATCH_MAX_T];                           // by value: nothing to upload, nothing that outlives the call
+};
+
+__global__ __launch_bounds__(INST_THREADS) void inst_match_kernel(const MatchParams P) {
+    extern __shared__ unsigned inst_lds[];
+    const int K = P.K, nc = P.nc, T = P.T;
+    unsigned* info = inst_lds;
+    int* list = (int*)(info + K);
+    unsigned* matched = (unsigned*)(list + K);
+    int* ccnt = (int*)(matched + P.mg);
+    int* cstart = ccnt + nc;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int* pairs = P.pairs + (long)b * P.N * 3;
+    const int n = min(max(P.n_pairs[b], 0), P.N);
+    const int* ptable = P.ptable + (long)b * P.mp * 8;
+    const int* gtable = P.gtable + (long)b * P.mg * 8;
+    const int* porder = P.porder + (long)b * P.mp;
+    const int Kp = min(max(P.pcount[b], 0), P.mp), Kg = min(max(P.gcount[b], 0), P.mg);
+    int* dstart = P.dstart + (long)b * K;
+
+    if (tid == 0) P.overflow[b] = (P.pcount[b] > P.mp || P.gcount[b] > P.mg) ? 1 : 0;
+    for (int c = tid; c < nc; c += INST_THREADS) ccnt[c] = 0;
+    for (int g = tid; g < P.mg; g += INST_THREADS) matched[g] = 0u;
+    __syncthreads();
+    for (int g = tid; g < Kg; g += INST_THREADS) {
+        const int c = gtable[(long)g * 8];
+        if (c >= 1 && c < nc) atomicAdd(&ccnt[c], 1);
+    }
+    for (int k = tid; k < K; k += INST_THREADS) {
+        const int p = porder[k];
+        int c = (p >= 1 && p <= Kp) ? ptable[(long)(p - 1) * 8] : 0;
+        if (c < 1 || c >= nc) c = 0;
+        info[k] = (unsigned)c;
+    }
+    __syncthreads();
+    for (int c = tid; c < nc; c += INST_THREADS) {
+        P.gt_per_class[(long)b * nc + c] = ccnt[c];
+        ccnt[c] = 0;
+    }
+    __syncthreads();
+
+    // rank of every row among the rows of its class (the low half of info[] does not change)
+    for (int k = tid; k < K; k += INST_THREADS) {
+        const unsigned c = info[k] & 0xffffu;
+        unsigned rank = 0xffffu;
+        if (c) {
+            rank = 0;
+            for (int j = 0; j < k; ++j) rank += ((info[j] & 0xffffu) == c);
+            if (rank < (unsigned)P.max_dets) atomicAdd(&ccnt[c], 1);
+            else rank = 0xffffu;
+        }
+        info[k] = c | (rank << 16);
+    }
+    __syncthreads();
+    if (wave == 0) {                                   // cstart = exclusive scan of the evaluated rows per class
+        int carry = 0;
+        for (int base = 0; base < nc; base += 64) {
+            const int c = base + lane;
+            const int v = c < nc ? ccnt[c] : 0;
+            int s = v;
+            for (int o = 1; o < 64; o <<= 1) {
+                const int u = __shfl_up(s, o);
+                if (lane >= o) s += u;
+            }
+            if (c < nc) cstart[c] = carry + s - v;
+            carry += __shfl(s, 63);
+        }
+        if (lane == 0) cstart[nc] = carry;
+    }
+    __syncthreads();
+
+    // per row: the [B,K] outputs, the row's place in its class's list, its first row in the pair table, the panoptic match
+    for (int k = tid; k < K; k += INST_THREADS) {
+        const unsigned c = info[k] & 0xffffu, rank = info[k] >> 16;
+        const bool valid = c != 0u && rank != 0xffffu;
+        const long o = (long)b * K + k;
+        int m_gt = 0, m_fp = 0;
+        double m_iou = 0.0;
+        if (valid) {
+            const int p = porder[k];
+            list[cstart[c] + (int)rank] = k;
+            int lo = 0, hi = n;                        // lower bound of p in the pair table
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (pairs[(long)mid * 3] < p) lo = mid + 1;
+                else hi = mid;
+            }
+            dstart[k] = lo;
+            const int a_p = ptable[(long)(p - 1) * 8 + 1];
+            int v = 0;
+            for (int r = lo; r < n && pairs[(long)r * 3] == p; ++r) {
+                const int g = pairs[(long)r * 3 + 1];
+                const int gc = (g >= 1 && g <= Kg) ? gtable[(long)(g - 1) * 8] : 0;
+                if (gc < 1 || gc >= nc) v += pairs[(long)r * 3 + 2];
+            }
+            for (int r = lo; r < n && pairs[(long)r * 3] == p; ++r) {
+                const int g = pairs[(long)r * 3 + 1];
+                if (g < 1 || g > Kg || gtable[(long)(g - 1) * 8] != (int)c) continue;
+                const int i = pairs[(long)r * 3 + 2];
+                const int u = a_p + gtable[(long)(g - 1) * 8 + 1] - i - v;
+                if (u <= 0) continue;
+                const double iou = (double)i / (double)u;
+                if (iou > 0.5) {
+                    m_gt = g;
+                    m_iou = iou;
+                }
+            }
+            if (!m_gt) m_fp = (a_p > 0 && (double)v / (double)a_p > 0.5) ? 0 : 1;
+            P.det_score[o] = P.pscore[(long)b * P.mp + p - 1];
+        } else {
+            dstart[k] = 0;
+            P.det_score[o] = 0.f;
+            for (int t = 0; t < T; ++t) {
+                P.det_gt[((long)b * T + t) * K + k] = 0;
+                P.det_iou[((long)b * T + t) * K + k] = 0.0;
+            }
+        }
+        P.det_valid[o] = valid ? 1 : 0;
+        P.det_class[o] = valid ? (int)c : 0;
+        P.pq_gt[o] = m_gt;
+        P.pq_iou[o] = m_iou;
+        P.pq_fp[o] = m_fp;
+    }
+    __syncthreads();
+
+    // COCO: chain q = (class, threshold); the T chains of a class sit in neighbouring lanes and read the same rows
+    for (int q = tid; q < (nc - 1) * T; q += INST_THREADS) {
+        const int c = 1 + q / T, t = q % T;
+        const double floor_iou = fmin(P.thr[t], 1.0 - 1e-10);
+        for (int s = cstart[c]; s < cstart[c + 1]; ++s) {
+            const int k = list[s];
+            const int p = porder[k];
+            const int a_p = ptable[(long)(p - 1) * 8 + 1];
+            double best = floor_iou;
+            int best_g = 0;
+            for (int r = dstart[k]; r < n && pairs[(long)r * 3] == p; ++r) {
+                const int g = pairs[(long)r * 3 + 1];
+                if (g < 1 || g > Kg || gtable[(long)(g - 1) * 8] != c) continue;
+                if ((*(volatile unsigned*)&matched[g - 1] >> t) & 1u) continue;
+                const int i = pairs[(long)r * 3 + 2];
+                const int u = a_p + gtable[(long)(g - 1) * 8 + 1] - i;
+                if (u <= 0) continue;
+                const double iou = (double)i / (double)u;
+                if (iou < best) continue;
+                best = iou;
+                best_g = g;
+            }
+            if (best_g) atomicOr(&matched[best_g - 1], 1u << t);
+            P.det_gt[((long)b * T + t) * K + k] = best_g;
+            P.det_iou[((long)b * T + t) * K + k] = best_g ? best : 0.0;
+        }
+    }
+}
+
+extern "C" int mu_instance_match_supported(int H, int W, int max_inst_pred, int max_inst_gt, int num_classes, int K, int max_dets, int T) {
+    if (mu_instance_pairs_supported(H, W, max_inst_pred, max_inst_gt) != MU_OK) return MU_ERR_SHAPE;
+    if (num_classes < 1 || num_classes > MATCH_MAX_CLASSES || T < 1 || T > MATCH_MAX_T) return MU_ERR_SHAPE;
+    if (K < 1 || K > max_inst_pred || max_dets < 1) return MU_ERR_SHAPE;
+    return MU_OK;
+}
+
+// int first_row[B][K]: where each detection's rows start in the pair table
+extern "C" long mu_instance_match_workspace_bytes(int B, int K) {
+    if (B <= 0 || K < 1 || K > INST_MAX_INSTANCES) return 0;
+    return (long)B * K * (long)sizeof(int);
+}
+
+extern "C" int mu_instance_match(const int* pairs, const int* n_pairs, const int* pred_table, const float* pred_score,
+                                 const int* pred_order, const int* pred_count, const int* gt_table, const int* gt_count, int B, int H,
+                                 int W, int max_inst_pred, int max_inst_gt, int num_classes, int K, int max_dets, const double* thr,
+                                 int T, int* det_valid, int* det_class, float* det_score, int* det_gt, double* det_iou,
+                                 int* gt_per_class, int* pq_gt, double* pq_iou, int* pq_fp, int* overflow, void* workspace,
+                                 long ws_bytes, void* stream) {
+    if (!pairs || !n_pairs || !pred_table || !pred_score || !pred_order || !pred_count || !gt_table || !gt_count || !thr || !det_valid ||
+        !det_class || !det_score || !det_gt || !det_iou || !gt_per_class || !pq_gt || !pq_iou || !pq_fp || !overflow || !workspace ||
+        B <= 0 || H <= 0 || W <= 0)
+        return MU_ERR_ARG;
+    if (mu_instance_match_supported(H, W, max_inst_pred, max_inst_gt, num_classes, K, max_dets, T) != MU_OK) return MU_ERR_SHAPE;
+    for (int t = 0; t < T; ++t)
+        if (!(thr[t] > 0.0 && thr[t] <= 1.0)) return MU_ERR_ARG;      // a threshold of 0 would match pairs that do not overlap
+    if (ws_bytes < mu_instance_match_workspace_bytes(B, K)) return MU_ERR_WORKSPACE;
+    MatchParams P;
+    P.pairs = pairs;
+    P.n_pairs = n_pairs;
+    P.ptable = pred_table;
+    P.pscore = pred_score;
+    P.porder = pred_order;
+    P.pcount = pred_count;
+    P.gtable = gt_table;
+    P.gcount = gt_count;
+    P.N = H * W;
+    P.mp = max_inst_pred;
+    P.mg = max_inst_gt;
+    P.nc = num_classes;
+    P.K = K;
+    P.max_dets = max_dets;
+    P.T = T;
+    P.det_valid = det_valid;
+    P.det_class = det_class;
+    P.det_score = det_score;
+    P.det_gt = det_gt;
+    P.det_iou = det_iou;
+    P.gt_per_class = gt_per_class;
+    P.pq_gt = pq_gt;
+    P.pq_iou = pq_iou;
+    P.pq_fp = pq_fp;
+    P.overflow = overflow;
+    P.dstart = (int*)workspace;
+    for (int t = 0; t < MATCH_MAX_T; ++t) P.thr[t] = t < T ? thr[t] : 1.0;
+    const size_t lds = (size_t)(2 * K + max_inst_gt + 2 * num_classes + 1) * sizeof(int);      // 57348 bytes at the limits: no grant needed
+    inst_match_kernel<<<B, INST_THREADS, lds, (hipStream_t)stream>>>(P);
+    MU_CHECK_LAUNCH();
+    return MU_OK;
+}
