@@ -484,6 +484,34 @@ int mu_instance_match(const int* pairs, const int* n_pairs, const int* pred_tabl
                       int max_inst_gt, int num_classes, int K, int max_dets, const double* thr, int T, int* det_valid, int* det_class,
                       float* det_score, int* det_gt, double* det_iou, int* gt_per_class, int* pq_gt, double* pq_iou, int* pq_fp,
                       int* overflow, void* workspace, long ws_bytes, void* stream);
+/* COCO run-length masks: what mask_to_rle / maskUtils.encode make of every prediction (city_instance.py:399-403, coco_instance.py:351,397)
+ * and annToMask (coco_instance.py:63) reads, restated from the published maskApi.c (rleEncode, rleDecode, rleToString, rleArea).
+ * Format.  A mask [H,W] is read COLUMN-major: position j = x * H + y, N = H * W.  counts = the lengths of alternating runs, starting with
+ * a run of zeros (which may be 0 long): with the boundaries b_0 < .. < b_{m-1} (m even; the positions where the value changes, N included
+ * if the mask ends in a one) counts = [b_0, b_1 - b_0, ..], closed by N - b_{m-1} iff b_{m-1} < N; an empty mask is [N].  area = the sum
+ * of the odd-indexed counts.  String: count i contributes x = counts[i], for i > 2 x = counts[i] - counts[i-2], as the characters
+ * 48 + (c | 0x20 if more), c = x & 0x1f, x >>= 5 (arithmetic), more = (c & 0x10) ? x != -1 : x != 0, until more is false.
+ * mu_rle_encode: ids int32 [B,H,W] (any id map: it partitions the image, so all rows of an image are encoded in one pass over it);
+ * sel int32 [B,K]: row k encodes the mask ids == sel[b][k]; 0 or an id outside 1..max_id gives an EMPTY row (no counts, no characters,
+ * area 0), an id that does not occur gives [N].  The non-zero ids of a row of sel are distinct (of equal ones the first row gets the mask,
+ * the others [N]).  With L = 2 * H * W + K:
+ *   offsets int32 [B,K+1], counts int32 [B,L]: row k's counts are counts[b][offsets[b][k] .. offsets[b][k+1]);
+ *   area int32 [B,K];  str_offsets int32 [B,K+1], str_bytes uint8 [B,4*L] (4-byte aligned): row k's string likewise.  Every byte past the
+ *   used part is 0.
+ * L counts and 4 * L characters always suffice: at most two events per boundary, one closing count per row, |x| <= 65536 is 4 characters.
+ * H*W <= 65536, 1 <= K <= 4096, 1 <= max_id <= 65536, else MU_ERR_SHAPE.  Stream-ordered, no host synchronisation, integer arithmetic
+ * only: bit-identical from run to run.  The *_supported / *_workspace_bytes queries are host only (0 bytes for unsupported shapes).
+ * mu_rle_decode: offsets int32 [B,K+1] and counts int32 [B,counts_per_image] as above (counts_per_image = L for the output of
+ * mu_rle_encode; annotation files may hold more) -> ids int32 [B,H,W]: the largest k + 1 over the valid rows k whose mask covers the
+ * pixel, else 0 (overlapping rows are legal); valid int32 [B,K] = 1 iff the row's offsets lie in order inside the image's counts, no
+ * count is negative and they sum to exactly H*W.  An invalid or empty row paints nothing.  Parsing strings is host work. */
+int mu_rle_encode_supported(int H, int W, int K, int max_id);
+long mu_rle_encode_workspace_bytes(int B, int H, int W, int K, int max_id);
+int mu_rle_encode(const int* ids, const int* sel, int B, int H, int W, int K, int max_id, int* offsets, int* counts, int* area,
+                  int* str_offsets, unsigned char* str_bytes, void* workspace, long ws_bytes, void* stream);
+int mu_rle_decode_supported(int H, int W, int K);
+int mu_rle_decode(const int* offsets, const int* counts, int B, int H, int W, int K, long counts_per_image, int* ids, int* valid,
+                  void* stream);
 /* f4: uint8 HWC image bytes [npix, C] -> [0,1] floats in the NHWC compute layout [npix, Cp] (ToTensor, ade_semantic.py:85) */
 int mu_u8_to_nhwc(const unsigned char* src, void* dst, long npix, int C, int Cp, int dtype, void* stream);
 /* f4, resize half: the sample preparation of the reference datasets on the device.  src: decoded image bytes [B][Hs][Ws][C] (C <= 4, as

@@ -10,6 +10,7 @@ from .dp import DataParallel, shard_batch
 from .losses import CrossEntropyLoss, InstanceContrastiveLoss, cross_entropy, mean_iou, pixel_cross_entropy_nhwc
 from .instances import Instances, generate_instance_mask, instances_from_embeddings, instances_from_labels, predict_instances
 from .matching import InstanceAP, Matches, PanopticQuality, match_instances
+from .rle import RLEs, decode_rle, encode_rle, rle_counts_from_string, rle_string_from_counts
 from .ops import resize_labels_u8, resize_u8_to_nhwc
 from .optim import FusedAdamW
 from .graph import GraphedStep
@@ -20,5 +21,5 @@ __all__ = ["ConvBlock", "DownSample", "UpSample", "Mask2FormerAttention", "UNet"
            "mean_iou", "InstanceContrastiveLoss", "FusedAdamW", "CrossEntropyLoss", "cross_entropy", "GraphedStep",
            "resize_u8_to_nhwc", "resize_labels_u8", "set_float32_matmul_precision", "get_float32_matmul_precision", "predict_instances",
            "instances_from_labels", "generate_instance_mask", "Instances", "instances_from_embeddings", "match_instances", "Matches",
-           "InstanceAP", "PanopticQuality"]
+           "InstanceAP", "PanopticQuality", "RLEs", "encode_rle", "decode_rle", "rle_counts_from_string", "rle_string_from_counts"]
 __version__ = "0.1.0"

@@ -109,6 +109,11 @@ SIGNATURES = {
     "mu_instance_match_supported": (I, [I, I, I, I, I, I, I, I]),
     "mu_instance_match_workspace_bytes": (L, [I, I]),
     "mu_instance_match": (I, [P] * 8 + [I] * 8 + [P, I] + [P] * 10 + [P, L, P]),
+    "mu_rle_encode_supported": (I, [I, I, I, I]),
+    "mu_rle_encode_workspace_bytes": (L, [I, I, I, I, I]),
+    "mu_rle_encode": (I, [P, P, I, I, I, I, I, P, P, P, P, P, P, L, P]),
+    "mu_rle_decode_supported": (I, [I, I, I]),
+    "mu_rle_decode": (I, [P, P, I, I, I, I, L, P, P, P]),
     "mu_u8_to_nhwc": (I, [P, P, L, I, I, I, P]),
     "mu_adamw_chunk": (I, []),
     "mu_adamw_multi": (I, [P, P, P, I, I, F, F, F, F, F, F, P, P, I, P, P]),

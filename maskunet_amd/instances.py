@@ -63,6 +63,13 @@ class Instances:
                         "score": float(scores[k - 1]), "mask": (ids == k).numpy()})
         return out
 
+    def rle(self, max_queries=None):
+        """The COCO run-length masks (maskunet_amd.rle.RLEs) of the reference's sorted(...)[:max_queries]: row k of image b is the
+        instance order[b, k], the rows past an image's instances are empty.  Encoded on the device; never synchronises."""
+        from .rle import encode_rle
+        sel = self.order if max_queries is None else self.order[:, :max_queries]
+        return encode_rle(self.ids, sel, max_id=self.order.shape[1])
+
 
 def _label(classes, prob, max_instances):
     B, H, W = classes.shape
