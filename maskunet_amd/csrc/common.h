@@ -344,6 +344,27 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
 }
+// the integer ones (instances.hip, rle.hip)
+__device__ __forceinline__ unsigned wave_sum(unsigned v) {
+    for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o);
+    return v;
+}
+__device__ __forceinline__ int wave_sum(int v) { return (int)wave_sum((unsigned)v); }
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+__device__ __forceinline__ unsigned wave_min(unsigned v) {
+    for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, o));
+    return v;
+}
+__device__ __forceinline__ unsigned wave_max(unsigned v) {
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o));
+    return v;
+}
 
 // XCD-aware block id: blocks b and b+8 share an XCD (private L2); hand each XCD a contiguous
 // range of logical tiles so that tiles sharing an activation panel hit the same L2.

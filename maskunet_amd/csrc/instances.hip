@@ -9,7 +9,7 @@
 //                 an exclusive scan over root flags.
 //   stats kernel  integer LDS atomics per instance (area, bbox, 2^-24 fixed-point probability sum: order-independent, so scores
 //                 are bit-identical from run to run), class_rank, and a bitonic sort of (score desc, id asc) keys in LDS.
-#include "common.h"
+#include "wave_prims.h"
 
 #define INST_THREADS 1024
 #define INST_WAVES (INST_THREADS / 64)
@@ -205,38 +205,29 @@ __global__ __launch_bounds__(INST_THREADS) void inst_label_kernel(const int* __r
     }
     __syncthreads();
 
-    // 4. ids = exclusive scan of the root flags in raster order: wave v owns pixels [v * seg, (v + 1) * seg)
-    const int seg = ((N + INST_WAVES * 64 - 1) / (INST_WAVES * 64)) * 64;
-    const int lo = wave * seg, hi = min(N, lo + seg);
-    unsigned mine = 0;
+    // 4. ids = exclusive scan of the root flags in raster order, every wave over its segment of the pixels
+    int lo, hi;
+    wave_segment(N, INST_WAVES, wave, lo, hi);
+    unsigned mine = 0, total;
     for (int base = lo; base < hi; base += 64) {
         const int i = base + lane;
         const bool root = i < hi && parent[i] == i && cls[i] > 0;
         mine += __popcll(__ballot(root));
     }
-    if (lane == 0) wave_total[wave] = mine;
-    __syncthreads();
-    unsigned running = 0, total = 0;
-    for (int v = 0; v < INST_WAVES; ++v) {
-        const unsigned t = wave_total[v];
-        if (v < wave) running += t;
-        total += t;
-    }
+    unsigned running = block_exclusive_base(mine, wave_total, lane, wave, INST_WAVES, total);
     if (tid == 0) count[b] = (int)total;
     for (int base = lo; base < hi; base += 64) {
         const int i = base + lane;
         const bool valid = i < hi;
         const bool fg = valid && cls[i] > 0;
         const bool root = fg && parent[i] == i;
-        const unsigned long long mask = __ballot(root);
+        const unsigned id = wave_flag_rank(root, lane, running) + 1u;
         if (root) {
-            const unsigned id = running + __popcll(mask & ((1ull << lane) - 1ull)) + 1u;
             ids[i] = (int)id;
             if (id <= (unsigned)max_inst) first[id - 1] = i;
         } else if (valid && !fg) {
             ids[i] = 0;
         }
-        running += __popcll(mask);
     }
     __syncthreads();                 // the roots' ids (global memory, same workgroup) are visible past this barrier
     for (int i = tid; i < N; i += INST_THREADS) {
@@ -249,22 +240,6 @@ __global__ __launch_bounds__(INST_THREADS) void inst_label_kernel(const int* __r
 // Per-instance statistics, table, score order.  Dynamic LDS, P = max_inst rounded up to a power of two:
 //   unsigned long long acc[P] (fixed-point sums, then the sort keys);  unsigned area[P], xmin[P], ymin[P], xmax[P], ymax[P]
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned wave_min_u(unsigned v) {
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, o));
-    return v;
-}
-__device__ __forceinline__ unsigned wave_max_u(unsigned v) {
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o));
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum_ull(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
-
 __device__ __forceinline__ unsigned long long prob_fixed(float p) {      // round(p * 2^24), two's complement
     return (unsigned long long)(long long)__float2ll_rn(p * 16777216.f);
 }
@@ -311,8 +286,8 @@ __global__ __launch_bounds__(INST_THREADS) void inst_stats_kernel(const int* __r
         const int id0 = __shfl(id, 0);
         if (__ballot(valid && id == id0) == ~0ull) {          // the whole wave inside one instance: one set of atomics per wave
             if (id0 > 0 && id0 <= K) {
-                const unsigned x0 = wave_min_u(x), x1 = wave_max_u(x), y0 = wave_min_u(y), y1 = wave_max_u(y);
-                const unsigned long long qs = wave_sum_ull(q);
+                const unsigned x0 = wave_min(x), x1 = wave_max(x), y0 = wave_min(y), y1 = wave_max(y);
+                const unsigned long long qs = wave_sum(q);
                 if (lane == 0) {
                     const int k = id0 - 1;
                     atomicAdd(&area[k], 64u);
@@ -503,21 +478,12 @@ __global__ __launch_bounds__(DB_GROUP_THREADS) void db_group_kernel(const int* _
     __syncthreads();
 
     // 1. per wave and class: pixels of the wave's raster range [lo, hi).  The counters of a wave are its own: no atomics.
-    const int span = ((N + DB_GROUP_THREADS - 1) / DB_GROUP_THREADS) * 64;
-    const int lo = wave * span, hi = min(N, lo + span);
+    int lo, hi;
+    wave_segment(N, DB_GROUP_WAVES, wave, lo, hi);
     int* mine = wcnt + wave * nc;
     for (int base = lo; base < hi; base += 64) {
-        const int i = base + lane;
-        const int c = i < hi ? cls[i] : 0;
-        const bool fg = c >= 1 && c < nc;
-        unsigned long long rem = __ballot(fg);
-        while (rem) {
-            const int leader = __ffsll((long long)rem) - 1;
-            const int c0 = __shfl(c, leader);
-            const unsigned long long m = __ballot(fg && c == c0);
-            if (lane == leader) mine[c0] += __popcll(m);
-            rem &= ~m;
-        }
+        const int c = base + lane < hi ? cls[base + lane] : 0;
+        wave_sort_chunk<false>(c, c >= 1 && c < nc, lane, mine);
     }
     __syncthreads();
 
@@ -535,27 +501,12 @@ __global__ __launch_bounds__(DB_GROUP_THREADS) void db_group_kernel(const int* _
 
     // 3. wave 0: exclusive scans over the classes of the point counts (segment starts) and of the tile counts
     if (wave == 0) {
-        int carry_n = 0, carry_t = 0;
-        for (int base = 0; base < nc; base += 64) {
-            const int c = base + lane;
-            const int n = c < nc ? cnt[c] : 0;
-            const int t = (n + DB_TR - 1) / DB_TR;
-            int sn = n, st = t;
-            for (int o = 1; o < 64; o <<= 1) {
-                const int un = __shfl_up(sn, o), ut = __shfl_up(st, o);
-                if (lane >= o) { sn += un; st += ut; }
-            }
-            if (c < nc) {
-                start[c] = carry_n + sn - n;
-                toff[c] = carry_t + st - t;
-                seg[c] = carry_n + sn - n;
-            }
-            carry_n += __shfl(sn, 63);
-            carry_t += __shfl(st, 63);
-        }
+        for (int c = lane; c < nc; c += 64) toff[c] = (cnt[c] + DB_TR - 1) / DB_TR;
+        const int n_all = wave_scan_excl_array(cnt, start, nc, lane), t_all = wave_scan_excl_array(toff, toff, nc, lane);
+        for (int c = lane; c < nc; c += 64) seg[c] = start[c];
         if (lane == 0) {
-            seg[nc] = carry_n;
-            P.ntiles[b] = carry_t;
+            seg[nc] = n_all;
+            P.ntiles[b] = t_all;
         }
     }
     __syncthreads();
@@ -577,28 +528,15 @@ __global__ __launch_bounds__(DB_GROUP_THREADS) void db_group_kernel(const int* _
         const int i = base + lane;
         const int c = i < hi ? cls[i] : 0;
         const bool fg = c >= 1 && c < nc;
-        if (i < hi && !fg) pos_of[i] = -1;
-        unsigned long long rem = __ballot(fg);
-        while (rem) {
-            const int leader = __ffsll((long long)rem) - 1;
-            const int c0 = __shfl(c, leader);
-            const unsigned long long m = __ballot(fg && c == c0);
-            const int at = mine[c0];
-            if (fg && c == c0) {
-                const int pos = at + __popcll(m & ((1ull << lane) - 1ull));
-                perm[pos] = i;
-                pos_of[i] = pos;
-            }
-            if (lane == leader) mine[c0] = at + __popcll(m);
-            rem &= ~m;
-        }
+        const int pos = wave_sort_chunk<true>(c, fg, lane, mine);
+        if (fg) perm[pos] = i;
+        if (i < hi) pos_of[i] = fg ? pos : -1;
     }
 }
 
-__device__ __forceinline__ int db_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ int db_find(const int* p, int x) {
     for (;;) {
-        const int q = db_ld(p + x);
+        const int q = mu_ld_agent(p + x);
         if (q == x) return x;
         x = q;                               // links strictly decrease along a chain
     }
@@ -741,28 +679,20 @@ __global__ __launch_bounds__(INST_THREADS) void db_number_kernel(DbParams P, int
     const int nfg = P.seg[(long)b * (P.nc + 1) + P.nc];
 
     for (int k = tid; k < max_inst; k += INST_THREADS) first[k] = 0x7fffffff;
-    const int span = ((nfg + INST_WAVES * 64 - 1) / (INST_WAVES * 64)) * 64;
-    const int lo = wave * span, hi = min(nfg, lo + span);
-    unsigned mine = 0;
+    int lo, hi;
+    wave_segment(nfg, INST_WAVES, wave, lo, hi);
+    unsigned mine = 0, total;
     for (int base = lo; base < hi; base += 64) {
         const int i = base + lane;
         mine += __popcll(__ballot(i < hi && lab[i] == i));
     }
-    if (lane == 0) wave_total[wave] = mine;
-    __syncthreads();
-    unsigned running = 0, total = 0;
-    for (int v = 0; v < INST_WAVES; ++v) {
-        const unsigned t = wave_total[v];
-        if (v < wave) running += t;
-        total += t;
-    }
+    unsigned running = block_exclusive_base(mine, wave_total, lane, wave, INST_WAVES, total);
     if (tid == 0) count[b] = (int)total;
     for (int base = lo; base < hi; base += 64) {
         const int i = base + lane;
         const bool root = i < hi && lab[i] == i;
-        const unsigned long long mask = __ballot(root);
-        if (root) rid[i] = (int)(running + __popcll(mask & ((1ull << lane) - 1ull)) + 1u);
-        running += __popcll(mask);
+        const unsigned id = wave_flag_rank(root, lane, running) + 1u;
+        if (root) rid[i] = (int)id;
     }
     __syncthreads();                 // the roots' ids (global memory, same workgroup) are visible past this barrier
     for (int i = tid; i < N; i += INST_THREADS) {
@@ -879,10 +809,6 @@ extern "C" int mu_dbscan_instances(const int* cls, const void* emb, int B, int H
 #define MATCH_MAX_CLASSES 1024
 #define MATCH_MAX_T 32
 
-__device__ __forceinline__ unsigned pair_ld(const unsigned* p) {      // written by atomics of other waves: read at the L2
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // key of pixel i: (p << 13) | g with ids outside 1..max folded to 0; 0 past the image
 __device__ __forceinline__ unsigned pair_key(const int* __restrict__ pred, const int* __restrict__ gt, int i, int N, int mp, int mg) {
     if (i >= N) return 0u;
@@ -919,34 +845,20 @@ __global__ __launch_bounds__(INST_THREADS) void inst_pairs_kernel(const int* __r
     }
     __syncthreads();
 
-    // 2. rows: wave v owns the words [v * seg, (v + 1) * seg)
-    const int seg = ((NW + INST_WAVES * 64 - 1) / (INST_WAVES * 64)) * 64;
-    const int lo = min(NW, wave * seg), hi = min(NW, lo + seg);
-    unsigned mine = 0;
+    // 2. rows, every wave over its segment of the words (bits[]: written by atomics of other waves)
+    int lo, hi;
+    wave_segment(NW, INST_WAVES, wave, lo, hi);
+    unsigned mine = 0, total;
     for (int base = lo; base < hi; base += 64) {
         const int w = base + lane;
-        mine += w < hi ? __popc(pair_ld(bits + w)) : 0;
+        mine += w < hi ? __popc(mu_ld_agent(bits + w)) : 0;
     }
-    for (int o = 32; o > 0; o >>= 1) mine += (unsigned)__shfl_xor((int)mine, o);
-    if (lane == 0) wave_total[wave] = mine;
-    __syncthreads();
-    unsigned running = 0, total = 0;
-    for (int v = 0; v < INST_WAVES; ++v) {
-        const unsigned t = wave_total[v];
-        if (v < wave) running += t;
-        total += t;
-    }
+    unsigned running = block_exclusive_base(wave_sum(mine), wave_total, lane, wave, INST_WAVES, total);
     if (tid == 0) n_pairs[b] = (int)total;
     for (int base = lo; base < hi; base += 64) {
         const int w = base + lane;
-        unsigned word = w < hi ? pair_ld(bits + w) : 0u;
-        const unsigned cnt = __popc(word);
-        unsigned incl = cnt;
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned u = (unsigned)__shfl_up((int)incl, o);
-            if (lane >= o) incl += u;
-        }
-        unsigned row = running + incl - cnt;
+        unsigned word = w < hi ? mu_ld_agent(bits + w) : 0u;
+        unsigned row = wave_scan_excl((unsigned)__popc(word), lane, running);
         if (w < hi) pre[w] = row;
         const int p = w / GW + 1, g0 = (w % GW) * 32;
         while (word) {
@@ -958,7 +870,6 @@ __global__ __launch_bounds__(INST_THREADS) void inst_pairs_kernel(const int* __r
             r[2] = 0;
             ++row;
         }
-        running += (unsigned)__shfl((int)incl, 63);
     }
     for (long e = (long)total * 3 + tid; e < (long)N * 3; e += INST_THREADS) pairs[e] = 0;
     __syncthreads();
@@ -974,7 +885,7 @@ __global__ __launch_bounds__(INST_THREADS) void inst_pairs_kernel(const int* __r
             const int len = higher ? __ffsll((long long)higher) : 64 - lane;
             const unsigned g = key & 0x1fffu;
             const unsigned w = ((key >> 13) - 1u) * GW + (g >> 5);
-            const unsigned row = pair_ld(pre + w) + __popc(pair_ld(bits + w) & ((1u << (g & 31u)) - 1u));
+            const unsigned row = mu_ld_agent(pre + w) + __popc(mu_ld_agent(bits + w) & ((1u << (g & 31u)) - 1u));
             atomicAdd(&pairs[(long)row * 3 + 2], len);
         }
     }
@@ -1084,19 +995,8 @@ __global__ __launch_bounds__(INST_THREADS) void inst_match_kernel(const MatchPar
     }
     __syncthreads();
     if (wave == 0) {                                   // cstart = exclusive scan of the evaluated rows per class
-        int carry = 0;
-        for (int base = 0; base < nc; base += 64) {
-            const int c = base + lane;
-            const int v = c < nc ? ccnt[c] : 0;
-            int s = v;
-            for (int o = 1; o < 64; o <<= 1) {
-                const int u = __shfl_up(s, o);
-                if (lane >= o) s += u;
-            }
-            if (c < nc) cstart[c] = carry + s - v;
-            carry += __shfl(s, 63);
-        }
-        if (lane == 0) cstart[nc] = carry;
+        const int evaluated = wave_scan_excl_array(ccnt, cstart, nc, lane);
+        if (lane == 0) cstart[nc] = evaluated;
     }
     __syncthreads();
 

@@ -8,15 +8,15 @@
 //   rowmap   the row + 1 of every pixel in COLUMN-MAJOR order (the walk of the format), 16 bits each: all later passes read it coalesced;
 //   events   boundary j (0..N) lies between positions j - 1 and j; where the row changes there, the row left and the row entered get one
 //            event (row, j) each.  A row's events in ascending j ARE its boundaries b_0 < b_1 < ...  They are bucketed by row with the
-//            stable counting sort of db_group_kernel (instances.hip): every wave owns a contiguous range of boundaries and counters of
-//            its own per row (no atomics), the rows of a 64-boundary chunk are peeled off with ballots;
+//            stable counting sort of wave_prims.h (wave_segment, wave_sort_chunk), here with two keys per lane (rle_sort_chunk): every
+//            wave owns a contiguous range of boundaries and counters of its own per row (no atomics);
 //   counts   differences of neighbouring boundaries, one wave per row; the closing count unless the row covers position N - 1;
 //   string   per count the 5-bit groups of rleToString; two scans give the offsets (counts per row, characters per row), a wave scan
 //            the place of every count's characters inside its row.
 // mu_rle_decode: one workgroup per image, one wave per row: the row is checked (sum == N, no negative count), then its odd runs are
 // painted with integer atomicMax of row + 1, so overlapping rows give the same map in any order.
 // Integer arithmetic only: bit-identical from run to run.
-#include "common.h"
+#include "wave_prims.h"
 
 #define RLE_THREADS 512
 #define RLE_WAVES (RLE_THREADS / 64)
@@ -26,32 +26,6 @@
 #define RLE_NONE 0x7fffffff
 
 typedef unsigned short rle_u16;
-
-__device__ __forceinline__ int rle_ld(const int* p) {      // written by atomics of other waves: read at the L2
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// wave 0: dst[i] = sum of src[0..i) for i < n (src == dst is fine); returns the total in every lane
-__device__ __forceinline__ int rle_wave_scan(const int* src, int* dst, int n, int lane) {
-    int carry = 0;
-    for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        const int v = i < n ? src[i] : 0;
-        int s = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(s, o);
-            if (lane >= o) s += u;
-        }
-        if (i < n) dst[i] = carry + s - v;
-        carry += __shfl(s, 63);
-    }
-    return carry;
-}
-
-__device__ __forceinline__ int rle_wave_sum(int v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // characters of one value of the string (rleToString): 5 bits each, bit 4 of the last one is the sign.  |x| <= 65536 (a count or
 // the difference of two) takes at most 4; they are returned packed, first character in the low byte
@@ -90,16 +64,30 @@ struct RleParams {
     int* ws;                                           // per image: int table[max_id + 1], int bnd[2 * N], u16 rowmap[N]
 };
 
-// the rows that change at the boundaries [base, base + 64) of the walk: `leave` / `enter` = row + 1 of the run that ends / starts at
-// boundary base + lane, 0 where there is none.  A row never does both at one boundary.
-__device__ __forceinline__ void rle_events(const rle_u16* rowmap, int N, int j, int hi, int& leave, int& enter) {
-    leave = enter = 0;
-    if (j < hi) {                                      // hi <= N + 1
+// One 64-boundary chunk of the bucketing of the events by row: wave_sort_chunk (wave_prims.h) with two keys per lane.  `leave` / `enter`
+// = row + 1 of the run that ends / starts at boundary j (this lane's; j < hi <= N + 1), 0 where there is none.  A row never does both
+// at one boundary, and both events of a row are peeled in ONE round, so a row's events keep their order along the walk.
+// mine[] = the wave's own counters.  PLACE: the event goes to bnd[ev0[row] + counter + (the row's events in the lanes below)].
+template <bool PLACE>
+__device__ __forceinline__ void rle_sort_chunk(const rle_u16* rowmap, int N, int j, int hi, int lane, rle_u16* mine, const int* ev0,
+                                               int* bnd) {
+    int leave = 0, enter = 0;
+    if (j < hi) {
         const int prev = j > 0 ? rowmap[j - 1] : 0, cur = j < N ? rowmap[j] : 0;
         if (prev != cur) {
             leave = prev;
             enter = cur;
         }
+    }
+    unsigned long long rem_l = __ballot(leave != 0), rem_e = __ballot(enter != 0);
+    while (rem_l | rem_e) {
+        const int r0 = rem_l ? __shfl(leave, __ffsll((long long)rem_l) - 1) : __shfl(enter, __ffsll((long long)rem_e) - 1);
+        const unsigned long long ml = __ballot(leave == r0), me = __ballot(enter == r0);
+        const int at = mine[r0 - 1];
+        if (PLACE && (leave == r0 || enter == r0)) bnd[ev0[r0 - 1] + at + __popcll((ml | me) & lanes_below(lane))] = j;
+        if (lane == 0) mine[r0 - 1] = (rle_u16)(at + __popcll(ml) + __popcll(me));
+        rem_l &= ~ml;
+        rem_e &= ~me;
     }
 }
 
@@ -142,30 +130,19 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_encode_kernel(const RleParams
         const int id = ids[y * W + x];
         int r = 0;
         if (id >= 1 && id <= P.max_id) {
-            const int t = rle_ld(table + id);
+            const int t = mu_ld_agent(table + id);             // written by atomicMin of other waves
             if (t != RLE_NONE) r = t;
         }
         rowmap[j] = (rle_u16)r;
     }
     __syncthreads();                                   // rowmap (global memory, same workgroup) is visible past this barrier
 
-    // events per (wave, row): wave v owns the boundaries [v * span, (v + 1) * span) of 0..N.  A row has at most one event per boundary,
-    // so a wave's counter is at most span <= 8256 and the events of the waves before it at most 7 * span < 65536: 16 bits hold both.
-    const int span = ((N + 1 + RLE_THREADS - 1) / RLE_THREADS) * 64;
-    const int lo = wave * span, hi = min(N + 1, lo + span);
+    // events per (wave, row): every wave over its segment of at most span = 8256 of the boundaries 0..N.  A row has at most one event
+    // per boundary, so a wave's counter is at most span and the events of the waves before it at most 7 * span < 65536: 16 bits hold both.
+    int lo, hi;
+    wave_segment(N + 1, RLE_WAVES, wave, lo, hi);
     rle_u16* mine = wcnt + wave * K;
-    for (int base = lo; base < hi; base += 64) {
-        int leave, enter;
-        rle_events(rowmap, N, base + lane, hi, leave, enter);
-        unsigned long long rem_l = __ballot(leave != 0), rem_e = __ballot(enter != 0);
-        while (rem_l | rem_e) {
-            const int r0 = rem_l ? __shfl(leave, __ffsll((long long)rem_l) - 1) : __shfl(enter, __ffsll((long long)rem_e) - 1);
-            const unsigned long long ml = __ballot(leave == r0), me = __ballot(enter == r0);
-            if (lane == 0) mine[r0 - 1] = (rle_u16)(mine[r0 - 1] + __popcll(ml) + __popcll(me));
-            rem_l &= ~ml;
-            rem_e &= ~me;
-        }
-    }
+    for (int base = lo; base < hi; base += 64) rle_sort_chunk<false>(rowmap, N, base + lane, hi, lane, mine, ev0, bnd);
     __syncthreads();
 
     // per row: exclusive prefix over the waves, events m, counts n = m + 1 unless the row covers the last position
@@ -183,9 +160,9 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_encode_kernel(const RleParams
     }
     __syncthreads();
     if (wave == 0) {
-        rle_wave_scan(m_of, ev0, K, lane);
+        wave_scan_excl_array(m_of, ev0, K, lane);
         for (int k = lane; k < K; k += 64) soff[k] = off[k];                 // n per row, kept until the counts are written
-        const int total = rle_wave_scan(off, off, K, lane);
+        const int total = wave_scan_excl_array(off, off, K, lane);
         for (int k = lane; k < K; k += 64) offsets[k] = off[k];
         if (lane == 0) {
             offsets[K] = total;
@@ -195,20 +172,7 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_encode_kernel(const RleParams
     __syncthreads();
 
     // placement, stable: the same walk
-    for (int base = lo; base < hi; base += 64) {
-        int leave, enter;
-        rle_events(rowmap, N, base + lane, hi, leave, enter);
-        unsigned long long rem_l = __ballot(leave != 0), rem_e = __ballot(enter != 0);
-        while (rem_l | rem_e) {
-            const int r0 = rem_l ? __shfl(leave, __ffsll((long long)rem_l) - 1) : __shfl(enter, __ffsll((long long)rem_e) - 1);
-            const unsigned long long ml = __ballot(leave == r0), me = __ballot(enter == r0);
-            const int at = mine[r0 - 1];
-            if (leave == r0 || enter == r0) bnd[ev0[r0 - 1] + at + __popcll((ml | me) & ((1ull << lane) - 1ull))] = base + lane;
-            if (lane == 0) mine[r0 - 1] = (rle_u16)(at + __popcll(ml) + __popcll(me));
-            rem_l &= ~ml;
-            rem_e &= ~me;
-        }
-    }
+    for (int base = lo; base < hi; base += 64) rle_sort_chunk<true>(rowmap, N, base + lane, hi, lane, mine, ev0, bnd);
     __syncthreads();                                   // bnd (global memory, same workgroup) is visible past this barrier
 
     // counts, area and the characters per row: one wave per row
@@ -223,8 +187,8 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_encode_kernel(const RleParams
             if (i & 1) a += c;
             ch += rle_chars(i > 2 ? c - rle_count(rb, m, N, i - 2) : c, packed);
         }
-        a = rle_wave_sum(a);
-        ch = rle_wave_sum(ch);
+        a = wave_sum(a);
+        ch = wave_sum(ch);
         if (lane == 0) {                               // soff[k] belongs to the wave that owns row k
             area[k] = a;
             soff[k] = ch;
@@ -232,7 +196,7 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_encode_kernel(const RleParams
     }
     __syncthreads();
     if (wave == 0) {
-        const int total = rle_wave_scan(soff, soff, K, lane);
+        const int total = wave_scan_excl_array(soff, soff, K, lane);
         for (int k = lane; k < K; k += 64) str_offsets[k] = soff[k];
         if (lane == 0) {
             str_offsets[K] = total;
@@ -251,14 +215,8 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_encode_kernel(const RleParams
             const int i = base + lane;
             unsigned packed = 0u;
             const int nc = i < n ? rle_chars(rle_value(rb, m, N, i), packed) : 0;
-            int s = nc;
-            for (int o = 1; o < 64; o <<= 1) {
-                const int u = __shfl_up(s, o);
-                if (lane >= o) s += u;
-            }
-            unsigned char* dst = str + carry + s - nc;
+            unsigned char* dst = str + wave_scan_excl(nc, lane, carry);
             for (int q = 0; q < nc; ++q) dst[q] = (unsigned char)(packed >> (8 * q));
-            carry += __shfl(s, 63);
         }
     }
     // the unused tails are zero
@@ -351,23 +309,14 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_decode_kernel(const int* __re
             bad |= (c < 0 || c > N);
             sum += c;
         }
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned l = (unsigned)__shfl_xor((int)(unsigned)sum, o), h = (unsigned)__shfl_xor((int)(unsigned)(sum >> 32), o);
-            sum += (long long)(((unsigned long long)h << 32) | l);
-        }
-        ok = ok && __ballot(bad != 0) == 0ull && sum == (long long)N;
+        ok = ok && __ballot(bad != 0) == 0ull && (long long)wave_sum((unsigned long long)sum) == (long long)N;
         if (lane == 0) valid_all[(long)b * K + k] = ok ? 1 : 0;
         if (!ok) continue;
         int carry = 0;                                  // every count is in 0..N and they sum to N from here on
         for (int base = 0; base < n; base += 64) {
             const int i = base + lane;
             const int c = i < n ? rc[i] : 0;
-            int s = c;
-            for (int o = 1; o < 64; o <<= 1) {
-                const int u = __shfl_up(s, o);
-                if (lane >= o) s += u;
-            }
-            const int start = carry + s - c;
+            const int start = wave_scan_excl(c, lane, carry);
             const bool one = (i & 1) && c > 0;
             if (one && c <= RLE_SHORT_RUN)
                 for (int p = start; p < start + c; ++p) rle_paint(ids, H, W, p, k + 1);
@@ -378,7 +327,6 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_decode_kernel(const int* __re
                 const int s0 = __shfl(start, l), len = __shfl(c, l);
                 for (int p = s0 + lane; p < s0 + len; p += 64) rle_paint(ids, H, W, p, k + 1);
             }
-            carry += __shfl(s, 63);
         }
     }
 }

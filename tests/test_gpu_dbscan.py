@@ -162,6 +162,28 @@ def test_background_only_and_one_pixel_per_class():
     compare(run_dbscan(one, emb, 1024, min_samples=1), ref)                  # the upper end of num_classes
 
 
+@pytest.mark.parametrize("nc", [64, 65, 130])
+def test_class_counts_across_the_scan_turns(nc):
+    """segment starts and tile offsets are scanned 64 classes per turn (csrc/wave_prims.h): points in classes 1, 63, 64 (where it exists)
+    and the last one, every other class empty"""
+    sizes = [0] * (nc - 1)
+    for c, n in ((1, 40), (63, 70), (64, 33), (nc - 1, 50)):
+        if c < nc:
+            sizes[c - 1] = n
+    cls, emb, _, ref = _clustered(60 + nc, 16, 16, 4, tuple(sizes))
+    assert {c for c in (1, 63, 64, nc - 1) if c < nc} == set(ref["table"][0, :ref["count"][0], 0].tolist())
+    compare(run_dbscan(cls[None], emb[None], nc), ref)
+
+
+def test_sixty_four_classes_in_one_chunk_then_one_class():
+    """the counting sort by class: in the first 64-pixel chunk every lane is a class of its own, the second chunk is one class"""
+    emb = (8.0 * np.arange(128, dtype=np.float32)).reshape(1, 8, 16, 1)          # far apart: with min_samples = 1 every pixel is a cluster
+    cls = np.concatenate([1 + np.random.default_rng(8).permutation(64), np.full(64, 7)]).reshape(1, 8, 16).astype(np.int32)
+    ref = R.instances(cls, emb, 65, 0.5, 1, 128)
+    assert ref["count"][0] == 128 and ref["table"][0, :, 0].tolist() == sorted(cls.reshape(-1).tolist())
+    compare(run_dbscan(cls, emb, 65, min_samples=1, max_inst=128), ref)
+
+
 # ------------------------------------------------------------------------------------------------
 # the rules
 @pytest.mark.parametrize("D", [2, 16])

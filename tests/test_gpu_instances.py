@@ -195,6 +195,35 @@ def test_random_maps(name):
 
 
 # ------------------------------------------------------------------------------------------------
+# edges of the shared wave / workgroup helpers (csrc/wave_prims.h): N = 1, 63, 64, 65, 511, 512, 513, 1023, 1024, 1025 pixels, i.e. one
+# 64-lane chunk and one full turn of the 1024 threads (512 in rle.hip), each one short, exact and one over
+EDGE_SHAPES = [(1, 1), (1, 63), (1, 64), (1, 65), (7, 73), (16, 32), (19, 27), (31, 33), (32, 32), (25, 41)]
+
+
+def last_segment_start(n, waves):
+    """first element of the last non-empty wave segment of [0, n): every wave owns ceil(n / (64 waves)) chunks of 64"""
+    seg = -(-n // (waves * 64)) * 64
+    return (n - 1) // seg * seg
+
+
+@pytest.mark.parametrize("shape", EDGE_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_pixel_counts_at_chunk_and_segment_edges(shape):
+    """per-pixel noise (many roots in every chunk).  Image 0: foreground forced on the last pixel and on the first pixel of the last
+    wave's segment; image 1: those two pixels in a class of their own, so each is the root of its component"""
+    H, W = shape
+    N = H * W
+    edge = [last_segment_start(N, 16), N - 1]
+    g = np.random.default_rng(N).integers(0, 3, (2, N)).astype(np.int32)
+    g[0, edge] = np.maximum(g[0, edge], 1)
+    g[1, edge] = 3
+    g = g.reshape(2, H, W)
+    p = grid_prob(g.shape, N)
+    ref = R.instances(g, p.astype(np.float64), 1024)
+    assert (ref["ids"].reshape(2, N)[:, edge] > 0).all() and (ref["table"][1, :, 0] == 3).any()
+    compare(run_instances(g, p, 1024), ref)
+
+
+# ------------------------------------------------------------------------------------------------
 # arg-max pass
 def argmax_case(C, seed=0, M=1000):
     """logits [M, C] on a grid of 1/8 after a ReLU (exact ties at 0 are the common case), with all-zero rows and repeated maxima"""

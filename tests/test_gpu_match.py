@@ -172,6 +172,59 @@ def test_capacity_65536_pairs():
     assert len(set(low["det_gt"][0, 0][hit].tolist())) == hit.sum()          # a ground truth is matched once
 
 
+# edges of the shared wave / workgroup helpers (csrc/wave_prims.h), as in test_gpu_instances.py
+EDGE_SHAPES = [(1, 1), (1, 63), (1, 64), (1, 65), (7, 73), (16, 32), (19, 27), (31, 33), (32, 32), (25, 41)]
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_sides(H, W, C):
+    """runs of three pixels along the raster, the prediction one pixel behind the ground truth.  Image 0: foreground forced on the last
+    pixel and on the first pixel of the last wave's segment (16 waves, 64-pixel chunks), on both sides; image 1: an id of their own there"""
+    N = H * W
+    seg = -(-N // 1024) * 64
+    edge = [(N - 1) // seg * seg, N - 1]
+    rng = np.random.default_rng(N)
+    raw = np.repeat(rng.integers(0, 6, (2, 2, -(-N // 3) + 1)), 3, axis=2)          # [side, image, pixel]
+    raw = np.stack([raw[0, :, 1:N + 1], raw[1, :, :N]])
+    raw[:, 0, edge] = np.maximum(raw[:, 0, edge], 1)
+    raw[:, 1, edge] = 7
+    sides = []
+    for s in range(2):
+        ids = R.compact(raw[s].reshape(2, H, W))
+        n = [int(ids[b].max()) for b in range(2)]
+        cls = [1 + (np.arange(k) * (3 + 2 * s)) % (C - 1) for k in n]
+        sc = [((np.arange(k) * 37) % 64 + 1) / 64.0 for k in n]
+        sides.append(R.side_from_ids(ids, cls, 8, sc if s == 0 else None))
+    return frozen(*sides)
+
+
+@pytest.mark.parametrize("shape", EDGE_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_pixel_counts_at_chunk_and_segment_edges(shape):
+    pred, gt = _edge_sides(*shape, 4)
+    last = shape[0] * shape[1] - 1
+    assert pred["ids"].reshape(2, -1)[:, last].all() and gt["ids"].reshape(2, -1)[:, last].all()
+    ref = R.match(pred, gt, 4)
+    assert ref["n_pairs"].min() >= 1
+    compare(run_match(pred, gt, 4), ref)
+
+
+@pytest.mark.parametrize("nc", [64, 65, 130])
+def test_class_counts_across_the_scan_turns(nc):
+    """the per-class starts are scanned 64 classes per turn: evaluated rows in classes 1, 63, 64 (where it exists) and the last one;
+    4 x 4 segments, the prediction one column to the right: IoU 12 / 20 with the segment of the same class"""
+    yy, xx = np.mgrid[0:16, 0:16]
+    g = (1 + (yy // 4) * 4 + xx // 4)[None].astype(np.int32)
+    p = np.roll(g, 1, axis=2)
+    p[0, :, 0] = 0
+    classes = np.array(sorted({c for c in (1, 63, 64, nc - 1) if c < nc}))
+    cls = [classes[np.arange(16) % len(classes)]]
+    pred, gt = R.side_from_ids(p, cls, 16, [((np.arange(16) * 5) % 8 + 1) / 8.0]), R.side_from_ids(g, cls, 16)
+    ref = R.match(pred, gt, nc)
+    assert set(ref["det_class"][0].tolist()) == set(classes.tolist()) and (ref["det_gt"][0, 0] > 0).all()
+    assert ref["gt_per_class"][0, nc - 1] > 0
+    compare(run_match(pred, gt, nc), ref)
+
+
 def test_disconnected_regions_and_classes_outside_the_range():
     """random_case draws scattered regions and classes from 0..num_classes: class 0 and class num_classes take part on neither side,
     and the pixels of such ground truths are void"""

@@ -137,6 +137,43 @@ def test_random_ids_k_below_equal_above(shape):
         check(ids, sel)
 
 
+# edges of the shared wave / workgroup helpers (csrc/wave_prims.h), as in test_gpu_instances.py
+EDGE_SHAPES = [(1, 1), (1, 63), (1, 64), (1, 65), (7, 73), (16, 32), (19, 27), (31, 33), (32, 32), (25, 41)]
+
+
+@pytest.mark.parametrize("shape", EDGE_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_pixel_counts_at_chunk_and_segment_edges(shape):
+    """per-pixel noise.  The 8 waves share the boundaries 0..N of the column-major walk in 64-boundary chunks: foreground is forced on the
+    last position and on the first position of the last wave's segment (image 0: whatever row is there; image 1: a row of their own)"""
+    H, W = shape
+    N = H * W
+    seg = -(-(N + 1) // 512) * 64
+    ids = blocky(N, 2, H, W, 3, 1)
+    for j in (min(N // seg * seg, N - 1), N - 1):          # position j of the walk = column j // H, line j % H
+        ids[0, j % H, j // H] = max(ids[0, j % H, j // H], 1)
+        ids[1, j % H, j // H] = 4
+    check(ids, np.array([[1, 2, 3, 4], [4, 3, 2, 1]], np.int32))
+
+
+@pytest.mark.parametrize("K", [63, 64, 65, 129])
+def test_row_counts_across_the_scan_turns(K):
+    """offsets and string offsets are scanned 64 rows per turn: a few real rows at the turn's edges, the others empty (image 0: pad
+    rows, no counts at all; image 1: absent ids, one count each)"""
+    ids = blocky(K, 2, 16, 16, 5, 4)
+    sel = np.stack([np.zeros(K, np.int32), 100 + np.arange(K, dtype=np.int32)])
+    for n, k in enumerate(k for k in (0, 62, 63, 64, 128) if k < K):
+        sel[:, k] = 1 + n
+    got = check(ids, sel, max_id=256)
+    assert got["offsets"][1, -1] >= K
+
+
+def test_sixty_four_rows_in_one_chunk():
+    """the counting sort by row: 64 single-pixel rows on an 8 x 8 image, so the one chunk of boundaries holds every row twice"""
+    ids = (1 + np.random.default_rng(6).permutation(64)).reshape(1, 8, 8).astype(np.int32)
+    got = check(ids, np.arange(64, 0, -1, dtype=np.int32)[None])
+    assert got["area"].tolist() == [[1] * 64]
+
+
 def test_one_pixel_image_both_values():
     got = check(np.array([[[3]], [[0]]], np.int32), np.array([[3], [3]], np.int32), max_id=5)
     assert got["counts"][:, :2].tolist() == [[0, 1], [1, 0]] and got["offsets"].tolist() == [[0, 2], [0, 1]]
