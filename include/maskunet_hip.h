@@ -512,6 +512,49 @@ int mu_rle_encode(const int* ids, const int* sel, int B, int H, int W, int K, in
 int mu_rle_decode_supported(int H, int W, int K);
 int mu_rle_decode(const int* offsets, const int* counts, int B, int H, int W, int K, long counts_per_image, int* ids, int* valid,
                   void* stream);
+/* COCO annotations to masks and training targets: what coco_instance.py:52-83, 331-338 do on the host -- annToMask of every annotation
+ * (rleFrPoly per polygon, their union; crowd annotations carry an RLE), cv2.resize(.., INTER_NEAREST) of every mask, torch.sum over them --
+ * from the PARSED segmentation fields.  Restated from the published maskApi.c / coco.py, not pinned to pycocotools; this text is the
+ * specification.  Masks are read column-major: position p = x * h + y, N = h * w.
+ * Polygon (k >= 1 points xy[2j], xy[2j+1], fp64) -> toggle positions (rleFrPoly):
+ *   1. X[j] = (int)(5.0 * xy[2j] + .5), Y[j] likewise (C truncation toward zero); X[k] = X[0], Y[k] = Y[0].
+ *   2. Edge j = 0..k-1: xs, xe, ys, ye = X[j], X[j+1], Y[j], Y[j+1]; dx = |xe - xs|, dy = |ys - ye|;
+ *      flip = (dx >= dy && xs > xe) || (dx < dy && ys > ye); if flip, the two ends are swapped.
+ *   3. dx >= dy: s = (double)(ye - ys) / dx; for d = 0..dx: t = flip ? dx - d : d, u = t + xs, v = (int)((ys + s * t) + .5).
+ *      Otherwise: s = (double)(xe - xs) / dy; for d = 0..dy: t = flip ? dy - d : d, v = t + ys, u = (int)((xs + s * t) + .5).
+ *      So the points run from the edge's original start to its original end; a degenerate edge (dx = dy = 0) emits (xs, ys).  Every
+ *      fp64 operation is rounded on its own, in the order written: NO fused multiply-add.
+ *   4. Over the concatenated points, every i >= 1 with u[i] != u[i-1] (no wrap-around from the last point to the first; the predecessor
+ *      of an edge's first point is the previous edge's last emitted point, by that edge's own formula):
+ *      xd = (double)(u[i] < u[i-1] ? u[i] : u[i] - 1); xd = (xd + .5) / 5.0 - .5; skipped if floor(xd) != xd, xd < 0 or xd > w - 1;
+ *      yd = (double)(v[i] < v[i-1] ? v[i] : v[i-1]); yd = (yd + .5) / 5.0 - .5, clamped to [0, h], then ceil;
+ *      the toggle is a = (int)xd * h + (int)yd.
+ *   5. Position p < N of the polygon's mask is set iff an odd number of toggles is <= p (equal to maskApi's sort, difference and merge
+ *      of zero-length runs).
+ * Annotation a = the polygons ann_poly_offsets[a] .. ann_poly_offsets[a+1] (polygon q = the points poly_offsets[q] .. poly_offsets[q+1]
+ * of xy; a polygon without points adds nothing), OR-ed, or -- where its range of rle_counts, ann_rle_offsets[a] .. ann_rle_offsets[a+1],
+ * is not empty -- one RLE at the image's size, whose toggles are the prefix sums of its counts without the last.  The annotations
+ * img_ann_offsets[b] .. img_ann_offsets[b+1] belong to image b of size (h, w) = sizes[b][0..1] (int32 [B,2], on the device like every
+ * array here): the images of one call have sizes of their own.  A row is INVALID (valid = 0, area = 0, paints nothing) if a coordinate
+ * is not finite or |5 x + .5| >= 2^24; a polygon has more than max_points upsampled points (sum of max(dx, dy) + 1 over its edges); a
+ * count is negative or the counts do not sum to h * w; h < 1, w < 1 or h * w > 2^19; it has polygons and counts; or its offsets are out
+ * of order or out of range.
+ * Outputs at (Ho, Wo), sampled as mu_resize_nearest_u8 does (sx[j] = min(floor(j * (1.0 / (Wo / (double)w))), w - 1), rows likewise;
+ * out[i][j] = mask[sy[i]][sx[j]]):
+ *   cover int64 [B,Ho,Wo]   how many valid annotations of the image cover the pixel (the reference's combined_mask, as the loss takes it);
+ *   ids   int32 [B,Ho,Wo]   the largest (row within the image + 1) among them, else 0: the rule of mu_rle_decode;
+ *   masks uint8 [A,Ho,Wo]   per annotation (may be NULL);  area int32 [A]: the set bits at the ORIGINAL size (rleArea);  valid int32 [A].
+ * Every output byte is written (cover and ids are zeroed here).  Ho * Wo <= 65536 and 1 <= max_points <= 2^21, else MU_ERR_SHAPE
+ * (mu_coco_masks_supported: host only).  B >= 1; A = 0 is legal (xy / rle_counts may be NULL where n_points / n_counts is 0, area / valid
+ * where A is 0).  One workgroup per annotation with both bitmaps in LDS: mu_coco_masks_workspace_bytes is 0 today and `workspace` may be
+ * NULL; the arguments are there so that a build with the union bitmap in global memory keeps this ABI.  Stream-ordered, no host
+ * synchronisation, integer atomics only: bit-identical from run to run. */
+int mu_coco_masks_supported(int Ho, int Wo, int max_points);
+long mu_coco_masks_workspace_bytes(int B, int A, int Ho, int Wo);
+int mu_coco_masks(const double* xy, const int* poly_offsets, const int* ann_poly_offsets, const int* rle_counts, const int* ann_rle_offsets,
+                  const int* img_ann_offsets, const int* sizes, int B, int A, int P, long n_points, long n_counts, int Ho, int Wo,
+                  int max_points, long* cover, int* ids, unsigned char* masks_or_null, int* area, int* valid, void* workspace,
+                  long ws_bytes, void* stream);
 /* f4: uint8 HWC image bytes [npix, C] -> [0,1] floats in the NHWC compute layout [npix, Cp] (ToTensor, ade_semantic.py:85) */
 int mu_u8_to_nhwc(const unsigned char* src, void* dst, long npix, int C, int Cp, int dtype, void* stream);
 /* f4, resize half: the sample preparation of the reference datasets on the device.  src: decoded image bytes [B][Hs][Ws][C] (C <= 4, as

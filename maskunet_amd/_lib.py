@@ -114,6 +114,9 @@ SIGNATURES = {
     "mu_rle_encode": (I, [P, P, I, I, I, I, I, P, P, P, P, P, P, L, P]),
     "mu_rle_decode_supported": (I, [I, I, I]),
     "mu_rle_decode": (I, [P, P, I, I, I, I, L, P, P, P]),
+    "mu_coco_masks_supported": (I, [I, I, I]),
+    "mu_coco_masks_workspace_bytes": (L, [I, I, I, I]),
+    "mu_coco_masks": (I, [P] * 7 + [I, I, I, L, L, I, I, I] + [P] * 6 + [L, P]),
     "mu_u8_to_nhwc": (I, [P, P, L, I, I, I, P]),
     "mu_adamw_chunk": (I, []),
     "mu_adamw_multi": (I, [P, P, P, I, I, F, F, F, F, F, F, P, P, I, P, P]),
