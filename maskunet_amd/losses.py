@@ -124,15 +124,24 @@ class CrossEntropyLoss(torch.nn.Module):
         return cross_entropy(input, target, self.ignore_index, self.grad_scale)
 
 
-def mean_iou(y_pred, y_true, num_classes, smooth=1e-6):
+def mean_iou(y_pred, y_true, num_classes, smooth=1e-6, layout=None):
     """mean_iou of the reference (ade_semantic.py:128-146) on device, no host synchronisation.
-    y_pred: NCHW [B,C,H,W] (the module output) or NHWC channel-padded [B,H,W,Cp]; y_true: int64 [B,H,W]."""
+    y_pred: NCHW [B,C,H,W] (the module output) or NHWC channel-padded [B,H,W,Cp]; y_true: int64 [B,H,W].
+    layout: "nchw" or "nhwc" says which; None guesses from the shape, NCHW first -- a padded NHWC tensor with H == Cp == num_classes
+    (32 classes at 32 x 32) also fits NCHW and is then read with the wrong strides, so pass the layout where that can happen."""
     y_pred = y_pred.contiguous()
     labels = y_true.contiguous().view(-1)
     M = labels.numel()
     if y_pred.dim() != 4:
         raise RuntimeError("mean_iou expects a 4-D prediction tensor")
-    if y_pred.shape[1] == num_classes and y_pred.shape[0] * y_pred.shape[2] * y_pred.shape[3] == M:   # NCHW
+    if layout not in (None, "nchw", "nhwc"):
+        raise ValueError(f'mean_iou: layout must be None, "nchw" or "nhwc", got {layout!r}')
+    fits_nchw = y_pred.shape[1] == num_classes and y_pred.shape[0] * y_pred.shape[2] * y_pred.shape[3] == M
+    fits_nhwc = y_pred.shape[3] >= num_classes and y_pred.shape[0] * y_pred.shape[1] * y_pred.shape[2] == M
+    if (layout == "nchw" and not fits_nchw) or (layout == "nhwc" and not fits_nhwc):
+        raise RuntimeError(f"mean_iou: a {layout} prediction of shape {tuple(y_pred.shape)} does not match {num_classes} classes "
+                           f"and {M} labels")
+    if layout == "nchw" or (layout is None and fits_nchw):                                            # NCHW
         hw = y_pred.shape[2] * y_pred.shape[3]
         inner, outer, cs, ps = hw, num_classes * hw, hw, 1
     else:                                                                                              # NHWC padded
