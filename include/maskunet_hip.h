@@ -452,6 +452,31 @@ int mu_dbscan_supported(int H, int W, int D, int num_classes, int max_inst);
 int mu_dbscan_instances(const int* cls, const void* emb, int B, int H, int W, int D, long inner, long outer_stride, long c_stride,
                         long p_stride, int dtype, int num_classes, float eps, int min_samples, int max_inst, int* ids, int* table,
                         float* score, int* count, int* order, void* workspace, long ws_bytes, void* stream);
+/* Ground-truth instances from an id map the dataset supplies: get_instance_annotations(gt_inst, gt_sem) (city_instance.py:431-449,
+ * called at :472-474) on Cityscapes instanceIds, on panopticapi's rgb2id of a COCO panoptic PNG (coco_panoptic.py:70-85) or on the ids
+ * of mu_coco_masks.  id_map [B,H,W]: MU_IDMAP_I32 int32, MU_IDMAP_I64 int64, or MU_IDMAP_RGB8 uint8 [B,H,W,3] in RGB order with
+ * v = R + 256 * G + 65536 * B formed in the kernel.  sem: int32 [B,H,W].
+ *   dropped    a pixel with v != 0 whose class is outside [0, class_cap) (bit 0 of invalid[b]) or whose int64 v does not fit int32
+ *              (bit 1) counts as v = 0 below; invalid [B] is written for every image, 0 when clean;
+ *   numbering  the distinct non-zero values in ascending SIGNED order (np.unique) are v_1 < ... < v_count; instance k is the set of
+ *              pixels that hold v_k (it need not be connected);
+ *   ids / count / table / score / order as for mu_instances (ids and count complete past max_inst; score 1.0 and order 1..K over the
+ *              K = min(count, max_inst) rows, zero after), with
+ *              class       = (c_((n-1)/2) + c_(n/2)) / 2 over the instance's n semantic values in ascending order, integer division:
+ *                            int(np.median(..)), possibly a class that no pixel of the instance has,
+ *              first_pixel = the instance's lowest raster index;
+ *   values [B,max_inst]: v_k in row k - 1 for k <= K, 0 after.
+ * Stream-ordered, nothing read back, integer atomics only: bit-identical from run to run; every output byte is written.
+ * H*W <= 65536, 1 <= max_inst <= 4096, 1 <= class_cap <= 1024, else MU_ERR_SHAPE; an unknown id_kind is MU_ERR_ARG
+ * (mu_id_instances_supported and mu_id_instances_workspace_bytes: host only; the latter is 0 for unsupported shapes). */
+#define MU_IDMAP_I32 0
+#define MU_IDMAP_I64 1
+#define MU_IDMAP_RGB8 2
+int mu_id_instances_supported(int H, int W, int max_inst, int class_cap);
+long mu_id_instances_workspace_bytes(int B, int H, int W, int max_inst, int class_cap);
+int mu_id_instances(const void* id_map, int id_kind, const int* sem, int B, int H, int W, int max_inst, int class_cap, int* ids,
+                    int* table, float* score, int* count, int* order, int* values, int* invalid, void* workspace, long ws_bytes,
+                    void* stream);
 /* Instance matching: what evaluate_instances / evaluate_panoptic_metrics (ade_panoptic.py:520-586, city_instance.py:451-500) hand to
  * pycocotools and panopticapi, restated from the published algorithms (COCOeval.evaluateImg, maskUtils.iou, panopticapi's
  * pq_compute_single_core) on id maps; no RLE.  Not pinned to those packages.

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("MU_LIB_PATH") or os.path.join(_HERE, "libmaskunet_hip
 
 MU_F32, MU_F16, MU_F32X = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
+MU_IDMAP_I32, MU_IDMAP_I64, MU_IDMAP_RGB8 = 0, 1, 2
 _ERR = {-1: "MU_ERR_ARG", -2: "MU_ERR_SHAPE", -3: "MU_ERR_LAUNCH", -4: "MU_ERR_WORKSPACE"}
 
 # name -> (restype, argtypes); must list EVERY symbol of include/maskunet_hip.h (tests/test_abi.py checks)
@@ -103,6 +104,9 @@ SIGNATURES = {
     "mu_dbscan_workspace_bytes": (L, [I, I, I, I, I]),
     "mu_dbscan_supported": (I, [I, I, I, I, I]),
     "mu_dbscan_instances": (I, [P, P, I, I, I, I, L, L, L, L, I, I, F, I, I, P, P, P, P, P, P, L, P]),
+    "mu_id_instances_supported": (I, [I, I, I, I]),
+    "mu_id_instances_workspace_bytes": (L, [I, I, I, I, I]),
+    "mu_id_instances": (I, [P, I, P, I, I, I, I, I] + [P] * 8 + [L, P]),
     "mu_instance_pairs_supported": (I, [I, I, I, I]),
     "mu_instance_pairs_workspace_bytes": (L, [I, I, I, I, I]),
     "mu_instance_pairs": (I, [P, P, I, I, I, I, I, P, P, P, L, P]),

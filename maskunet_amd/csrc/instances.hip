@@ -237,7 +237,8 @@ __global__ __launch_bounds__(INST_THREADS) void inst_label_kernel(const int* __r
 }
 
 // ------------------------------------------------------------------------------------------
-// Per-instance statistics, table, score order.  Dynamic LDS, P = max_inst rounded up to a power of two:
+// Per-instance statistics, table, score order.  The class of an instance is inst_cls[k] where the caller has one per id (id maps: the
+// median), else the class of its first pixel (components of one class).  Dynamic LDS, P = max_inst rounded up to a power of two:
 //   unsigned long long acc[P] (fixed-point sums, then the sort keys);  unsigned area[P], xmin[P], ymin[P], xmax[P], ymax[P]
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ unsigned long long prob_fixed(float p) {      // round(p * 2^24), two's complement
@@ -246,8 +247,9 @@ __device__ __forceinline__ unsigned long long prob_fixed(float p) {      // roun
 
 __global__ __launch_bounds__(INST_THREADS) void inst_stats_kernel(const int* __restrict__ cls_all, const float* __restrict__ prob_all,
                                                                    const int* __restrict__ ids_all, const int* __restrict__ count,
-                                                                   const int* __restrict__ first_all, int N, int W, int max_inst, int P,
-                                                                   int* __restrict__ table_all, float* __restrict__ score_all,
+                                                                   const int* __restrict__ first_all,
+                                                                   const int* __restrict__ inst_cls_all, int N, int W, int max_inst,
+                                                                   int P, int* __restrict__ table_all, float* __restrict__ score_all,
                                                                    int* __restrict__ order_all) {
     extern __shared__ unsigned inst_lds[];
     unsigned long long* acc = (unsigned long long*)inst_lds;      // first: 8-byte aligned for every P (P = 1 included)
@@ -261,6 +263,7 @@ __global__ __launch_bounds__(INST_THREADS) void inst_stats_kernel(const int* __r
     const int* ids = ids_all + (long)b * N;
     const float* prob = prob_all ? prob_all + (long)b * N : nullptr;
     const int* first = first_all + (long)b * max_inst;
+    const int* inst_cls = inst_cls_all ? inst_cls_all + (long)b * max_inst : nullptr;      // null: the class of the first pixel
     int* table = table_all + (long)b * max_inst * 8;
     float* score = score_all + (long)b * max_inst;
     int* order = order_all + (long)b * max_inst;
@@ -316,7 +319,7 @@ __global__ __launch_bounds__(INST_THREADS) void inst_stats_kernel(const int* __r
         int c = 0;
         if (k < K) {
             const int f = first[k];
-            c = cls[f];
+            c = inst_cls ? inst_cls[k] : cls[f];
             const float s = prob ? (float)((double)(long long)acc[k] / ((double)area[k] * 16777216.0)) : 1.f;
             int* row = table + (long)k * 8;
             row[0] = c;
@@ -413,7 +416,8 @@ extern "C" int mu_instances(const int* cls, const float* prob_or_null, int B, in
     if (!inst_lds_granted()) return MU_ERR_LAUNCH;
     inst_label_kernel<<<B, INST_THREADS, lds_label, st>>>(cls, N, W, max_inst, ids, count, first);
     MU_CHECK_LAUNCH();
-    inst_stats_kernel<<<B, INST_THREADS, lds_stats, st>>>(cls, prob_or_null, ids, count, first, N, W, max_inst, P, table, score, order);
+    inst_stats_kernel<<<B, INST_THREADS, lds_stats, st>>>(cls, prob_or_null, ids, count, first, nullptr, N, W, max_inst, P, table, score,
+                                                           order);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
@@ -787,7 +791,7 @@ extern "C" int mu_dbscan_instances(const int* cls, const void* emb, int B, int H
     db_number_kernel<<<B, INST_THREADS, lds_number, st>>>(P, max_inst, ids, count, first);
     MU_CHECK_LAUNCH();
     const size_t lds_stats = (size_t)PW * (5 * sizeof(unsigned) + sizeof(unsigned long long));
-    inst_stats_kernel<<<B, INST_THREADS, lds_stats, st>>>(cls, nullptr, ids, count, first, N, W, max_inst, PW, table, score, order);
+    inst_stats_kernel<<<B, INST_THREADS, lds_stats, st>>>(cls, nullptr, ids, count, first, nullptr, N, W, max_inst, PW, table, score, order);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
@@ -1140,6 +1144,305 @@ extern "C" int mu_instance_match(const int* pairs, const int* n_pairs, const int
     for (int t = 0; t < MATCH_MAX_T; ++t) P.thr[t] = t < T ? thr[t] : 1.0;
     const size_t lds = (size_t)(2 * K + max_inst_gt + 2 * num_classes + 1) * sizeof(int);      // 57348 bytes at the limits: no grant needed
     inst_match_kernel<<<B, INST_THREADS, lds, (hipStream_t)stream>>>(P);
+    MU_CHECK_LAUNCH();
+    return MU_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// mu_id_instances: ground-truth instances from an id map the dataset supplies -- get_instance_annotations
+// (city_instance.py:431-449) on Cityscapes instanceIds, panopticapi's rgb2id of a COCO panoptic PNG, or coco_masks(...).ids.  Instance
+// k is the set of pixels that hold the k-th distinct non-zero value in ascending signed order (np.unique); its class is the median of
+// the semantic map over its pixels.  Four launches, one workgroup per image, stream-ordered, integer atomics only:
+//   rank    effective values (dropped pixels count as 0) -> run heads in raster order, compacted -> LSD radix sort, 8 bits per pass,
+//           passes whose digit is the same in every key skipped -> distinct list (count, values) -> every pixel finds its rank by
+//           bisection (once per run of a 64-pixel chunk); first pixel by atomicMin in LDS;
+//   pairs   inst_pairs_kernel on (ids, semantic map): the (id, class, pixels) rows sorted by (id, class);
+//   median  one thread per instance walks its rows to the cumulative positions (n - 1) / 2 and n / 2;
+//   stats   inst_stats_kernel with the per-id class array.
+// ------------------------------------------------------------------------------------------
+#define IDMAP_MAX_CLASSES 1024
+#define IDMAP_DIGITS 256
+
+template <int KIND>
+__device__ __forceinline__ const void* idmap_image(const void* map, int b, int N) {
+    if (KIND == MU_IDMAP_I32) return (const int*)map + (long)b * N;
+    if (KIND == MU_IDMAP_I64) return (const long long*)map + (long)b * N;
+    return (const unsigned char*)map + (long)b * N * 3;
+}
+
+// effective value of pixel i; inv collects why pixels were dropped (bit 0: class outside [0, class_cap), bit 1: an int64 id outside int32)
+template <int KIND>
+__device__ __forceinline__ int idmap_value(const void* __restrict__ map, const int* __restrict__ sem, int i, int class_cap, unsigned& inv) {
+    int v;
+    bool fits = true;
+    if (KIND == MU_IDMAP_I32) {
+        v = ((const int*)map)[i];
+    } else if (KIND == MU_IDMAP_I64) {
+        const long long w = ((const long long*)map)[i];
+        v = (int)w;
+        fits = (long long)v == w;
+        if (!fits) v = 1;                                      // non-zero whatever the low word holds
+    } else {
+        const unsigned char* p = (const unsigned char*)map + 3 * i;
+        v = (int)p[0] | ((int)p[1] << 8) | ((int)p[2] << 16);  // panopticapi's rgb2id
+    }
+    if (v == 0) return 0;
+    const unsigned bad = ((unsigned)sem[i] >= (unsigned)class_cap ? 1u : 0u) | (fits ? 0u : 2u);
+    inv |= bad;
+    return bad ? 0 : v;
+}
+
+// one 64-pixel chunk of the wave's segment [.., hi): v = the lane's effective value; true where a run of a non-zero value starts
+template <int KIND>
+__device__ __forceinline__ bool idmap_head(const void* __restrict__ map, const int* __restrict__ sem, int base, int lane, int hi,
+                                           int class_cap, int& v, unsigned& inv) {
+    const int i = base + lane;
+    v = i < hi ? idmap_value<KIND>(map, sem, i, class_cap, inv) : 0;
+    int pv = __shfl_up(v, 1);
+    if (lane == 0) {
+        unsigned other = 0;                                    // that pixel reports its own bits
+        pv = base > 0 ? idmap_value<KIND>(map, sem, base - 1, class_cap, other) : 0;
+    }
+    return v != 0 && v != pv;
+}
+
+// keys_all: 2 * N words per image (the two sides of the sort).  Dynamic LDS (ints): cnt[INST_WAVES][256], tot[256], first[max_inst]:
+// 33 KiB at the limits, no grant needed.
+template <int KIND>
+__global__ __launch_bounds__(INST_THREADS) void idmap_rank_kernel(const void* __restrict__ map_all, const int* __restrict__ sem_all, int N,
+                                                                   int max_inst, int class_cap, unsigned* keys_all,
+                                                                   int* __restrict__ ids_all, int* __restrict__ count,
+                                                                   int* __restrict__ values_all, int* __restrict__ invalid,
+                                                                   int* __restrict__ first_all) {
+    extern __shared__ unsigned inst_lds[];
+    __shared__ unsigned wave_total[INST_WAVES];
+    __shared__ unsigned red[3];                                // dropped-pixel bits; OR and AND of the keys
+    int* cnt = (int*)inst_lds;
+    int* tot = cnt + INST_WAVES * IDMAP_DIGITS;
+    int* first = tot + IDMAP_DIGITS;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const void* map = idmap_image<KIND>(map_all, b, N);
+    const int* sem = sem_all + (long)b * N;
+    unsigned* src = keys_all + (long)b * N * 2;
+    unsigned* dst = src + N;
+    int* ids = ids_all + (long)b * N;
+    int* values = values_all + (long)b * max_inst;
+
+    if (tid == 0) {
+        red[0] = 0u;
+        red[1] = 0u;
+        red[2] = ~0u;
+    }
+    for (int k = tid; k < max_inst; k += INST_THREADS) first[k] = 0x7fffffff;
+
+    // 1. run heads in raster order, compacted: keys = value with the sign bit flipped (unsigned order = signed order)
+    int lo, hi, v;
+    wave_segment(N, INST_WAVES, wave, lo, hi);
+    unsigned mine = 0, total, inv = 0, kor = 0u, kand = ~0u;
+    for (int base = lo; base < hi; base += 64) mine += __popcll(__ballot(idmap_head<KIND>(map, sem, base, lane, hi, class_cap, v, inv)));
+    unsigned running = block_exclusive_base(mine, wave_total, lane, wave, INST_WAVES, total);
+    const int nh = (int)total;
+    for (int base = lo; base < hi; base += 64) {
+        const bool head = idmap_head<KIND>(map, sem, base, lane, hi, class_cap, v, inv);
+        const unsigned pos = wave_flag_rank(head, lane, running);
+        if (head) {
+            const unsigned key = (unsigned)v ^ 0x80000000u;
+            src[pos] = key;
+            kor |= key;
+            kand &= key;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        inv |= (unsigned)__shfl_xor((int)inv, o);
+        kor |= (unsigned)__shfl_xor((int)kor, o);
+        kand &= (unsigned)__shfl_xor((int)kand, o);
+    }
+    if (lane == 0) {
+        atomicOr(&red[0], inv);
+        atomicOr(&red[1], kor);
+        atomicAnd(&red[2], kand);
+    }
+    __syncthreads();                 // the keys (global memory, same workgroup) and red[] are visible past this barrier
+    if (tid == 0) invalid[b] = (int)red[0];
+    const unsigned live = nh ? red[1] ^ red[2] : 0u;          // the bits in which two keys differ
+
+    // 2. stable LSD radix sort of the heads.  Every wave owns a segment of the keys and its own counters: no atomics, a fixed order.
+    wave_segment(nh, INST_WAVES, wave, lo, hi);
+    int* my_cnt = cnt + wave * IDMAP_DIGITS;
+    for (int shift = 0; shift < 32; shift += 8) {
+        if (((live >> shift) & 255u) == 0u) continue;          // the same digit in every key (uniform over the workgroup)
+        for (int k = tid; k < INST_WAVES * IDMAP_DIGITS; k += INST_THREADS) cnt[k] = 0;
+        __syncthreads();
+        for (int base = lo; base < hi; base += 64) {
+            const bool has = base + lane < hi;
+            const unsigned key = has ? src[base + lane] : 0u;
+            wave_sort_chunk<false>((int)((key >> shift) & 255u), has, lane, my_cnt);
+        }
+        __syncthreads();
+        if (tid < IDMAP_DIGITS) {                              // per digit: exclusive prefix over the waves, total
+            int run = 0;
+            for (int w = 0; w < INST_WAVES; ++w) {
+                const int t = cnt[w * IDMAP_DIGITS + tid];
+                cnt[w * IDMAP_DIGITS + tid] = run;
+                run += t;
+            }
+            tot[tid] = run;
+        }
+        __syncthreads();
+        if (wave == 0) wave_scan_excl_array(tot, tot, IDMAP_DIGITS, lane);
+        __syncthreads();
+        for (int k = tid; k < INST_WAVES * IDMAP_DIGITS; k += INST_THREADS) cnt[k] += tot[k & (IDMAP_DIGITS - 1)];
+        __syncthreads();
+        for (int base = lo; base < hi; base += 64) {
+            const bool has = base + lane < hi;
+            const unsigned key = has ? src[base + lane] : 0u;
+            const int pos = wave_sort_chunk<true>((int)((key >> shift) & 255u), has, lane, my_cnt);
+            if (has) dst[pos] = key;
+        }
+        __syncthreads();
+        unsigned* t = src;
+        src = dst;
+        dst = t;
+    }
+
+    // 3. the distinct keys, ascending: dst[0..n)
+    mine = 0;
+    for (int base = lo; base < hi; base += 64) {
+        const int j = base + lane;
+        const unsigned key = j < hi ? src[j] : 0u;
+        unsigned prev = (unsigned)__shfl_up((int)key, 1);
+        if (lane == 0 && j > 0 && j < hi) prev = src[j - 1];
+        mine += __popcll(__ballot(j < hi && (j == 0 || key != prev)));
+    }
+    running = block_exclusive_base(mine, wave_total, lane, wave, INST_WAVES, total);
+    const int n = (int)total;
+    if (tid == 0) count[b] = n;
+    for (int base = lo; base < hi; base += 64) {
+        const int j = base + lane;
+        const unsigned key = j < hi ? src[j] : 0u;
+        unsigned prev = (unsigned)__shfl_up((int)key, 1);
+        if (lane == 0 && j > 0 && j < hi) prev = src[j - 1];
+        const bool fresh = j < hi && (j == 0 || key != prev);
+        const unsigned r = wave_flag_rank(fresh, lane, running);
+        if (fresh) {
+            dst[r] = key;
+            if (r < (unsigned)max_inst) values[r] = (int)(key ^ 0x80000000u);
+        }
+    }
+    for (int k = n + tid; k < max_inst; k += INST_THREADS) values[k] = 0;
+    __syncthreads();
+
+    // 4. ids: one bisection per run of a 64-pixel chunk, the run's pixels take its result
+    for (int base = wave * 64; base < N; base += INST_THREADS) {
+        const int i = base + lane;
+        unsigned other = 0;
+        v = i < N ? idmap_value<KIND>(map, sem, i, class_cap, other) : 0;
+        const int pv = __shfl_up(v, 1);
+        const bool edge = lane == 0 || v != pv;
+        int id = 0;
+        if (edge && v != 0) {
+            const unsigned key = (unsigned)v ^ 0x80000000u;
+            int a = 0, z = n;                                  // the first position whose key is not below: the key is in the list
+            while (a < z) {
+                const int m = (a + z) >> 1;
+                if (dst[m] < key) a = m + 1;
+                else z = m;
+            }
+            id = a + 1;
+            if (id <= max_inst) atomicMin(&first[id - 1], i);
+        }
+        const unsigned long long edges = __ballot(edge) & (lanes_below(lane) | (1ull << lane));      // lane 0 is always one
+        id = __shfl(id, 63 - __builtin_clzll(edges));
+        if (i < N) ids[i] = id;
+    }
+    __syncthreads();
+    for (int k = tid; k < max_inst; k += INST_THREADS) first_all[(long)b * max_inst + k] = first[k];
+}
+
+// pairs: the rows of inst_pairs_kernel on (ids, semantic map), sorted by (id, class).  inst_cls[k] = (c_(n-1)/2 + c_n/2) / 2 over the
+// sorted classes of id k + 1: int(np.median(..)); 0 past min(count, max_inst).
+__global__ __launch_bounds__(INST_THREADS) void idmap_median_kernel(const int* __restrict__ pairs_all, const int* __restrict__ n_pairs,
+                                                                     const int* __restrict__ count, int N, int max_inst,
+                                                                     int* __restrict__ inst_cls_all) {
+    const int b = blockIdx.x;
+    const int* pairs = pairs_all + (long)b * N * 3;
+    int* inst_cls = inst_cls_all + (long)b * max_inst;
+    const int rows = n_pairs[b], K = min(count[b], max_inst);
+    for (int k = threadIdx.x; k < max_inst; k += INST_THREADS) {
+        int c = 0;
+        if (k < K) {
+            int a = 0, z = rows;                               // the first row of id k + 1
+            while (a < z) {
+                const int m = (a + z) >> 1;
+                if (pairs[3 * m] < k + 1) a = m + 1;
+                else z = m;
+            }
+            int n = 0;
+            for (int r = a; r < rows && pairs[3 * r] == k + 1; ++r) n += pairs[3 * r + 2];
+            const int t0 = (n - 1) >> 1, t1 = n >> 1;
+            int cum = 0, c0 = -1, c1 = 0;
+            for (int r = a; r < rows && pairs[3 * r] == k + 1; ++r) {
+                cum += pairs[3 * r + 2];
+                if (c0 < 0 && cum > t0) c0 = pairs[3 * r + 1];
+                if (cum > t1) {
+                    c1 = pairs[3 * r + 1];
+                    break;
+                }
+            }
+            c = (c0 + c1) / 2;
+        }
+        inst_cls[k] = c;
+    }
+}
+
+extern "C" int mu_id_instances_supported(int H, int W, int max_inst, int class_cap) {
+    if (mu_instances_supported(H, W, max_inst) != MU_OK) return MU_ERR_SHAPE;
+    if (class_cap < 1 || class_cap > IDMAP_MAX_CLASSES) return MU_ERR_SHAPE;
+    return MU_OK;
+}
+
+// ints per image: keys [2 N], first [max_inst], inst_cls [max_inst], bits and pre [max_inst * words each], pairs [3 N], n_pairs [1]
+extern "C" long mu_id_instances_workspace_bytes(int B, int H, int W, int max_inst, int class_cap) {
+    if (B <= 0 || mu_id_instances_supported(H, W, max_inst, class_cap) != MU_OK) return 0;
+    const long N = (long)H * W;
+    return (long)B * (5 * N + 2L * max_inst * (1 + pair_row_words(class_cap - 1)) + 1) * (long)sizeof(int);
+}
+
+extern "C" int mu_id_instances(const void* id_map, int id_kind, const int* sem, int B, int H, int W, int max_inst, int class_cap, int* ids,
+                               int* table, float* score, int* count, int* order, int* values, int* invalid, void* workspace,
+                               long ws_bytes, void* stream) {
+    if (!id_map || !sem || !ids || !table || !score || !count || !order || !values || !invalid || !workspace || B <= 0 || H <= 0 || W <= 0)
+        return MU_ERR_ARG;
+    if (id_kind != MU_IDMAP_I32 && id_kind != MU_IDMAP_I64 && id_kind != MU_IDMAP_RGB8) return MU_ERR_ARG;
+    if (mu_id_instances_supported(H, W, max_inst, class_cap) != MU_OK) return MU_ERR_SHAPE;
+    if (ws_bytes < mu_id_instances_workspace_bytes(B, H, W, max_inst, class_cap)) return MU_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int N = H * W, P = inst_pow2(max_inst), GW = pair_row_words(class_cap - 1);
+    unsigned* keys = (unsigned*)workspace;
+    int* first = (int*)(keys + (long)B * N * 2);
+    int* inst_cls = first + (long)B * max_inst;
+    unsigned* bits = (unsigned*)(inst_cls + (long)B * max_inst);
+    unsigned* pre = bits + (long)B * max_inst * GW;
+    int* pairs = (int*)(pre + (long)B * max_inst * GW);
+    int* n_pairs = pairs + (long)B * N * 3;
+    if (!inst_lds_granted()) return MU_ERR_LAUNCH;
+    const size_t lds_rank = (size_t)((INST_WAVES + 1) * IDMAP_DIGITS + max_inst) * sizeof(int);
+    if (id_kind == MU_IDMAP_I32)
+        idmap_rank_kernel<MU_IDMAP_I32><<<B, INST_THREADS, lds_rank, st>>>(id_map, sem, N, max_inst, class_cap, keys, ids, count, values,
+                                                                          invalid, first);
+    else if (id_kind == MU_IDMAP_I64)
+        idmap_rank_kernel<MU_IDMAP_I64><<<B, INST_THREADS, lds_rank, st>>>(id_map, sem, N, max_inst, class_cap, keys, ids, count, values,
+                                                                          invalid, first);
+    else
+        idmap_rank_kernel<MU_IDMAP_RGB8><<<B, INST_THREADS, lds_rank, st>>>(id_map, sem, N, max_inst, class_cap, keys, ids, count, values,
+                                                                           invalid, first);
+    MU_CHECK_LAUNCH();
+    inst_pairs_kernel<<<B, INST_THREADS, 0, st>>>(ids, sem, N, max_inst, class_cap - 1, GW, bits, pre, pairs, n_pairs);
+    MU_CHECK_LAUNCH();
+    idmap_median_kernel<<<B, INST_THREADS, 0, st>>>(pairs, n_pairs, count, N, max_inst, inst_cls);
+    MU_CHECK_LAUNCH();
+    const size_t lds_stats = (size_t)P * (5 * sizeof(unsigned) + sizeof(unsigned long long));
+    inst_stats_kernel<<<B, INST_THREADS, lds_stats, st>>>(sem, nullptr, ids, count, first, inst_cls, N, W, max_inst, P, table, score, order);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }

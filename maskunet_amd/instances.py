@@ -11,6 +11,9 @@ ids run 1..count within an image, ordered by each instance's first pixel in rast
 The 3-head model (`UNet(c_in, c_out, embed_dim=16)`) is evaluated differently: evaluate_instances (city_instance.py:451-482) clusters
 the embedding head per predicted class with sklearn's DBSCAN (get_instances_from_embeddings / get_instance_annotations,
 city_instance.py:405-449).  instances_from_embeddings does that on the device (mu_dbscan_instances) and returns the same `Instances`.
+
+The ground truth of that script is an id map the dataset supplies (get_instance_annotations(gt_inst, gt_sem), city_instance.py:472-474):
+instances_from_id_map (mu_id_instances) numbers its distinct values and takes each instance's class as the median of the semantic map.
 """
 from __future__ import annotations
 
@@ -36,6 +39,9 @@ class Instances:
     count: torch.Tensor          # int32 [B]
     order: torch.Tensor          # int32 [B,max_instances]     ids by descending score (ties: ascending id), padded with 0
     prob: torch.Tensor | None = None     # fp32 [B,H,W] probability of the arg-max class (None for label input)
+    values: torch.Tensor | None = None   # int32 [B,max_instances]  the id map's value of id k in row k-1 (instances_from_id_map only)
+    invalid: torch.Tensor | None = None  # int32 [B]  instances_from_id_map only: bit 0 = pixels dropped for a class outside [0, class_cap),
+                                         #            bit 1 = for an int64 id outside int32; 0 = clean
 
     def top(self, max_queries):
         """(ids, scores) [B, max_queries] of the reference's sorted(instances, key=score, reverse=True)[:max_queries]; id 0 (score 0)
@@ -117,6 +123,47 @@ def instances_from_labels(labels, max_instances=1024):
     if labels.dim() != 3 or labels.dtype not in (torch.int64, torch.int32) or not labels.is_cuda:
         raise RuntimeError("instances_from_labels expects an int64 / int32 [B,H,W] class map on the GPU")
     return _label(labels.to(torch.int32).contiguous(), None, max_instances)
+
+
+def instances_from_id_map(instance_mask, semantic_mask, max_instances=1024, class_cap=256):
+    """Ground-truth instances of an id map the dataset supplies: get_instance_annotations(gt_inst, gt_sem) (city_instance.py:431-449).
+    `instance_mask`: int32 / int64 [B,H,W] (Cityscapes instanceIds, coco_masks(...).ids) or a uint8 [B,H,W,3] RGB image, read as
+    R + 256 G + 65536 B (panopticapi's rgb2id of a COCO panoptic PNG).  `semantic_mask`: int32 / int64 [B,H,W].  Id k is the set of
+    pixels with the k-th distinct non-zero value in ascending signed order (np.unique), connected or not; its class is
+    int(np.median(semantic_mask[mask])); every score is 1.0; `values` holds the value of each id.  A pixel of a non-zero id whose class
+    is outside [0, class_cap), or whose int64 id does not fit int32, is dropped (counts as id 0) and reported in `invalid`.
+    Never synchronises."""
+    m, c = instance_mask, semantic_mask
+    if not (torch.is_tensor(m) and torch.is_tensor(c) and m.is_cuda and c.is_cuda):
+        raise RuntimeError("instances_from_id_map expects the id map and the semantic map on the GPU")
+    rgb = m.dtype == torch.uint8
+    if not ((rgb and m.dim() == 4 and m.shape[-1] == 3) or (m.dtype in (torch.int64, torch.int32) and m.dim() == 3)):
+        raise RuntimeError("instances_from_id_map expects an int64 / int32 [B,H,W] id map or a uint8 [B,H,W,3] RGB image")
+    if c.dim() != 3 or c.dtype not in (torch.int64, torch.int32):
+        raise RuntimeError("instances_from_id_map expects an int64 / int32 [B,H,W] semantic map")
+    if tuple(m.shape[:3]) != tuple(c.shape):
+        raise RuntimeError("the id map and the semantic map differ in batch or image size")
+    B, H, W = c.shape
+    lib = _lib.load()
+    max_instances, class_cap = int(max_instances), int(class_cap)
+    if B < 1 or lib.mu_id_instances_supported(H, W, max_instances, class_cap) != 0:
+        raise RuntimeError("maskunet_amd: id-map instances need B >= 1, H*W <= 65536, 1 <= max_instances <= 4096 and "
+                           f"1 <= class_cap <= 1024, got {B}x{H}x{W}, {max_instances}, {class_cap}")
+    kind = _lib.MU_IDMAP_RGB8 if rgb else (_lib.MU_IDMAP_I64 if m.dtype == torch.int64 else _lib.MU_IDMAP_I32)
+    m = m.contiguous()
+    classes = c.to(torch.int32).contiguous()
+    dev = classes.device
+    ids = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    table = torch.empty((B, max_instances, 8), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, max_instances), dtype=torch.float32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    order = torch.empty((B, max_instances), dtype=torch.int32, device=dev)
+    values = torch.empty((B, max_instances), dtype=torch.int32, device=dev)
+    invalid = torch.empty(B, dtype=torch.int32, device=dev)
+    ws = torch.empty(lib.mu_id_instances_workspace_bytes(B, H, W, max_instances, class_cap), dtype=torch.uint8, device=dev)
+    call("mu_id_instances", ptr(m), kind, ptr(classes), B, H, W, max_instances, class_cap, ptr(ids), ptr(table), ptr(scores), ptr(count),
+         ptr(order), ptr(values), ptr(invalid), ptr(ws), ws.numel(), stream())
+    return Instances(classes, ids, table, scores, count, order, None, values, invalid)
 
 
 def generate_instance_mask(semantic_mask, max_instances=1024):
