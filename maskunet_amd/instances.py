@@ -77,22 +77,51 @@ class Instances:
         return encode_rle(self.ids, sel, max_id=self.order.shape[1])
 
 
+def _class_map(t, what):
+    """the contiguous int32 copy of an int64 / int32 [B,H,W] class map on the GPU; `what` is the complaint otherwise"""
+    if t.dim() != 3 or t.dtype not in (torch.int64, torch.int32) or not t.is_cuda:
+        raise RuntimeError(what)
+    return t.to(torch.int32).contiguous()
+
+
+def _strided_source(t):
+    """(x, inner, outer, cs, ps) of a module output [B,C,H,W]: the NHWC tensor an untouched output was converted from, else the
+    contiguous NCHW tensor, with the pixel / channel strides the kernels take"""
+    B, C, H, W = t.shape
+    src = _nhwc_source(t)
+    if src is not None and src[0].is_contiguous():
+        x = src[0].detach()
+        return x, B * H * W, 0, 1, x.shape[-1]
+    return t.detach().contiguous(), H * W, C * H * W, H * W, 1
+
+
+def _argmax_prob(logits, temperature):
+    """(classes int32, prob fp32) [B,H,W]: the first arg-max of the logits [B,C,H,W] and softmax(logits / temperature) of it"""
+    B, C, H, W = logits.shape
+    x, inner, outer, cs, ps = _strided_source(logits)
+    classes = torch.empty((B, H, W), dtype=torch.int32, device=x.device)
+    prob = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
+    call("mu_argmax_prob", ptr(x), B * H * W, C, inner, outer, cs, ps, 1.0 / float(temperature), ptr(classes), ptr(prob), dt(x), stream())
+    return classes, prob
+
+
+def _outputs(B, H, W, max_instances, device):
+    """ids, table, scores, count, order: the five tensors every producer fills"""
+    i32 = dict(dtype=torch.int32, device=device)
+    return (torch.empty((B, H, W), **i32), torch.empty((B, max_instances, 8), **i32),
+            torch.empty((B, max_instances), dtype=torch.float32, device=device), torch.empty(B, **i32), torch.empty((B, max_instances), **i32))
+
+
 def _label(classes, prob, max_instances):
     B, H, W = classes.shape
     lib = _lib.load()
     max_instances = int(max_instances)
     if lib.mu_instances_supported(H, W, max_instances) != 0:
         raise RuntimeError(f"maskunet_amd: instances need H*W <= 65536 and 1 <= max_instances <= 4096, got {H}x{W}, {max_instances}")
-    dev = classes.device
-    ids = torch.empty((B, H, W), dtype=torch.int32, device=dev)
-    table = torch.empty((B, max_instances, 8), dtype=torch.int32, device=dev)
-    scores = torch.empty((B, max_instances), dtype=torch.float32, device=dev)
-    count = torch.empty(B, dtype=torch.int32, device=dev)
-    order = torch.empty((B, max_instances), dtype=torch.int32, device=dev)
-    ws = torch.empty(lib.mu_instances_workspace_bytes(B, H, W, max_instances), dtype=torch.uint8, device=dev)
-    call("mu_instances", ptr(classes), ptr(prob), B, H, W, max_instances, ptr(ids), ptr(table), ptr(scores), ptr(count), ptr(order),
-         ptr(ws), ws.numel(), stream())
-    return Instances(classes, ids, table, scores, count, order, prob)
+    out = _outputs(B, H, W, max_instances, classes.device)
+    ws = torch.empty(lib.mu_instances_workspace_bytes(B, H, W, max_instances), dtype=torch.uint8, device=classes.device)
+    call("mu_instances", ptr(classes), ptr(prob), B, H, W, max_instances, *map(ptr, out), ptr(ws), ws.numel(), stream())
+    return Instances(classes, *out, prob)
 
 
 def predict_instances(outputs, temperature=0.5, max_instances=1024):
@@ -103,26 +132,12 @@ def predict_instances(outputs, temperature=0.5, max_instances=1024):
         raise RuntimeError("predict_instances expects the module output [B,C,H,W] on the GPU")
     if not temperature > 0:
         raise ValueError("temperature must be positive")
-    B, C, H, W = outputs.shape
-    M = B * H * W
-    src = _nhwc_source(outputs)
-    if src is not None and src[0].is_contiguous():
-        x = src[0].detach()
-        inner, outer, cs, ps = M, 0, 1, x.shape[-1]
-    else:
-        x = outputs.detach().contiguous()
-        inner, outer, cs, ps = H * W, C * H * W, H * W, 1
-    classes = torch.empty((B, H, W), dtype=torch.int32, device=x.device)
-    prob = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
-    call("mu_argmax_prob", ptr(x), M, C, inner, outer, cs, ps, 1.0 / float(temperature), ptr(classes), ptr(prob), dt(x), stream())
-    return _label(classes, prob, max_instances)
+    return _label(*_argmax_prob(outputs, temperature), max_instances)
 
 
 def instances_from_labels(labels, max_instances=1024):
     """Instances of an int64 / int32 class map [B,H,W] (the ground-truth side: every score is 1.0)."""
-    if labels.dim() != 3 or labels.dtype not in (torch.int64, torch.int32) or not labels.is_cuda:
-        raise RuntimeError("instances_from_labels expects an int64 / int32 [B,H,W] class map on the GPU")
-    return _label(labels.to(torch.int32).contiguous(), None, max_instances)
+    return _label(_class_map(labels, "instances_from_labels expects an int64 / int32 [B,H,W] class map on the GPU"), None, max_instances)
 
 
 def instances_from_id_map(instance_mask, semantic_mask, max_instances=1024, class_cap=256):
@@ -139,8 +154,7 @@ def instances_from_id_map(instance_mask, semantic_mask, max_instances=1024, clas
     rgb = m.dtype == torch.uint8
     if not ((rgb and m.dim() == 4 and m.shape[-1] == 3) or (m.dtype in (torch.int64, torch.int32) and m.dim() == 3)):
         raise RuntimeError("instances_from_id_map expects an int64 / int32 [B,H,W] id map or a uint8 [B,H,W,3] RGB image")
-    if c.dim() != 3 or c.dtype not in (torch.int64, torch.int32):
-        raise RuntimeError("instances_from_id_map expects an int64 / int32 [B,H,W] semantic map")
+    classes = _class_map(c, "instances_from_id_map expects an int64 / int32 [B,H,W] semantic map")
     if tuple(m.shape[:3]) != tuple(c.shape):
         raise RuntimeError("the id map and the semantic map differ in batch or image size")
     B, H, W = c.shape
@@ -151,19 +165,14 @@ def instances_from_id_map(instance_mask, semantic_mask, max_instances=1024, clas
                            f"1 <= class_cap <= 1024, got {B}x{H}x{W}, {max_instances}, {class_cap}")
     kind = _lib.MU_IDMAP_RGB8 if rgb else (_lib.MU_IDMAP_I64 if m.dtype == torch.int64 else _lib.MU_IDMAP_I32)
     m = m.contiguous()
-    classes = c.to(torch.int32).contiguous()
     dev = classes.device
-    ids = torch.empty((B, H, W), dtype=torch.int32, device=dev)
-    table = torch.empty((B, max_instances, 8), dtype=torch.int32, device=dev)
-    scores = torch.empty((B, max_instances), dtype=torch.float32, device=dev)
-    count = torch.empty(B, dtype=torch.int32, device=dev)
-    order = torch.empty((B, max_instances), dtype=torch.int32, device=dev)
+    out = _outputs(B, H, W, max_instances, dev)
     values = torch.empty((B, max_instances), dtype=torch.int32, device=dev)
     invalid = torch.empty(B, dtype=torch.int32, device=dev)
     ws = torch.empty(lib.mu_id_instances_workspace_bytes(B, H, W, max_instances, class_cap), dtype=torch.uint8, device=dev)
-    call("mu_id_instances", ptr(m), kind, ptr(classes), B, H, W, max_instances, class_cap, ptr(ids), ptr(table), ptr(scores), ptr(count),
-         ptr(order), ptr(values), ptr(invalid), ptr(ws), ws.numel(), stream())
-    return Instances(classes, ids, table, scores, count, order, None, values, invalid)
+    call("mu_id_instances", ptr(m), kind, ptr(classes), B, H, W, max_instances, class_cap, *map(ptr, out), ptr(values), ptr(invalid),
+         ptr(ws), ws.numel(), stream())
+    return Instances(classes, *out, None, values, invalid)
 
 
 def generate_instance_mask(semantic_mask, max_instances=1024):
@@ -198,46 +207,25 @@ def instances_from_embeddings(semantic, embeddings, eps=0.5, min_samples=5, temp
             raise ValueError("temperature must be positive")
         if tuple(semantic.shape[0:1] + semantic.shape[2:]) != (B, H, W):
             raise RuntimeError("semantic and embeddings differ in batch or image size")
-        C = semantic.shape[1]
-        num_classes = C if num_classes is None else int(num_classes)
-        M = B * H * W
-        src = _nhwc_source(semantic)
-        if src is not None and src[0].is_contiguous():
-            x = src[0].detach()
-            inner, outer, cs, ps = M, 0, 1, x.shape[-1]
-        else:
-            x = semantic.detach().contiguous()
-            inner, outer, cs, ps = H * W, C * H * W, H * W, 1
-        classes = torch.empty((B, H, W), dtype=torch.int32, device=x.device)
-        prob = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
-        call("mu_argmax_prob", ptr(x), M, C, inner, outer, cs, ps, 1.0 / float(temperature), ptr(classes), ptr(prob), dt(x), stream())
+        num_classes = semantic.shape[1] if num_classes is None else int(num_classes)
+        classes, prob = _argmax_prob(semantic, temperature)
     else:
-        if semantic.dim() != 3 or semantic.dtype not in (torch.int64, torch.int32) or tuple(semantic.shape) != (B, H, W):
-            raise RuntimeError("semantic must be the logits [B,C,H,W] or an int64 / int32 class map [B,H,W] of the embeddings' size")
+        what = "semantic must be the logits [B,C,H,W] or an int64 / int32 class map [B,H,W] of the embeddings' size"
+        classes = _class_map(semantic, what)
+        if tuple(semantic.shape) != (B, H, W):
+            raise RuntimeError(what)
         if num_classes is None:
             raise ValueError("num_classes is required with a class map")
         num_classes = int(num_classes)
-        classes = semantic.to(torch.int32).contiguous()
     lib = _lib.load()
     max_instances, min_samples = int(max_instances), int(min_samples)
     if lib.mu_dbscan_supported(H, W, D, num_classes, max_instances) != 0 or min_samples < 1 or not eps > 0:
         raise RuntimeError("maskunet_amd: embedding instances need H*W <= 65536, 1 <= D <= 64, 1 <= num_classes <= 1024, "
                            f"1 <= max_instances <= 4096, min_samples >= 1, eps > 0; got {H}x{W}, D={D}, {num_classes} classes, "
                            f"{max_instances}, {min_samples}, {eps}")
-    src = _nhwc_source(embeddings)
-    if src is not None and src[0].is_contiguous():
-        e = src[0].detach()
-        inner, outer, cs, ps = B * H * W, 0, 1, e.shape[-1]
-    else:
-        e = embeddings.detach().contiguous()
-        inner, outer, cs, ps = H * W, D * H * W, H * W, 1
-    dev = e.device
-    ids = torch.empty((B, H, W), dtype=torch.int32, device=dev)
-    table = torch.empty((B, max_instances, 8), dtype=torch.int32, device=dev)
-    scores = torch.empty((B, max_instances), dtype=torch.float32, device=dev)
-    count = torch.empty(B, dtype=torch.int32, device=dev)
-    order = torch.empty((B, max_instances), dtype=torch.int32, device=dev)
-    ws = torch.empty(lib.mu_dbscan_workspace_bytes(B, H, W, num_classes, max_instances), dtype=torch.uint8, device=dev)
+    e, inner, outer, cs, ps = _strided_source(embeddings)
+    out = _outputs(B, H, W, max_instances, e.device)
+    ws = torch.empty(lib.mu_dbscan_workspace_bytes(B, H, W, num_classes, max_instances), dtype=torch.uint8, device=e.device)
     call("mu_dbscan_instances", ptr(classes), ptr(e), B, H, W, D, inner, outer, cs, ps, dt(e), num_classes, float(eps), min_samples,
-         max_instances, ptr(ids), ptr(table), ptr(scores), ptr(count), ptr(order), ptr(ws), ws.numel(), stream())
-    return Instances(classes, ids, table, scores, count, order, prob)
+         max_instances, *map(ptr, out), ptr(ws), ws.numel(), stream())
+    return Instances(classes, *out, prob)

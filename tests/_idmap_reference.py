@@ -10,6 +10,8 @@ the case generators that the host and the GPU tests share.  Written from the con
 """
 import numpy as np
 
+from tests._instances_reference import table_from_ids
+
 I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
 
 
@@ -27,12 +29,9 @@ def instances(id_map, sem, max_instances=1024, class_cap=256):
     assert v_all.shape == (B, H, W)
     M = max_instances
     ids = np.zeros((B, H * W), np.int32)
-    count = np.zeros(B, np.int32)
-    table = np.zeros((B, M, 8), np.int32)
-    score = np.zeros((B, M), np.float32)
-    order = np.zeros((B, M), np.int32)
     values = np.zeros((B, M), np.int32)
     invalid = np.zeros(B, np.int32)
+    classes = []
     for b in range(B):
         v, c = v_all[b].reshape(-1), sem[b].reshape(-1).astype(np.int64)
         bad_c = (v != 0) & ((c < 0) | (c >= class_cap))
@@ -44,33 +43,18 @@ def instances(id_map, sem, max_instances=1024, class_cap=256):
         number[uniq == 0] = 0
         ids[b] = number[inverse.reshape(-1)]
         distinct = uniq[uniq != 0]
-        count[b] = len(distinct)
         K = min(len(distinct), M)
-        if K == 0:
-            continue
         values[b, :K] = distinct[:K]
         pix = np.flatnonzero((ids[b] >= 1) & (ids[b] <= K))
         k = ids[b][pix].astype(np.int64) - 1
         area = np.bincount(k, minlength=K)
-        lo = np.full((3, K), np.iinfo(np.int64).max)
-        hi = np.zeros((2, K), np.int64)
-        np.minimum.at(lo[0], k, pix % W)
-        np.minimum.at(lo[1], k, pix // W)
-        np.minimum.at(lo[2], k, pix)
-        np.maximum.at(hi[0], k, pix % W)
-        np.maximum.at(hi[1], k, pix // W)
-        by = np.lexsort((c[pix], k))                        # by instance, then by class
-        cs = c[pix][by]
+        cs = c[pix][np.lexsort((c[pix], k))]                # by instance, then by class
         start = np.cumsum(area) - area
-        cls = (cs[start + (area - 1) // 2] + cs[start + area // 2]) // 2
-        seen, rank = {}, np.zeros(K, np.int64)
-        for j, cj in enumerate(cls.tolist()):
-            seen[cj] = rank[j] = seen.get(cj, 0) + 1
-        table[b, :K] = np.stack([cls, area, lo[0], lo[1], hi[0], hi[1], lo[2], rank], 1)
-        score[b, :K] = 1.0
-        order[b, :K] = np.arange(1, K + 1)
-    return {"ids": ids.reshape(B, H, W), "count": count, "table": table, "score": score, "order": order, "values": values,
-            "invalid": invalid}
+        classes.append((cs[start + (area - 1) // 2] + cs[start + area // 2]) // 2)
+    ids = ids.reshape(B, H, W)
+    r = table_from_ids(ids, classes, M)
+    return {"ids": ids, "count": r["count"], "table": r["table"], "score": r["score"].astype(np.float32), "order": r["order"],
+            "values": values, "invalid": invalid}
 
 
 # ------------------------------------------------------------------------------------------------

@@ -8,6 +8,8 @@ A "side" is a dict of numpy arrays as the instance producers return them: ids [B
 """
 import numpy as np
 
+from tests._instances_reference import table_from_ids
+
 DEFAULT_THRESHOLDS = np.linspace(0.5, 0.95, 10)
 
 
@@ -15,25 +17,9 @@ def side_from_ids(ids, classes, max_inst, scores=None):
     """A side from arbitrary id maps: ids [B,H,W] (ids 1..n_b, every one present, regions of any shape), classes[b][k-1] the class of
     id k, scores[b][k-1] its score (1.0 without).  Order: score descending (as fp32), ties by ascending id."""
     ids = np.asarray(ids, np.int32)
-    B, H, W = ids.shape
-    count = np.zeros(B, np.int32)
-    table = np.zeros((B, max_inst, 8), np.int32)
-    score = np.zeros((B, max_inst), np.float32)
-    order = np.zeros((B, max_inst), np.int32)
-    for b in range(B):
-        n = int(ids[b].max())
-        count[b] = n
-        seen = {}
-        for k in range(1, min(n, max_inst) + 1):
-            ys, xs = np.nonzero(ids[b] == k)
-            assert len(ys), "every id must be present"
-            c = int(classes[b][k - 1])
-            seen[c] = seen.get(c, 0) + 1
-            table[b, k - 1] = [c, len(ys), xs.min(), ys.min(), xs.max(), ys.max(), ys[0] * W + xs[0], seen[c]]
-            score[b, k - 1] = 1.0 if scores is None else np.float32(scores[b][k - 1])
-        K = min(n, max_inst)
-        order[b, :K] = 1 + np.asarray(sorted(range(K), key=lambda k: (-float(score[b, k]), k)), np.int32)
-    return {"ids": ids, "count": count, "table": table, "score": score, "order": order}
+    r = table_from_ids(ids, classes, max_inst, scores)
+    assert (r["table"][:, :, 1] > 0).sum(1).tolist() == np.minimum(r["count"], max_inst).tolist(), "every id must be present"
+    return {"ids": ids, "count": r["count"], "table": r["table"], "score": r["score"].astype(np.float32), "order": r["order"]}
 
 
 def pair_table(pred_ids, gt_ids, max_pred, max_gt):

@@ -13,35 +13,15 @@ import pytest
 import torch
 
 from tests import _dbscan_reference as R
+from tests._device_buffers import Guarded, call
 from tests.conftest import GOLDEN as _GOLDEN
 
 GOLDEN = os.path.join(_GOLDEN, "dbscan")
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-GUARD = 1024                         # elements (4 KiB of int32 / fp32; 2 KiB of fp16 on top of the 32-channel row padding)
-SENT_I, SENT_F = -777, -777.0
 T_ROWS, T_COLS = 256, 64             # DB_TR / DB_TC of csrc/instances.hip: points per workgroup, points per LDS chunk
 PAD = 100.0                          # value of the padded NHWC channels: reading one would move every distance
-
-
-class Guarded:
-    """n elements between two guard bands; everything starts as the sentinel."""
-
-    def __init__(self, n, dtype, data=None):
-        self.n = n
-        self.sent = SENT_F if dtype.is_floating_point else SENT_I
-        self.buf = torch.full((n + 2 * GUARD,), self.sent, dtype=dtype, device=DEV)
-        if data is not None:
-            self.buf[GUARD:GUARD + n] = torch.as_tensor(np.ascontiguousarray(data)).to(dtype).reshape(-1).to(DEV)
-
-    @property
-    def t(self):
-        return self.buf[GUARD:GUARD + self.n]
-
-    def check(self, what):
-        assert bool((self.buf[:GUARD] == self.sent).all()), f"{what}: guard band BEFORE the buffer was written"
-        assert bool((self.buf[GUARD + self.n:] == self.sent).all()), f"{what}: guard band AFTER the buffer was written"
 
 
 def run_dbscan(cls, emb, num_classes, eps=0.5, min_samples=5, max_inst=64, layout="nchw", dtype=None):
@@ -59,29 +39,17 @@ def run_dbscan(cls, emb, num_classes, eps=0.5, min_samples=5, max_inst=64, layou
         data = np.full((B, H, W, Dp), PAD, emb.dtype)
         data[..., :D] = emb
         strides = (B * H * W, 0, 1, Dp)
-    g_cls = Guarded(cls.size, torch.int32, cls)
-    g_emb = Guarded(data.size, tdt, data)
-    emb_before = g_emb.t.clone()
-    g_ids = Guarded(B * H * W, torch.int32)
-    g_table = Guarded(B * max_inst * 8, torch.int32)
-    g_score = Guarded(B * max_inst, torch.float32)
-    g_count = Guarded(B, torch.int32)
-    g_order = Guarded(B * max_inst, torch.int32)
+    i32, f32 = torch.int32, torch.float32
+    g_cls = Guarded(cls.size, i32, cls, "the class map")
+    g_emb = Guarded(data.size, tdt, data, "the embedding tensor")
+    shapes = {"ids": ((B, H, W), i32), "table": ((B, max_inst, 8), i32), "score": ((B, max_inst), f32), "count": ((B,), i32),
+              "order": ((B, max_inst), i32)}
+    outs = {k: Guarded(int(np.prod(s)), d, name=k) for k, (s, d) in shapes.items()}
     nws = lib.mu_dbscan_workspace_bytes(B, H, W, num_classes, max_inst)
     assert nws > 0 and nws % 4 == 0
-    g_ws = Guarded(nws // 4, torch.int32)
-    _lib.call("mu_dbscan_instances", g_cls.t.data_ptr(), g_emb.t.data_ptr(), B, H, W, D, *strides, _lib.dt(tdt), num_classes, float(eps),
-              int(min_samples), max_inst, g_ids.t.data_ptr(), g_table.t.data_ptr(), g_score.t.data_ptr(), g_count.t.data_ptr(),
-              g_order.t.data_ptr(), g_ws.t.data_ptr(), nws, _lib.stream())
-    torch.cuda.synchronize()
-    for name, g in [("cls", g_cls), ("emb", g_emb), ("ids", g_ids), ("table", g_table), ("score", g_score), ("count", g_count),
-                    ("order", g_order), ("workspace", g_ws)]:
-        g.check(name)
-    assert np.array_equal(g_cls.t.cpu().numpy().reshape(cls.shape), cls), "the class map is an input"
-    assert torch.equal(g_emb.t, emb_before), "the embeddings are an input"
-    return {"ids": g_ids.t.cpu().numpy().reshape(B, H, W), "table": g_table.t.cpu().numpy().reshape(B, max_inst, 8),
-            "score": g_score.t.cpu().numpy().reshape(B, max_inst), "count": g_count.t.cpu().numpy(),
-            "order": g_order.t.cpu().numpy().reshape(B, max_inst)}
+    call("mu_dbscan_instances", g_cls, g_emb, B, H, W, D, *strides, _lib.dt(tdt), num_classes, float(eps), int(min_samples), max_inst,
+         *outs.values(), Guarded(nws // 4, i32, name="workspace"), nws)
+    return {k: outs[k].host(shapes[k][0]) for k in shapes}
 
 
 def compare(got, ref, overflow=False):

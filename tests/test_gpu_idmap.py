@@ -11,42 +11,14 @@ import pytest
 import torch
 
 from tests import _idmap_reference as R
+from tests._device_buffers import Guarded, call, side_of
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-GUARD_BYTES = 4096
-SENT = {torch.int32: -777, torch.int64: -777, torch.uint8: 0xA5, torch.float32: -777.0}
 OUT_KEYS = ("ids", "table", "score", "count", "order", "values", "invalid")
 KIND = {"i32": (0, torch.int32), "i64": (1, torch.int64), "rgb8": (2, torch.uint8)}
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "idmap")
-
-
-class Guarded:
-    """n elements between two guard bands; everything starts as the sentinel."""
-
-    def __init__(self, n, dtype, data=None):
-        self.n, self.g, self.sent = n, GUARD_BYTES // torch.empty(0, dtype=dtype).element_size(), SENT[dtype]
-        self.buf = torch.full((n + 2 * self.g,), self.sent, dtype=dtype, device=DEV)
-        self.data = None
-        if data is not None:
-            self.data = torch.as_tensor(np.ascontiguousarray(data)).to(dtype).reshape(-1)
-            assert self.data.numel() == n
-            self.buf[self.g:self.g + n] = self.data.to(DEV)
-
-    @property
-    def p(self):
-        return self.buf[self.g:self.g + self.n].data_ptr()
-
-    @property
-    def t(self):
-        return self.buf[self.g:self.g + self.n]
-
-    def check(self, what):
-        assert bool((self.buf[:self.g] == self.sent).all()), f"{what}: guard band BEFORE the buffer was written"
-        assert bool((self.buf[self.g + self.n:] == self.sent).all()), f"{what}: guard band AFTER the buffer was written"
-        if self.data is not None:
-            assert torch.equal(self.t.cpu(), self.data), f"{what} is an input"
 
 
 def run(id_map, sem, max_inst, class_cap, kind="i64"):
@@ -57,25 +29,20 @@ def run(id_map, sem, max_inst, class_cap, kind="i64"):
     code, dtype = KIND[kind]
     if kind == "i32":
         assert ((id_map >= R.I32_MIN) & (id_map <= R.I32_MAX)).all()
-    g_map = Guarded(id_map.size, dtype, id_map)
-    g_sem = Guarded(sem.size, torch.int32, sem)
+    g_map = Guarded(id_map.size, dtype, id_map, "id map")
+    g_sem = Guarded(sem.size, torch.int32, sem, "semantic map")
     shapes = {"ids": ((B, H, W), torch.int32), "table": ((B, max_inst, 8), torch.int32), "score": ((B, max_inst), torch.float32),
               "count": ((B,), torch.int32), "order": ((B, max_inst), torch.int32), "values": ((B, max_inst), torch.int32),
               "invalid": ((B,), torch.int32)}
-    outs = {k: Guarded(int(np.prod(s)), d) for k, (s, d) in shapes.items()}
+    outs = {k: Guarded(int(np.prod(s)), d, name=k) for k, (s, d) in shapes.items()}
     assert lib.mu_id_instances_supported(H, W, max_inst, class_cap) == 0
     nws = lib.mu_id_instances_workspace_bytes(B, H, W, max_inst, class_cap)
     assert nws > 0 and nws % 4 == 0
-    ws = Guarded(nws // 4, torch.int32)
-    _lib.call("mu_id_instances", g_map.p, code, g_sem.p, B, H, W, max_inst, class_cap, *[outs[k].p for k in OUT_KEYS], ws.p, nws,
-              _lib.stream())
-    torch.cuda.synchronize()
-    for name, g in [("id map", g_map), ("semantic map", g_sem), ("workspace", ws)] + list(outs.items()):
-        g.check(name)
-    got = {k: outs[k].t.cpu().numpy().reshape(shapes[k][0]) for k in OUT_KEYS}
+    call("mu_id_instances", g_map, code, g_sem, B, H, W, max_inst, class_cap, *[outs[k] for k in OUT_KEYS],
+         Guarded(nws // 4, torch.int32, name="workspace"), nws)
     for k in OUT_KEYS:
-        assert not (got[k] == SENT[shapes[k][1]]).any(), f"{k}: not every element was written"
-    return got
+        outs[k].all_written()
+    return {k: outs[k].host(shapes[k][0]) for k in OUT_KEYS}
 
 
 def same(got, ref):
@@ -188,11 +155,6 @@ def test_two_runs_are_bit_identical():
 
 
 # ------------------------------------------------------------------------------------------------
-def _side_of(inst):
-    names = {"ids": "ids", "count": "count", "table": "table", "score": "scores", "order": "order", "values": "values", "invalid": "invalid"}
-    return {k: getattr(inst, f).cpu().numpy() for k, f in names.items() if getattr(inst, f) is not None}
-
-
 @pytest.mark.parametrize("name", sorted(R.GOLDEN))
 def test_goldens_through_the_python_api(name):
     import maskunet_amd
@@ -200,7 +162,7 @@ def test_goldens_through_the_python_api(name):
     g = np.load(os.path.join(GOLDEN, name + ".npz"))
     inst = maskunet_amd.instances_from_id_map(torch.from_numpy(g["id_map"]).to(DEV), torch.from_numpy(g["sem"]).to(DEV), 64, 256)
     assert inst.prob is None and inst.classes.dtype == torch.int32 and np.array_equal(inst.classes.cpu().numpy(), g["sem"])
-    got = _side_of(inst)
+    got = side_of(inst)
     check_against_golden(got, g)
     same(got, R.instances(g["id_map"], g["sem"], 64, 256))
     for d, c, box in zip(inst.to_reference(0), g["category_id"], g["bbox"]):       # equal scores: ascending id = the reference's order
@@ -215,14 +177,14 @@ def test_python_api_dtypes_defaults_and_non_contiguous_inputs():
     assert not tv.is_contiguous() and not ts.is_contiguous()
     inst = maskunet_amd.instances_from_id_map(tv, ts)
     assert inst.table.shape == (2, 1024, 8) and inst.values.shape == (2, 1024) and inst.invalid.shape == (2,)
-    same(_side_of(inst), R.instances(v, sem, 1024, 256))
+    same(side_of(inst), R.instances(v, sem, 1024, 256))
     fits = np.clip(v, R.I32_MIN, R.I32_MAX)
     inst = maskunet_amd.instances_from_id_map(torch.from_numpy(fits.astype(np.int32)).to(DEV), torch.from_numpy(sem).to(DEV), 32, 19)
-    same(_side_of(inst), R.instances(fits, sem, 32, 19))
+    same(side_of(inst), R.instances(fits, sem, 32, 19))
     img = R.rgb_of(np.abs(fits) % (1 << 24))
     wide = torch.from_numpy(np.concatenate([img, img], -1)).to(DEV)[..., :3]       # a non-contiguous colour image
     assert not wide.is_contiguous()
-    same(_side_of(maskunet_amd.instances_from_id_map(wide, torch.from_numpy(sem).to(DEV), 32, 19)), R.instances(img, sem, 32, 19))
+    same(side_of(maskunet_amd.instances_from_id_map(wide, torch.from_numpy(sem).to(DEV), 32, 19)), R.instances(img, sem, 32, 19))
 
 
 def test_python_api_errors():
@@ -262,7 +224,7 @@ def test_match_instances_against_the_host_reference():
     gt = maskunet_amd.instances_from_id_map(torch.from_numpy(v).to(DEV), torch.from_numpy(sem).to(DEV), 64, C)
     pred = maskunet_amd.instances_from_labels(torch.from_numpy(np.roll(labels, 1, 2)).to(DEV), max_instances=256)
     m = maskunet_amd.match_instances(pred, gt, C, max_queries=200)
-    ref = MR.match(_side_of(pred), _side_of(gt), C, max_queries=200)
+    ref = MR.match(side_of(pred), side_of(gt), C, max_queries=200)
     print(f"coco matches per threshold {(ref['det_gt'] > 0).sum((0, 2)).tolist()}, panoptic {(ref['pq_gt'] > 0).sum()}")
     assert (ref["det_gt"][:, 0] > 0).sum() >= 20 and (ref["pq_gt"] > 0).sum() >= 20 and not ref["overflow"].any()
     for k in MATCH_KEYS:
@@ -300,7 +262,7 @@ def test_panoptic_quality_changes_with_the_ground_truth_partition():
 
 
 def test_coco_masks_ids_become_instances():
-    """what tests/test_gpu_poly.py::as_instances builds by hand around coco_masks(...).ids: ids, areas and counts"""
+    """what tests/test_gpu_poly.py::as_instances builds on the host around coco_masks(...).ids: ids, areas and counts"""
     import maskunet_amd
     rect = lambda x0, y0, x1, y1: [x0, y0, x1, y0, x1, y1, x0, y1]
     ann = [[[rect(2, 2, 14, 14)], [rect(10, 10, 20, 20)], [rect(15, 15, 30, 32)], [rect(40, 40, 50, 50)]], [[rect(1, 1, 9, 5)]], []]

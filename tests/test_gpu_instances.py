@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from tests import _cc_reference as R
+from tests._device_buffers import Guarded, call
 
 pytestmark = pytest.mark.gpu
 
@@ -23,27 +24,6 @@ FP32_ROUTE_ERROR = 1.50e-07          # measured, see the module docstring (measu
 GATE = 4 * FP32_ROUTE_ERROR          # 6.0e-07
 
 DEV = "cuda"
-GUARD = 1024                         # elements (4 KiB of int32 / fp32)
-SENT_I, SENT_F = -777, -777.0
-
-
-class Guarded:
-    """n elements between two guard bands; everything starts as the sentinel."""
-
-    def __init__(self, n, dtype, data=None):
-        self.n = n
-        self.sent = SENT_F if dtype.is_floating_point else SENT_I
-        self.buf = torch.full((n + 2 * GUARD,), self.sent, dtype=dtype, device=DEV)
-        if data is not None:
-            self.buf[GUARD:GUARD + n] = torch.as_tensor(data, dtype=dtype).reshape(-1).to(DEV)
-
-    @property
-    def t(self):
-        return self.buf[GUARD:GUARD + self.n]
-
-    def check(self, what):
-        assert bool((self.buf[:GUARD] == self.sent).all()), f"{what}: guard band BEFORE the buffer was written"
-        assert bool((self.buf[GUARD + self.n:] == self.sent).all()), f"{what}: guard band AFTER the buffer was written"
 
 
 def run_instances(cls, prob, max_inst):
@@ -51,29 +31,16 @@ def run_instances(cls, prob, max_inst):
     from maskunet_amd import _lib
     lib = _lib.load()
     B, H, W = cls.shape
-    g_cls = Guarded(B * H * W, torch.int32, cls)
-    g_prob = Guarded(B * H * W, torch.float32, prob) if prob is not None else None
-    g_ids = Guarded(B * H * W, torch.int32)
-    g_table = Guarded(B * max_inst * 8, torch.int32)
-    g_score = Guarded(B * max_inst, torch.float32)
-    g_count = Guarded(B, torch.int32)
-    g_order = Guarded(B * max_inst, torch.int32)
+    i32, f32 = torch.int32, torch.float32
+    g_cls = Guarded(B * H * W, i32, cls, "the class map")
+    g_prob = Guarded(B * H * W, f32, prob, "prob") if prob is not None else None
+    shapes = {"ids": ((B, H, W), i32), "table": ((B, max_inst, 8), i32), "score": ((B, max_inst), f32), "count": ((B,), i32),
+              "order": ((B, max_inst), i32)}
+    outs = {k: Guarded(int(np.prod(s)), d, name=k) for k, (s, d) in shapes.items()}
     nws = lib.mu_instances_workspace_bytes(B, H, W, max_inst)
     assert nws > 0 and nws % 4 == 0
-    g_ws = Guarded(nws // 4, torch.int32)
-    _lib.call("mu_instances", g_cls.t.data_ptr(), g_prob.t.data_ptr() if g_prob else None, B, H, W, max_inst, g_ids.t.data_ptr(),
-              g_table.t.data_ptr(), g_score.t.data_ptr(), g_count.t.data_ptr(), g_order.t.data_ptr(), g_ws.t.data_ptr(), nws, _lib.stream())
-    torch.cuda.synchronize()
-    for name, g in [("cls", g_cls), ("prob", g_prob), ("ids", g_ids), ("table", g_table), ("score", g_score), ("count", g_count),
-                    ("order", g_order), ("workspace", g_ws)]:
-        if g is not None:
-            g.check(name)
-    assert np.array_equal(g_cls.t.cpu().numpy().reshape(cls.shape), cls), "the class map is an input"
-    if prob is not None:
-        assert np.array_equal(g_prob.t.cpu().numpy().reshape(prob.shape), prob.astype(np.float32)), "prob is an input"
-    return {"ids": g_ids.t.cpu().numpy().reshape(B, H, W), "table": g_table.t.cpu().numpy().reshape(B, max_inst, 8),
-            "score": g_score.t.cpu().numpy().reshape(B, max_inst), "count": g_count.t.cpu().numpy(),
-            "order": g_order.t.cpu().numpy().reshape(B, max_inst)}
+    call("mu_instances", g_cls, g_prob, B, H, W, max_inst, *outs.values(), Guarded(nws // 4, i32, name="workspace"), nws)
+    return {k: outs[k].host(shapes[k][0]) for k in shapes}
 
 
 def grid_prob(shape, seed):
@@ -251,15 +218,12 @@ def run_argmax(x, dtype, layout, want_prob=True, temperature=0.5):
         data = np.full((M, Cp), 100.0)
         data[:, :C] = x
         n, args = data.size, (M, 0, 1, Cp)
-    g_x = Guarded(n, tdt, data)
-    g_cls = Guarded(M, torch.int32)
-    g_prob = Guarded(M, torch.float32)
-    _lib.call("mu_argmax_prob", g_x.t.data_ptr(), M, C, *args, 1.0 / temperature, g_cls.t.data_ptr(),
-              g_prob.t.data_ptr() if want_prob else None, _lib.dt(tdt), _lib.stream())
-    torch.cuda.synchronize()
-    for name, g in [("logits", g_x), ("cls", g_cls), ("prob", g_prob)]:
-        g.check(name)
-    return g_cls.t.cpu().numpy(), g_prob.t.cpu().numpy()
+    g_x = Guarded(n, tdt, data, "logits")
+    g_cls = Guarded(M, torch.int32, name="cls")
+    g_prob = Guarded(M, torch.float32, name="prob")
+    call("mu_argmax_prob", g_x, M, C, *args, 1.0 / temperature, g_cls, g_prob if want_prob else None, _lib.dt(tdt))
+    g_prob.check()
+    return g_cls.host(), g_prob.host()
 
 
 @pytest.mark.parametrize("layout", ["nchw", "nhwc"])
@@ -284,7 +248,7 @@ def test_argmax_layouts_agree_bit_for_bit_and_prob_is_optional():
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.int32), b[1].view(np.int32))
     assert np.array_equal(a[1].view(np.int32), c[1].view(np.int32))
     cls, prob = run_argmax(x, "fp32", "nhwc", want_prob=False)
-    assert np.array_equal(cls, a[0]) and (prob == SENT_F).all()
+    assert np.array_equal(cls, a[0]) and (prob == -777.0).all()          # still the sentinel
 
 
 def measure_fp32_route_error():

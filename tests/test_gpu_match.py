@@ -11,41 +11,14 @@ import pytest
 import torch
 
 from tests import _match_reference as R
+from tests._device_buffers import Guarded, call, side_of
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-GUARD_BYTES = 4096
-SENT = -777
 EPS = 2.0 ** -53
 OUT_KEYS = ("det_valid", "det_class", "det_score", "det_gt", "det_iou", "gt_per_class", "pq_gt", "pq_iou", "pq_fp", "overflow",
             "pairs", "n_pairs")
-
-
-class Guarded:
-    """n elements between two guard bands; everything starts as the sentinel."""
-
-    def __init__(self, n, dtype, data=None):
-        self.n, self.g = n, GUARD_BYTES // torch.empty(0, dtype=dtype).element_size()
-        self.buf = torch.full((n + 2 * self.g,), SENT, dtype=dtype, device=DEV)
-        self.data = None
-        if data is not None:
-            self.data = torch.as_tensor(np.ascontiguousarray(data)).to(dtype).reshape(-1)
-            self.buf[self.g:self.g + n] = self.data.to(DEV)
-
-    @property
-    def t(self):
-        return self.buf[self.g:self.g + self.n]
-
-    @property
-    def p(self):
-        return self.t.data_ptr()
-
-    def check(self, what):
-        assert bool((self.buf[:self.g] == SENT).all()), f"{what}: guard band BEFORE the buffer was written"
-        assert bool((self.buf[self.g + self.n:] == SENT).all()), f"{what}: guard band AFTER the buffer was written"
-        if self.data is not None:
-            assert torch.equal(self.t.cpu(), self.data), f"{what} is an input"
 
 
 def run_match(pred, gt, num_classes, thresholds=None, max_queries=None, max_dets=100):
@@ -57,28 +30,24 @@ def run_match(pred, gt, num_classes, thresholds=None, max_queries=None, max_dets
     Mp, Mg, T, N = pred["table"].shape[1], gt["table"].shape[1], len(thr), H * W
     K = Mp if max_queries is None else min(max_queries, Mp)
     i32, f32, f64 = torch.int32, torch.float32, torch.float64
-    ins = {"pred ids": Guarded(B * N, i32, pred["ids"]), "gt ids": Guarded(B * N, i32, gt["ids"]),
-           "pred table": Guarded(B * Mp * 8, i32, pred["table"]), "pred score": Guarded(B * Mp, f32, pred["score"]),
-           "pred order": Guarded(B * Mp, i32, pred["order"]), "pred count": Guarded(B, i32, pred["count"]),
-           "gt table": Guarded(B * Mg * 8, i32, gt["table"]), "gt count": Guarded(B, i32, gt["count"])}
+    sizes = {"ids": (B * N, i32), "table": (B * Mp * 8, i32), "score": (B * Mp, f32), "order": (B * Mp, i32), "count": (B, i32)}
+    p_in = {k: Guarded(n, d, pred[k], "pred " + k) for k, (n, d) in sizes.items()}
+    g_in = {k: Guarded(n, i32, gt[k], "gt " + k) for k, n in (("ids", B * N), ("table", B * Mg * 8), ("count", B))}
     shapes = {"det_valid": ((B, K), i32), "det_class": ((B, K), i32), "det_score": ((B, K), f32), "det_gt": ((B, T, K), i32),
               "det_iou": ((B, T, K), f64), "gt_per_class": ((B, num_classes), i32), "pq_gt": ((B, K), i32), "pq_iou": ((B, K), f64),
               "pq_fp": ((B, K), i32), "overflow": ((B,), i32), "pairs": ((B, N, 3), i32), "n_pairs": ((B,), i32)}
-    outs = {k: Guarded(int(np.prod(s)), d) for k, (s, d) in shapes.items()}
+    outs = {k: Guarded(int(np.prod(s)), d, name=k) for k, (s, d) in shapes.items()}
     nws1 = lib.mu_instance_pairs_workspace_bytes(B, H, W, Mp, Mg)
     nws2 = lib.mu_instance_match_workspace_bytes(B, K)
     assert nws1 > 0 and nws1 % 4 == 0 and nws2 == B * K * 4
-    ws1, ws2 = Guarded(nws1 // 4, i32), Guarded(nws2 // 4, i32)
+    ws1, ws2 = Guarded(nws1 // 4, i32, name="pair workspace"), Guarded(nws2 // 4, i32, name="match workspace")
     assert lib.mu_instance_match_supported(H, W, Mp, Mg, num_classes, K, max_dets, T) == 0
-    _lib.call("mu_instance_pairs", ins["pred ids"].p, ins["gt ids"].p, B, H, W, Mp, Mg, outs["pairs"].p, outs["n_pairs"].p, ws1.p, nws1,
-              _lib.stream())
-    _lib.call("mu_instance_match", outs["pairs"].p, outs["n_pairs"].p, ins["pred table"].p, ins["pred score"].p, ins["pred order"].p,
-              ins["pred count"].p, ins["gt table"].p, ins["gt count"].p, B, H, W, Mp, Mg, num_classes, K, max_dets, thr.ctypes.data, T,
-              *[outs[k].p for k in OUT_KEYS[:10]], ws2.p, nws2, _lib.stream())
-    torch.cuda.synchronize()
-    for name, g in list(ins.items()) + list(outs.items()) + [("pair workspace", ws1), ("match workspace", ws2)]:
-        g.check(name)
-    return {k: outs[k].t.cpu().numpy().reshape(shapes[k][0]) for k in OUT_KEYS}
+    call("mu_instance_pairs", p_in["ids"], g_in["ids"], B, H, W, Mp, Mg, outs["pairs"], outs["n_pairs"], ws1, nws1)
+    call("mu_instance_match", outs["pairs"], outs["n_pairs"], p_in["table"], p_in["score"], p_in["order"], p_in["count"], g_in["table"],
+         g_in["count"], B, H, W, Mp, Mg, num_classes, K, max_dets, thr.ctypes.data, T, *[outs[k] for k in OUT_KEYS[:10]], ws2, nws2)
+    for g in (*p_in.values(), *g_in.values(), *outs.values(), ws1, ws2):       # and every buffer again after the second launch
+        g.check()
+    return {k: outs[k].host(shapes[k][0]) for k in OUT_KEYS}
 
 
 def compare(got, ref):
@@ -308,11 +277,6 @@ def test_two_runs_are_bit_identical():
 
 
 # ------------------------------------------------------------------------------------------------
-def _side_of(inst):
-    return {"ids": inst.ids.cpu().numpy(), "count": inst.count.cpu().numpy(), "table": inst.table.cpu().numpy(),
-            "score": inst.scores.cpu().numpy(), "order": inst.order.cpu().numpy()}
-
-
 def _match_on_reference_lists(pred, gt, num_classes, max_queries, max_dets):
     """the restatement on the masks, categories and scores that Instances.to_reference() hands out"""
     B = pred.ids.shape[0]
@@ -349,7 +313,7 @@ def test_end_to_end_two_updates():
         acc_ap.update(m)
         acc_pq.update(m)
         assert not bool(m.overflow.any())
-        ref = R.match(_side_of(pred), _side_of(gt), C, max_queries=Q)
+        ref = R.match(side_of(pred), side_of(gt), C, max_queries=Q)
         got = {k: getattr(m, k).cpu().numpy() for k in OUT_KEYS}
         compare(got, ref)
         lists = _match_on_reference_lists(pred, gt, C, Q, 100)

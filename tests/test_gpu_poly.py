@@ -10,46 +10,18 @@ import pytest
 import torch
 
 from tests import _poly_reference as R
+from tests._device_buffers import Guarded, call
+from tests._instances_reference import table_from_ids
 from tests.test_poly_host import TIE_X, TIE_Y, unscaled
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-GUARD_BYTES = 4096
-SENT = {torch.int32: -777, torch.uint8: 0xA5, torch.int64: -777, torch.float64: -777.0}
 OUT_KEYS = ("cover", "ids", "masks", "area", "valid")
 IN_KEYS = ("xy", "poly_offsets", "ann_poly_offsets", "rle_counts", "ann_rle_offsets", "img_ann_offsets", "sizes")
 OUT_SIZES = [(128, 128), (3, 5), (96, 80)]             # the reference's; tiny; larger than five of the source sizes (upsampling)
 MAX_POINTS = 100000                                    # every legitimate polygon of the batch stays below, one row walks 120 000
 OVER_LIMIT = (1024, 513)                               # h * w = 2^19 + 1024
-
-
-class Guarded:
-    """n elements between two guard bands; everything starts as the sentinel."""
-
-    def __init__(self, n, dtype, data=None):
-        self.n, self.g, self.sent = n, GUARD_BYTES // torch.empty(0, dtype=dtype).element_size(), SENT[dtype]
-        self.buf = torch.full((n + 2 * self.g,), self.sent, dtype=dtype, device=DEV)
-        self.data = None
-        if data is not None:
-            self.data = torch.as_tensor(np.ascontiguousarray(data)).to(dtype).reshape(-1)
-            assert self.data.numel() == n
-            self.buf[self.g:self.g + n] = self.data.to(DEV)
-
-    @property
-    def t(self):
-        return self.buf[self.g:self.g + self.n]
-
-    @property
-    def p(self):
-        return self.t.data_ptr() if self.n else None
-
-    def check(self, what):
-        assert bool((self.buf[:self.g] == self.sent).all()), f"{what}: guard band BEFORE the buffer was written"
-        assert bool((self.buf[self.g + self.n:] == self.sent).all()), f"{what}: guard band AFTER the buffer was written"
-        if self.data is not None:
-            bits = (lambda t: t.view(torch.int64)) if self.data.dtype == torch.float64 else (lambda t: t)      # NaN is a legal input
-            assert torch.equal(bits(self.t.cpu()), bits(self.data)), f"{what} is an input"
 
 
 def rect(x0, y0, x1, y1):
@@ -129,23 +101,19 @@ def run_raw(p, out_hw, max_points=MAX_POINTS, masks=True):
     Ho, Wo = out_hw
     B, A, P = p["sizes"].shape[0], p["ann_poly_offsets"].size - 1, p["poly_offsets"].size - 1
     dt = {"xy": torch.float64}
-    ins = {k: Guarded(p[k].size, dt.get(k, torch.int32), p[k]) for k in IN_KEYS}
+    ins = [Guarded(p[k].size, dt.get(k, torch.int32), p[k], k) for k in IN_KEYS]
     shapes = {"cover": ((B, Ho, Wo), torch.int64), "ids": ((B, Ho, Wo), torch.int32), "masks": ((A, Ho, Wo), torch.uint8),
               "area": ((A,), torch.int32), "valid": ((A,), torch.int32)}
-    outs = {k: Guarded(int(np.prod(s)), d) for k, (s, d) in shapes.items()}
+    outs = {k: Guarded(int(np.prod(s)), d, name=k) for k, (s, d) in shapes.items()}
     assert lib.mu_coco_masks_supported(Ho, Wo, max_points) == 0
     nws = lib.mu_coco_masks_workspace_bytes(B, A, Ho, Wo)
     assert nws >= 0
-    ws = Guarded(nws, torch.uint8)
-    _lib.call("mu_coco_masks", *[ins[k].p for k in IN_KEYS], B, A, P, p["xy"].size // 2, p["rle_counts"].size, Ho, Wo, max_points,
-              outs["cover"].p, outs["ids"].p, outs["masks"].p if masks else None, outs["area"].p, outs["valid"].p, ws.p, nws,
-              _lib.stream())
-    torch.cuda.synchronize()
-    for name, g in list(ins.items()) + list(outs.items()) + [("workspace", ws)]:
-        g.check(name)
+    call("mu_coco_masks", *ins, B, A, P, p["xy"].size // 2, p["rle_counts"].size, Ho, Wo, max_points, outs["cover"], outs["ids"],
+         outs["masks"] if masks else None, outs["area"], outs["valid"], Guarded(nws, torch.uint8, name="workspace"), nws)
     if not masks:
-        assert bool((outs["masks"].t == SENT[torch.uint8]).all())
-    return {k: outs[k].t.cpu().numpy().reshape(shapes[k][0]) for k in OUT_KEYS}
+        outs["masks"].check()
+        assert bool((outs["masks"].t == outs["masks"].sent).all())
+    return {k: outs[k].host(shapes[k][0]) for k in OUT_KEYS}
 
 
 def same(got, ref, keys=OUT_KEYS):
@@ -251,18 +219,11 @@ def test_bad_arguments_touch_nothing():
 
 
 def as_instances(ids):
-    """an Instances around an id map whose ids are 1..count per image: class 1, area from the map"""
+    """an Instances around an id map whose ids are 1..count per image: class 1, the table of the shared restatement"""
     from maskunet_amd import Instances
-    B, M = ids.shape[0], 16
-    count = ids.view(B, -1).max(1).values.to(torch.int32)
-    table = torch.zeros((B, M, 8), dtype=torch.int32, device=ids.device)
-    for b in range(B):
-        n = int(count[b])
-        table[b, :n, 0] = 1
-        table[b, :n, 1] = torch.bincount(ids[b].view(-1).long(), minlength=M + 1)[1:n + 1].to(torch.int32)
-    order = torch.arange(1, M + 1, dtype=torch.int32, device=ids.device)[None].repeat(B, 1)
-    order = torch.where(order <= count[:, None], order, torch.zeros_like(order))
-    return Instances((ids > 0).to(torch.int32), ids.contiguous(), table, (order > 0).float(), count, order)
+    r = table_from_ids(ids.cpu().numpy(), [[1] * 16] * ids.shape[0], 16)
+    table, score, count, order = (torch.from_numpy(r[k]).to(ids.device) for k in ("table", "score", "count", "order"))
+    return Instances((ids > 0).to(torch.int32), ids.contiguous(), table, score.float(), count, order)
 
 
 def test_ids_feed_match_instances_and_cover_feeds_the_loss():

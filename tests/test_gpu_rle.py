@@ -10,41 +10,13 @@ import pytest
 import torch
 
 from tests import _rle_reference as R
+from tests._device_buffers import Guarded, call
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-GUARD_BYTES = 4096
-SENT = {torch.int32: -777, torch.uint8: 0xA5}
 ENC_KEYS = ("offsets", "counts", "area", "str_offsets", "str_bytes")
 MU_ERR_SHAPE = -2
-
-
-class Guarded:
-    """n elements between two guard bands; everything starts as the sentinel."""
-
-    def __init__(self, n, dtype, data=None):
-        self.n, self.g, self.sent = n, GUARD_BYTES // torch.empty(0, dtype=dtype).element_size(), SENT[dtype]
-        self.buf = torch.full((n + 2 * self.g,), self.sent, dtype=dtype, device=DEV)
-        self.data = None
-        if data is not None:
-            self.data = torch.as_tensor(np.ascontiguousarray(data)).to(dtype).reshape(-1)
-            assert self.data.numel() == n
-            self.buf[self.g:self.g + n] = self.data.to(DEV)
-
-    @property
-    def t(self):
-        return self.buf[self.g:self.g + self.n]
-
-    @property
-    def p(self):
-        return self.t.data_ptr()
-
-    def check(self, what):
-        assert bool((self.buf[:self.g] == self.sent).all()), f"{what}: guard band BEFORE the buffer was written"
-        assert bool((self.buf[self.g + self.n:] == self.sent).all()), f"{what}: guard band AFTER the buffer was written"
-        if self.data is not None:
-            assert torch.equal(self.t.cpu(), self.data), f"{what} is an input"
 
 
 def run_encode(ids, sel, max_id):
@@ -54,19 +26,15 @@ def run_encode(ids, sel, max_id):
     B, H, W = ids.shape
     K, L = sel.shape[1], 2 * H * W + sel.shape[1]
     i32, u8 = torch.int32, torch.uint8
-    ins = {"ids": Guarded(B * H * W, i32, ids), "sel": Guarded(B * K, i32, sel)}
+    g_ids, g_sel = Guarded(B * H * W, i32, ids, "ids"), Guarded(B * K, i32, sel, "sel")
     shapes = {"offsets": ((B, K + 1), i32), "counts": ((B, L), i32), "area": ((B, K), i32), "str_offsets": ((B, K + 1), i32),
               "str_bytes": ((B, 4 * L), u8)}
-    outs = {k: Guarded(int(np.prod(s)), d) for k, (s, d) in shapes.items()}
+    outs = {k: Guarded(int(np.prod(s)), d, name=k) for k, (s, d) in shapes.items()}
     assert lib.mu_rle_encode_supported(H, W, K, max_id) == 0
     nws = lib.mu_rle_encode_workspace_bytes(B, H, W, K, max_id)
     assert nws > 0 and nws % 4 == 0
-    ws = Guarded(nws // 4, i32)
-    _lib.call("mu_rle_encode", ins["ids"].p, ins["sel"].p, B, H, W, K, max_id, *[outs[k].p for k in ENC_KEYS], ws.p, nws, _lib.stream())
-    torch.cuda.synchronize()
-    for name, g in list(ins.items()) + list(outs.items()) + [("workspace", ws)]:
-        g.check(name)
-    return {k: outs[k].t.cpu().numpy().reshape(shapes[k][0]) for k in ENC_KEYS}
+    call("mu_rle_encode", g_ids, g_sel, B, H, W, K, max_id, *[outs[k] for k in ENC_KEYS], Guarded(nws // 4, i32, name="workspace"), nws)
+    return {k: outs[k].host(shapes[k][0]) for k in ENC_KEYS}
 
 
 def run_decode(offsets, counts, H, W):
@@ -75,14 +43,11 @@ def run_decode(offsets, counts, H, W):
     lib = _lib.load()
     B, K, Lc = offsets.shape[0], offsets.shape[1] - 1, counts.shape[1]
     i32 = torch.int32
-    ins = {"offsets": Guarded(B * (K + 1), i32, offsets), "counts": Guarded(B * Lc, i32, counts)}
-    outs = {"ids": Guarded(B * H * W, i32), "valid": Guarded(B * K, i32)}
+    g_off, g_cnt = Guarded(B * (K + 1), i32, offsets, "offsets"), Guarded(B * Lc, i32, counts, "counts")
+    g_ids, g_valid = Guarded(B * H * W, i32, name="ids"), Guarded(B * K, i32, name="valid")
     assert lib.mu_rle_decode_supported(H, W, K) == 0
-    _lib.call("mu_rle_decode", ins["offsets"].p, ins["counts"].p, B, H, W, K, Lc, outs["ids"].p, outs["valid"].p, _lib.stream())
-    torch.cuda.synchronize()
-    for name, g in list(ins.items()) + list(outs.items()):
-        g.check(name)
-    return outs["ids"].t.cpu().numpy().reshape(B, H, W), outs["valid"].t.cpu().numpy().reshape(B, K)
+    call("mu_rle_decode", g_off, g_cnt, B, H, W, K, Lc, g_ids, g_valid)
+    return g_ids.host((B, H, W)), g_valid.host((B, K))
 
 
 def restricted(ids, sel, max_id):
