@@ -477,6 +477,33 @@ long mu_id_instances_workspace_bytes(int B, int H, int W, int max_inst, int clas
 int mu_id_instances(const void* id_map, int id_kind, const int* sem, int B, int H, int W, int max_inst, int class_cap, int* ids,
                     int* table, float* score, int* count, int* order, int* values, int* invalid, void* workspace, long ws_bytes,
                     void* stream);
+/* Semantic evaluation of one validation batch in ONE read of the logits: what the validation loops take from `outputs` --
+ * criterion(outputs, labels) (ade_semantic.py:454; ignore_index = 255: city_semantic.py:341), mean_iou(outputs, labels, c_out)
+ * (city_panoptic.py:225-236, ade_semantic.py:128-146), compute_iou_for_image per image (city_panoptic.py:212-222) and
+ * softmax(outputs / 0.5) + argmax (ade_instance.py:408-411) -- and the confusion matrix their sklearn precision / recall / F1 are
+ * functions of.  Element (pixel r of M = B * HW, class c) at logits[(r / inner) * outer_stride + c * c_stride + (r % inner) * p_stride],
+ * exactly as mu_mean_iou / mu_argmax_prob; the image of r is r / HW; labels int64 [M]; the logits must be finite.
+ *   pred[r]    the first maximum over the C real channels (torch.argmax); padded channels are never read into the maximum;
+ *   void       row r is void if labels[r] == ignore_index or labels[r] lies outside [0, C);
+ *   img_counts int32 [B,3,C], overwritten: per image I_c = #(pred == c and label == c), P_c = #(pred == c), L_c = #(label == c).
+ *              P counts every pixel, void ones too; I and L only non-void ones -- what mean_iou and compute_iou_for_image count (a
+ *              label of 255 equals no class, but the prediction at that pixel still enters the union);
+ *   confusion  int64 [C+1,C], ADDED TO (the caller zeroes it once and accumulates a validation set): row = the label, or C for void;
+ *              column = pred.  Column sums are sum_b P_c, the sum of row c is sum_b L_c, the diagonal is sum_b I_c;
+ *   img_loss   fp64 [B,2], overwritten: {sum over the non-void rows of image b of lse_r - x[r, label_r], the number of such rows}; lse
+ *              in fp32 as mu_ce_fwd; the sums in a fixed order (per-block fp64 partials in the workspace, then an ordered finalize);
+ *   cls int32 [M], prob fp32 [M], each may be null: pred, and 1 / sum_c exp((x_c - x_max) * inv_temperature) as mu_argmax_prob.
+ * Integer atomics only: every output is bit-identical from run to run.  The (C+1) x C counters are privatised in LDS per workgroup
+ * for C <= MU_SEM_EVAL_LDS_MAX_C and flushed with 64-bit atomics; above it every pixel adds to the global matrix.
+ * Null required pointers, B < 1, HW < 1, HW >= 2^31, inner < 1, a dtype other than MU_F32 / MU_F16 or inv_temperature <= 0:
+ * MU_ERR_ARG; C outside [1, 4096]: MU_ERR_SHAPE (mu_sem_eval_supported); a short workspace: MU_ERR_WORKSPACE; all before the first
+ * launch.  mu_sem_eval_supported and mu_sem_eval_workspace_bytes are host only; the latter is 0 for unsupported shapes. */
+#define MU_SEM_EVAL_LDS_MAX_C 192
+int mu_sem_eval_supported(int C);
+long mu_sem_eval_workspace_bytes(int B, long HW, int C);
+int mu_sem_eval(const void* logits, const long* labels, int B, long HW, int C, long inner, long outer_stride, long c_stride,
+                long p_stride, long ignore_index, float inv_temperature, int* img_counts, double* img_loss, long* confusion,
+                int* cls_or_null, float* prob_or_null, void* workspace, long ws_bytes, int dtype, void* stream);
 /* Instance matching: what evaluate_instances / evaluate_panoptic_metrics (ade_panoptic.py:520-586, city_instance.py:451-500) hand to
  * pycocotools and panopticapi, restated from the published algorithms (COCOeval.evaluateImg, maskUtils.iou, panopticapi's
  * pq_compute_single_core) on id maps; no RLE.  Not pinned to those packages.

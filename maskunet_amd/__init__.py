@@ -11,6 +11,7 @@ from .losses import CrossEntropyLoss, InstanceContrastiveLoss, cross_entropy, me
 from .instances import (Instances, generate_instance_mask, instances_from_embeddings, instances_from_id_map, instances_from_labels,
                         predict_instances)
 from .matching import InstanceAP, Matches, PanopticQuality, match_instances
+from .metrics import SemanticBatch, SemanticMetrics, metrics_from_counts, semantic_eval
 from .rle import RLEs, decode_rle, encode_rle, rle_counts_from_string, rle_string_from_counts
 from .coco import CocoMasks, coco_masks
 from .ops import resize_labels_u8, resize_u8_to_nhwc
@@ -24,5 +25,6 @@ __all__ = ["ConvBlock", "DownSample", "UpSample", "Mask2FormerAttention", "UNet"
            "resize_u8_to_nhwc", "resize_labels_u8", "set_float32_matmul_precision", "get_float32_matmul_precision", "predict_instances",
            "instances_from_labels", "generate_instance_mask", "Instances", "instances_from_embeddings", "match_instances", "Matches",
            "InstanceAP", "PanopticQuality", "RLEs", "encode_rle", "decode_rle", "rle_counts_from_string", "rle_string_from_counts",
-           "coco_masks", "CocoMasks", "instances_from_id_map"]
+           "coco_masks", "CocoMasks", "instances_from_id_map", "semantic_eval", "SemanticBatch", "SemanticMetrics",
+           "metrics_from_counts"]
 __version__ = "0.1.0"

@@ -94,6 +94,9 @@ SIGNATURES = {
     "mu_ce_nchw_fwd": (I, [P, P, I, I, L, L, P, P, P, P, L, I, P]),
     "mu_ce_nchw_bwd": (I, [P, P, P, P, P, F, I, I, L, L, P, I, P]),
     "mu_mean_iou": (I, [P, P, L, I, L, L, L, L, F, P, P, I, P]),
+    "mu_sem_eval_supported": (I, [I]),
+    "mu_sem_eval_workspace_bytes": (L, [I, L, I]),
+    "mu_sem_eval": (I, [P, P, I, L, I, L, L, L, L, L, F, P, P, P, P, P, P, L, I, P]),
     "mu_inst_triplet_workspace_bytes": (L, [I, I]),
     "mu_inst_triplet_fwd": (I, [P, P, I, I, I, I, I, F, P, I, I, P, L, P, P]),
     "mu_inst_triplet_bwd": (I, [P, I, I, I, I, P, I, I, P, P, P]),
