@@ -274,7 +274,9 @@ int mu_ln_sample_bwd(const void* x, const void* dy, const float* w, const float*
                      float* db, int B, long L, void* workspace, long ws_bytes, int dtype, void* stream);
 
 /* ---- pooling / resampling -------------------------------------------------------------------- */
-/* nn.MaxPool2d(2) (:216); backward recomputes the arg-max (first maximum in scan order) */
+/* nn.MaxPool2d(2) (:216); backward recomputes the arg-max (first maximum in scan order).  NaN as in aten: the scan over
+ * (0,0), (0,1), (1,0), (1,1) updates on `t > m || isnan(t)`, so a window that holds a NaN pools to NaN and its gradient goes to the
+ * last NaN of the window.  Odd H / W floor; the uncovered last row / column gets a zero gradient (plus dx_add). */
 int mu_maxpool2_fwd(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream);
 int mu_maxpool2_bwd(const void* x, const void* dy, void* dx, int B, int H, int W, int C, int dtype, void* stream);
 /* mu_maxpool2_bwd with gradient joins that autograd would otherwise run as separate elementwise kernels: dy2 (may be NULL, pooled

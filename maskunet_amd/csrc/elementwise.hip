@@ -451,7 +451,14 @@ extern "C" int mu_split_encode(const void* src, void* dst, long n_elems, void* s
 // ------------------------------------------------------------------------------------------
 // MaxPool2d(2), NHWC.  Backward recomputes the arg-max from x (first maximum in (kh,kw) scan
 // order, the aten tie rule) so no index tensor is stored; windows are disjoint -> no atomics.
+// NaN follows aten as well: the scan over (0,0), (0,1), (1,0), (1,1) updates on `t > m || t != t`, so a window that holds a NaN
+// pools to NaN (fmaxf would drop it, and with it the overflow a later finite check is there to see) and its gradient goes to the
+// LAST NaN of the window.  Forward and backward run the same scan.
 // ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void pool_scan(float t, int k, float& m, int& best) {
+    if (t > m || t != t) { m = t; best = k; }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int B, int H, int W, int C) {
     constexpr int N = Vec16<T>::N;
@@ -465,7 +472,14 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const T* __restrict__ 
         Vec16<T> v00, v01, v10, v11, o;
         v00.load_nt(base); v01.load_nt(base + C); v10.load_nt(base + (long)W * C); v11.load_nt(base + (long)W * C + C);
 #pragma unroll
-        for (int i = 0; i < N; ++i) o.set(i, fmaxf(fmaxf(v00.get(i), v01.get(i)), fmaxf(v10.get(i), v11.get(i))));
+        for (int i = 0; i < N; ++i) {
+            int best = 0;
+            float m = v00.get(i);
+            pool_scan(v01.get(i), 1, m, best);
+            pool_scan(v10.get(i), 2, m, best);
+            pool_scan(v11.get(i), 3, m, best);
+            o.set(i, m);
+        }
         o.store(y + p * C + c);
     }
 }
@@ -496,10 +510,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ 
             int best = 0;
             float m = v[0].get(i);
 #pragma unroll
-            for (int k = 1; k < 4; ++k) {
-                float t = v[k].get(i);
-                if (t > m) { m = t; best = k; }
-            }
+            for (int k = 1; k < 4; ++k) pool_scan(v[k].get(i), k, m, best);
             float gi = g.get(i);
             if (dy2) gi += g2.get(i);
 #pragma unroll
