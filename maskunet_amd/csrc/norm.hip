@@ -2,8 +2,13 @@
 // Reference ops replaced: nn.BatchNorm2d / nn.GELU / F.gelu(x + block(x)) in ConvBlock
 // (ade_semantic.py:198-210), the trailing BatchNorm2d of DownSample/UpSample (:219,240),
 // final_layer BN+ReLU (:285-286) and nn.LayerNorm([64,128,128]) (:281,311).
-// Statistics are accumulated in fp64 (sum, sum of squares) so the biased variance is exact to
-// fp32 rounding regardless of mean/variance ratio; everything else is fp32 math on T storage.
+// BatchNorm statistics (sum, sum of squares): every thread sums U = 8 rows in fp32 (7 adds, 8 fmaf) and folds these short sums into
+// fp64 accumulators; everything behind the fold is fp64.  The fp32 roundings are relative to the short sums, i.e. to E[x^2], not to
+// the variance: |mean error| <= 2^-24 |m| + 8 * 2^-24 mean|x| and |biased variance error| <= 24 * 2^-24 E[x^2] (derived in
+// tests/_norm_reference.py bn_stats_bounds, held by tests/test_gpu_norm_edges.py).  At mean / std = r that is up to
+// 24 * 2^-24 (1 + r^2) of the variance -- fp32-exact for the zero-centred activations of this model, not "regardless of the
+// mean / variance ratio" (NOTES_r12.md has the measured error by ratio).  The statistics-from-rows path and the per-sample LayerNorm
+// accumulate every term in fp64 and keep 2^-23 at any ratio.  Everything else is fp32 math on T storage.
 #include "common.h"
 // Nontemporal loads of the streamed operands of bn_act_fwd (x), bn_bwd_apply, the residual operand and the per-sample LayerNorm apply
 // passes: the passes touch every byte once per launch; `nt` loads bypass the CU's L1 (MI355X_MICROARCH: L2-served).  Whole step
@@ -313,7 +318,12 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const T* __restrict__ x
                     o.set(i + 1, o1);
                 }
                 if constexpr (ENC) {
-                    const uint4 e4 = mu_ench4((f32x4){o.get(0), o.get(1), o.get(2), o.get(3)});
+                    // the encoding is that of the ROUNDED fp32 outputs, the values the plain kernel stores.  Without the (empty) asm the compiler
+                    // folds GELU's last product into the two conversions (v_fma_mix: hi = fp16 of the unrounded product, lo from fma(a, b, -hi)),
+                    // and the halves are a unit apart from mu_split_encode_h4 of the plain output (tests/test_gpu_norm_edges.py)
+                    float o0 = o.get(0), o1 = o.get(1), o2 = o.get(2), o3 = o.get(3);
+                    asm("" : "+v"(o0), "+v"(o1), "+v"(o2), "+v"(o3));
+                    const uint4 e4 = mu_ench4((f32x4){o0, o1, o2, o3});
                     *reinterpret_cast<uint4*>(y + (r + u * rstep) * ld + c) = e4;
                     if (y16) *reinterpret_cast<uint2*>(y16 + (r + u * rstep) * (long)C + c) = make_uint2(e4.x, e4.y);
                 } else {
