@@ -92,7 +92,7 @@ class GraphedStep:
     def _capture_segmented(self):
         """The step as TWO graphs sharing one memory pool, split INSIDE the single backward pass (a collective cannot be captured on this
         stack: tools/probe_graph_rccl.py dumps core): the gradient hook of ops.cut_point -- it fires when every node behind the cut has
-        run -- ends the first capture and begins the second.  One backward pass, so ops.GradLink / EncLink pairs across the cut keep
+        run -- ends the first capture and begins the second.  One backward pass, so ops.GradLink pairs across the cut keep
         working.  Replay: graph 1, the all-reduces of the buckets it completed (comm stream), graph 2 beside them, the rest."""
         import gc
         dev = self.inputs.device

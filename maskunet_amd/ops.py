@@ -9,6 +9,8 @@ from __future__ import annotations
 
 import math
 import os
+from types import SimpleNamespace
+from typing import NamedTuple
 
 import torch
 import torch.nn.functional as F
@@ -35,50 +37,52 @@ def _is_x(t_or_dtype) -> bool:
     return mdt(t_or_dtype) == _lib.MU_F32X
 
 
+def _enc_for(t, taps):
+    """fp32x: chunk-encoded copy of a matrix operand for the MU_F32X entry points (include/maskunet_hip.h), in the encoding a layer with
+    `taps` taps reads -- fp16 pairs ([4 fp16 hi | 4 fp16 lo] per chunk, round 6) for the 3x3 layers, bf16 pairs for 1x1 / Linear; the
+    tensor itself otherwise."""
+    if not _is_x(t):
+        return t
+    t = t.contiguous()
+    e = torch.empty_like(t)
+    call("mu_split_encode_h4" if taps == 9 else "mu_split_encode", ptr(t), ptr(e), t.numel(), stream())
+    return e
+
+
 def _enc(t):
-    """Chunk-encoded copy of a matrix operand for the MU_F32X entry points (include/maskunet_hip.h); the tensor itself otherwise."""
-    if not _is_x(t):
-        return t
-    t = t.contiguous()
-    e = torch.empty_like(t)
-    call("mu_split_encode", ptr(t), ptr(e), t.numel(), stream())
-    return e
+    return _enc_for(t, 1)
 
 
-def _enc3(t):
-    """fp32x: the 3x3-convolution operand encoding ([4 fp16 hi | 4 fp16 lo] per chunk, round 6) of an activation; the tensor itself otherwise."""
-    if not _is_x(t):
-        return t
-    t = t.contiguous()
-    e = torch.empty_like(t)
-    call("mu_split_encode_h4", ptr(t), ptr(e), t.numel(), stream())
-    return e
+class _Enc3(NamedTuple):
+    """fp32x: an activation as the 3x3 conv behind it reads it -- the chunk-encoded operand `e` of the forward conv and the fp16 rounding
+    `h` (plain rows) its backward keeps for the one-term weight gradient (mu_conv_wgrad_h1)."""
+    e: torch.Tensor
+    h: torch.Tensor
+
+
+class _DyH(NamedTuple):
+    """fp32x: the dy of a 3x3 conv as ONE power-of-two-scaled fp16 operand `h` with its device-side scale pair {S, 1 / S}."""
+    h: torch.Tensor
+    scale: torch.Tensor
 
 
 def _enc3x(t):
-    """fp32x: (the 3x3 operand encoding of t, the fp16 rounding of t as plain rows) from one pass -- the first feeds the forward conv, the
-    second is what its backward keeps for the one-term weight gradient (mu_conv_wgrad_h1)."""
+    """fp32x: the _Enc3 form of a plain activation from one pass."""
     t = t.contiguous()
     e = torch.empty_like(t)
     t16 = torch.empty(t.shape, dtype=torch.float16, device=t.device)
     call("mu_split_encode_h4x", ptr(t), ptr(e), ptr(t16), t.numel(), stream())
-    return e, t16
-
-
-def _enc_for(t, taps):
-    """The operand encoding a layer with `taps` taps reads: fp16 pairs for the 3x3 layers, bf16 pairs for 1x1 / Linear."""
-    return _enc3(t) if taps == 9 else _enc(t)
+    return _Enc3(e, t16)
 
 
 def dy_encode_h(gy):
-    """fp32x, 3x3 backward: a plain fp32 gradient as ONE power-of-two-scaled fp16 operand -> (tensor holding the halves, scale pair).  The
-    halves live at the start of an fp32-typed buffer of gy's shape (the form the BatchNorm backward hands over through EncLink)."""
+    """fp32x, 3x3 backward: a plain fp32 gradient -> its _DyH form (where no BatchNorm backward wrote it so)."""
     gy = gy.contiguous()
-    out = torch.empty_like(gy)
+    out = torch.empty(gy.shape, dtype=torch.float16, device=gy.device)
     scale = torch.empty(2, dtype=torch.float32, device=gy.device)
     ws = torch.empty(_lib.load().mu_dy_encode_h_workspace_bytes(), dtype=torch.uint8, device=gy.device)
     call("mu_dy_encode_h", ptr(gy), ptr(out), ptr(scale), gy.numel(), ptr(ws), ws.numel(), stream())
-    return out, scale
+    return _DyH(out, scale)
 
 
 def _enc_(t):
@@ -132,33 +136,6 @@ class GradLink:
 
 
 _graph_task_id = getattr(torch._C, "_current_graph_task_id", lambda: -1)     # id of the running backward pass (-1 outside one)
-
-
-class EncLink:
-    """fp32x: tells a 3x3 conv's backward that the dy it is handed was WRITTEN as one scaled fp16 operand by the backward of the BatchNorm
-    behind that conv (mu_bn_act_bwd_h) -- the BatchNorm's dx is the conv's dy and has no other consumer (ConvBlock wiring), so the separate
-    encoding pass disappears.  Carries the device-side scale pair {S, 1 / S} of that tensor.  One link per (conv, BatchNorm) pair and
-    forward call; valid only within the backward pass that marked it."""
-    __slots__ = ("task", "scale")
-
-    def __init__(self):
-        self.task = None
-        self.scale = None
-
-    def mark(self, scale):
-        self.task = _graph_task_id()
-        self.scale = scale
-
-    def take(self):
-        """-> the scale pair if this backward pass marked the link, else None"""
-        t, sc = self.task, self.scale
-        self.task = self.scale = None
-        return sc if (t is not None and t == _graph_task_id()) else None
-
-
-def enc_link(x):
-    """A fresh EncLink when x is an fp32 tensor in the fp32x mode and a backward can follow, else None."""
-    return EncLink() if (torch.is_grad_enabled() and _is_x(x)) else None
 
 
 def _same_mode(ctx_is_x, t):
@@ -407,24 +384,19 @@ def _take_step_prep(w, dtype, taps, rows_pad, cols_pad, need_dgrad):
     return pre[3], pre[4]
 
 
-def _conv_raw(x, wprep, bias_p, Cout_p, taps, want_stats=False, x_encoded=False):
-    """y = conv(x); with want_stats also the per-tile BatchNorm statistics rows of y ([rows, Cout_p, 2] floats) when the kernel
-    serving this shape has a statistics epilogue (else None).  fp32x: x is chunk-encoded here unless the caller already did."""
+def _conv_raw(x, wprep, bias_p, Cout_p, taps, want_stats=False):
+    """y = conv(x) on a ready operand (fp32x: chunk-encoded); with want_stats -> (y, the per-tile BatchNorm statistics rows of y
+    ([rows, Cout_p, 2] floats) when the kernel serving this shape has a statistics epilogue, else None)."""
     B, H, W, Cin_p = x.shape
     y = torch.empty((B, H, W, Cout_p), dtype=x.dtype, device=x.device)
-    if not x_encoded:
-        x = _enc_for(x, taps)
-    if want_stats:
-        rows = _lib.load().mu_conv_stats_rows(B, H, W, Cin_p, Cout_p, taps, mdt(x))
-        if rows > 0:
-            part = torch.empty((rows, Cout_p, 2), dtype=torch.float32, device=x.device)
-            call("mu_conv_fwd_stats", ptr(x), ptr(wprep), ptr(bias_p), ptr(y), B, H, W, Cin_p, Cout_p, taps, Cin_p, Cout_p, mdt(x),
-                 ptr(part), stream())
-            return y, part
+    part = None
+    if want_stats and (rows := _lib.load().mu_conv_stats_rows(B, H, W, Cin_p, Cout_p, taps, mdt(x))) > 0:
+        part = torch.empty((rows, Cout_p, 2), dtype=torch.float32, device=x.device)
+        call("mu_conv_fwd_stats", ptr(x), ptr(wprep), ptr(bias_p), ptr(y), B, H, W, Cin_p, Cout_p, taps, Cin_p, Cout_p, mdt(x),
+             ptr(part), stream())
+    else:
         call("mu_conv_fwd", ptr(x), ptr(wprep), ptr(bias_p), ptr(y), B, H, W, Cin_p, Cout_p, taps, Cin_p, Cout_p, mdt(x), stream())
-        return y, None
-    call("mu_conv_fwd", ptr(x), ptr(wprep), ptr(bias_p), ptr(y), B, H, W, Cin_p, Cout_p, taps, Cin_p, Cout_p, mdt(x), stream())
-    return y
+    return (y, part) if want_stats else y
 
 
 # Cut point of a segmented capture (maskunet_amd.GraphedStep over DataParallel): while CUT_HOOK is set, the tensor handed to cut_point()
@@ -466,29 +438,31 @@ def grad_out(param, shape, device):
     return torch.empty(shape, dtype=torch.float32, device=device)
 
 
-def _wgrad_raw(x, gy, w_shape, taps, gy_encoded=False, x_encoded=False, param=None, gy_scale=None):
-    """gy_scale (fp32x 3x3 layers): gy holds ONE scaled fp16 operand (dy_encode_h form) and this is its scale pair; x is then the fp16
-    rounding of the layer's input (a float16 tensor: the one-term weight gradient)."""
+def _wgrad_h1(x16, dyh, w_shape, param=None):
+    """fp32x 3x3 layers: the one-term weight gradient from the fp16 rounding of the layer's input and dy as a _DyH."""
+    B, H, W, Cin_p = x16.shape
+    O, I = w_shape[0], w_shape[1]
+    Cout_p = dyh.h.shape[-1]
+    gw = grad_out(param, tuple(w_shape), x16.device)
+    ws = workspace(_lib.load().mu_conv_wgrad_workspace_bytes(B, H, W, Cin_p, Cout_p, 9), x16.device)
+    call("mu_conv_wgrad_h1", ptr(x16), ptr(dyh.h), ptr(dyh.scale), ptr(gw), B, H, W, Cin_p, Cout_p, I, O, Cin_p, Cout_p, ptr(ws), ws.numel(),
+         stream())
+    return gw
+
+
+def _wgrad_raw(x, gy, w_shape, taps, gy_enc=False, x_enc=False, param=None):
+    """gy_enc / x_enc (fp32x): the operand is chunk-encoded already."""
     B, H, W, Cin_p = x.shape
     O, I = w_shape[0], w_shape[1]
-    if x.dtype == torch.float16 and gy.dtype == torch.float32:      # (fp16-mode layers hand over an fp16 dy and take the ordinary path below)
-        if gy_scale is None:
-            gy, gy_scale = dy_encode_h(gy)
-        Cout_p = gy.shape[-1]
-        gw = grad_out(param, tuple(w_shape), x.device)
-        ws = workspace(_lib.load().mu_conv_wgrad_workspace_bytes(B, H, W, Cin_p, Cout_p, 9), x.device)
-        call("mu_conv_wgrad_h1", ptr(x), ptr(gy), ptr(gy_scale), ptr(gw), B, H, W, Cin_p, Cout_p, I, O, Cin_p, Cout_p, ptr(ws), ws.numel(),
-             stream())
-        return gw
     code = mdt(x)
     if code == _lib.MU_F32X and taps == 9:
-        if I > 3 or gy_encoded or x_encoded:
+        if I > 3 or gy_enc or x_enc:
             raise RuntimeError("conv weight gradient: an fp32x 3x3 layer takes the fp16 rounding of its input (mu_conv_wgrad_h1)")
         code = _lib.MU_F32               # the first layer's weight gradient is a plain-FMA kernel (no matrix cores): plain fp32 operands
     if code == _lib.MU_F32X:
-        if not x_encoded:
+        if not x_enc:
             x = _enc(x)
-        if not gy_encoded:
+        if not gy_enc:
             gy = _enc(gy)
     Cout_p = gy.shape[-1]
     gw = grad_out(param, tuple(w_shape), x.device)
@@ -523,57 +497,108 @@ def _colsum(gy, n_valid, encoded=False):
     return out[:n_valid]
 
 
-class _Conv(torch.autograd.Function):
-    """nn.Conv2d k=3/pad=1 or k=1, NHWC (ade_semantic.py:199,202,284; city_instance.py:243-249)."""
+# Every layer below is a pair of plain functions -- *_fwd(...) -> (outputs, saved), *_bwd(saved, gy, ...) -> gradients, saved = (tensors,
+# python state) -- under a thin autograd.Function for the stand-alone API (conv, conv_stats, bn_act, bn_pair: the heads, the tests).
+# The ConvBlocks of the model run them inside ONE node per run of blocks (conv_blocks), the only place where operands travel from
+# layer to layer in an encoded form (_Enc3, _DyH): nothing autograd can see is ever encoded.
+def _conv_fwd(x, weight, bias, want_stats, cache_ok, needs):
+    """nn.Conv2d k=3/pad=1 or k=1, NHWC (ade_semantic.py:199,202,284; city_instance.py:243-249) -> ((y, statistics rows or None), saved).
+    x: a plain tensor, or the _Enc3 its producer wrote; needs: (dx, dw, db) wanted from the backward."""
+    enc = x if isinstance(x, _Enc3) else None
+    x = enc.e if enc is not None else x.contiguous()
+    O, I = weight.shape[0], weight.shape[1]
+    taps = weight.shape[2] * weight.shape[3]
+    Cin_p, Cout_p = x.shape[-1], pad32(O)
+    if pad32(I) != Cin_p:
+        raise RuntimeError(f"conv: input has {Cin_p} (padded) channels, weight expects {I}")
+    # the data-gradient layout is produced by the same launch when the backward will need it
+    wd = None
+    pre = _take_step_prep(weight, x.dtype, taps, Cout_p, Cin_p, needs[0])
+    if pre is not None:
+        wprep, wd = pre[0], (pre[1] if needs[0] else None)
+    elif needs[0]:
+        wprep, wd = _prep_weight(weight, x.dtype, Cout_p, Cin_p, 2)
+    else:
+        wprep = _prep_weight(weight, x.dtype, Cout_p, Cin_p, 0, cache_ok)
+    bias_p = _pad_vec(bias, Cout_p, 0.0) if bias is not None else None
+    # fp32x: the chunk-encoded input is what both the forward conv and the weight gradient read -- encode once, save THAT (the first
+    # layer's weight gradient is a plain-FMA kernel and keeps the plain tensor)
+    is_x = _is_x(x)
+    x_enc = is_x and not (taps == 9 and I <= 3)
+    # fp32x 3x3 layers (round 6): the backward keeps only the fp16 ROUNDING of the input (half the bytes of the encoded form) for the
+    # one-term weight gradient; the encoded form feeds the forward conv and is dropped
+    keep16 = x_enc and taps == 9 and needs[1]
+    if enc is None and keep16:
+        enc = _enc3x(x)
+    if enc is not None:
+        xop, keep = enc.e, (enc.h if keep16 else enc.e)
+    else:
+        xop = _enc_for(x, taps)
+        keep = xop if x_enc else x
+    y, part = _conv_raw(xop, wprep, bias_p, Cout_p, taps, True) if want_stats else (_conv_raw(xop, wprep, bias_p, Cout_p, taps), None)
+    return (y, part), ((keep, weight), SimpleNamespace(wd=wd, wparam=weight, has_bias=bias is not None, taps=taps, is_x=is_x, x_enc=x_enc))
 
+
+def _take_wd(m, weight, dtype, Cin_p, Cout_p):
+    """The data-gradient layout the forward left behind, once; a second backward over a retained graph makes it again."""
+    wd = m.wd if m.wd is not None else _prep_weight(weight, dtype, Cin_p, Cout_p, 1)
+    m.wd = None
+    return wd
+
+
+def _conv_bwd(saved, gy, needs):
+    """-> (dx, dw, db); gy: the plain dy, or the _DyH the BatchNorm backward behind an fp32x 3x3 matrix-core layer wrote."""
+    (x, weight), m = saved
+    dyh = gy if isinstance(gy, _DyH) else None
+    if dyh is None:
+        gy = gy.contiguous()
+        _same_mode(m.is_x, gy)
+    O = weight.shape[0]
+    gx = gw = gb = None
+    if m.is_x and m.taps == 9:
+        # fp32x 3x3 layer (round 6): dy as ONE power-of-two-scaled fp16 operand, shared by the data gradient (against the fp16 pair of
+        # the weights: two MFMAs per product) and the weight gradient (against the fp16 rounding of the saved input: one)
+        wg_h = needs[1] and m.x_enc           # (a <= 3-channel layer's weight gradient: plain-FMA kernel, plain dy)
+        if dyh is None and (needs[0] or wg_h):
+            dyh = dy_encode_h(gy)
+        if needs[0]:
+            B, H, W, Cin_p = x.shape
+            Cout_p = dyh.h.shape[-1]
+            wd = _take_wd(m, weight, torch.float32, Cin_p, Cout_p)
+            gx = torch.empty((B, H, W, Cin_p), dtype=torch.float32, device=x.device)
+            call("mu_conv_dgrad_h", ptr(dyh.h), ptr(wd), ptr(dyh.scale), ptr(gx), B, H, W, Cout_p, Cin_p, Cout_p, Cin_p, stream())
+        if wg_h:             # x: the fp16 rounding of the input (one term)
+            gw = _wgrad_h1(x, dyh, tuple(weight.shape), param=m.wparam)
+        elif needs[1]:
+            gw = _wgrad_raw(x, gy, tuple(weight.shape), 9, param=m.wparam)
+        if m.has_bias and needs[2]:
+            gb = _colsum(gy, O)
+        return gx, gw, gb
+    ge = _enc(gy) if (needs[0] or needs[1]) else gy       # fp32x: one encoding of dy for both
+    if needs[0]:
+        gx = _conv_raw(ge, _take_wd(m, weight, gy.dtype, x.shape[-1], gy.shape[-1]), None, x.shape[-1], m.taps)
+    if needs[1]:
+        both = _wgrad_bias_raw(x, gy, tuple(weight.shape), m.taps, m.wparam) if (m.has_bias and needs[2]) else None
+        if both is not None:
+            gw, gb = both
+        else:
+            first = not m.x_enc                                     # (the first layer's plain-FMA kernel: plain operands)
+            gw = _wgrad_raw(x, gy if first else ge, tuple(weight.shape), m.taps, gy_enc=_is_x(gy) and not first, x_enc=m.x_enc,
+                            param=m.wparam)
+    if m.has_bias and needs[2] and gb is None:
+        gb = _colsum(gy, O)
+    return gx, gw, gb
+
+
+class _Conv(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, want_stats=False, cache_ok=False, x_encoded=False, dy_link=None, x16=None):
-        x = x.contiguous()
-        ctx.dy_link = dy_link
-        O, I = weight.shape[0], weight.shape[1]
-        taps = weight.shape[2] * weight.shape[3]
-        Cin_p, Cout_p = x.shape[-1], pad32(O)
-        if pad32(I) != Cin_p:
-            raise RuntimeError(f"conv: input has {Cin_p} (padded) channels, weight expects {I}")
-        # the data-gradient layout is produced by the same launch when the backward will need it
-        ctx.wd = None
-        pre = _take_step_prep(weight, x.dtype, taps, Cout_p, Cin_p, ctx.needs_input_grad[0])
-        if pre is not None:
-            wprep, ctx.wd = pre[0], (pre[1] if ctx.needs_input_grad[0] else None)
-        elif ctx.needs_input_grad[0]:
-            wprep, ctx.wd = _prep_weight(weight, x.dtype, Cout_p, Cin_p, 2)
-        else:
-            wprep = _prep_weight(weight, x.dtype, Cout_p, Cin_p, 0, cache_ok)
-        bias_p = _pad_vec(bias, Cout_p, 0.0) if bias is not None else None
-        part = None
-        # fp32x: the chunk-encoded input is what both the forward conv and the weight gradient read -- encode once, save THAT (the first
-        # layer's weight gradient is a plain-FMA kernel and keeps the plain tensor)
-        ctx.is_x = _is_x(x)
-        ctx.x_enc = ctx.is_x and not (taps == 9 and I <= 3)
-        if x_encoded and not ctx.x_enc:
-            raise RuntimeError("conv: a pre-encoded input needs the fp32x mode and a matrix-core layer")
-        # fp32x 3x3 layers (round 6): the backward keeps only the fp16 ROUNDING of the input (x16: half the bytes of the encoded form) for the
-        # one-term weight gradient; the encoded form feeds the forward conv and is dropped.  x16 comes from the producer that wrote x
-        # encoded (bn_act: `_mu_x16`), or from the same pass that encodes x here.
-        keep16 = ctx.x_enc and taps == 9 and ctx.needs_input_grad[1]
-        if ctx.x_enc and not x_encoded:
-            if keep16:
-                x, x16 = _enc3x(x)
-            else:
-                x = _enc_for(x, taps)
-        if keep16 and x16 is None:
-            raise RuntimeError("conv: a pre-encoded 3x3 input needs its fp16 rounding beside it (bn_act(..., enc_out=True))")
-        if want_stats:
-            y, part = _conv_raw(x, wprep, bias_p, Cout_p, taps, True, x_encoded=ctx.x_enc)
-        else:
-            y = _conv_raw(x, wprep, bias_p, Cout_p, taps, x_encoded=ctx.x_enc)
-        ctx.save_for_backward(x16 if keep16 else x, weight)
-        ctx.wparam = weight                      # the Parameter itself: backward looks at its .grad
-        ctx.has_bias, ctx.taps = bias is not None, taps
+    def forward(ctx, x, weight, bias, want_stats=False, cache_ok=False):
+        (y, part), (tensors, ctx.m) = _conv_fwd(x, weight, bias, want_stats, cache_ok, ctx.needs_input_grad)
+        ctx.save_for_backward(*tensors)
         if not want_stats:
             return y
         if part is None:
-            part = torch.empty(0, dtype=torch.float32, device=x.device)
+            part = torch.empty(0, dtype=torch.float32, device=y.device)
         ctx.mark_non_differentiable(part)
         ctx.set_materialize_grads(False)         # no zero-filled "gradient" of the statistics rows in the backward
         return y, part
@@ -582,220 +607,43 @@ class _Conv(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gy, gpart=None):
         if gy is None:
-            return None, None, None, None, None, None, None, None
-        x, weight = ctx.saved_tensors
-        gy = gy.contiguous()
-        _same_mode(ctx.is_x, gy)
-        gy_sc = ctx.dy_link.take() if ctx.dy_link is not None else None      # fp32x: dy arrived as ONE scaled fp16 operand from the BatchNorm's backward
-        gy_pre = gy_sc is not None
-        O, I = weight.shape[0], weight.shape[1]
-        gx = gw = gb = None
-        if gy_pre and (not ctx.x_enc or ctx.taps != 9 or (ctx.has_bias and ctx.needs_input_grad[2])):
-            raise RuntimeError("conv backward: an encoded dy reached a path that needs it plain")
-        if ctx.is_x and ctx.taps == 9:
-            # fp32x 3x3 layer (round 6): dy as ONE power-of-two-scaled fp16 operand, shared by the data gradient (against the fp16 pair of
-            # the weights: two MFMAs per product) and the weight gradient (against the fp16 rounding of the saved input: one)
-            wg_h = ctx.needs_input_grad[1] and ctx.x_enc      # (a <= 3-channel layer's weight gradient: plain-FMA kernel, plain dy)
-            gh = gy if gy_pre else None
-            if gh is None and (ctx.needs_input_grad[0] or wg_h):
-                gh, gy_sc = dy_encode_h(gy)
-            if ctx.needs_input_grad[0]:
-                wd = ctx.wd if ctx.wd is not None else _prep_weight(weight, gy.dtype, x.shape[-1], gy.shape[-1], 1)
-                ctx.wd = None
-                B, H, W, Cin_p = x.shape
-                gx = torch.empty((B, H, W, Cin_p), dtype=torch.float32, device=x.device)
-                call("mu_conv_dgrad_h", ptr(gh), ptr(wd), ptr(gy_sc), ptr(gx), B, H, W, gy.shape[-1], Cin_p, gy.shape[-1], Cin_p, stream())
-            if wg_h:         # x: the fp16 rounding of the input (one term)
-                gw = _wgrad_raw(x, gh, tuple(weight.shape), 9, param=ctx.wparam, gy_scale=gy_sc)
-            elif ctx.needs_input_grad[1]:
-                gw = _wgrad_raw(x, gy, tuple(weight.shape), 9, param=ctx.wparam)
-            if ctx.has_bias and ctx.needs_input_grad[2]:
-                gb = _colsum(gy, O)
-            return gx, gw, gb, None, None, None, None, None
-        ge = _enc(gy) if (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) else gy     # fp32x: one encoding of dy for both
-        if ctx.needs_input_grad[0]:
-            wd = ctx.wd if ctx.wd is not None else _prep_weight(weight, gy.dtype, x.shape[-1], gy.shape[-1], 1)
-            ctx.wd = None
-            gx = _conv_raw(ge, wd, None, x.shape[-1], ctx.taps, x_encoded=True)
-        if ctx.needs_input_grad[1]:
-            both = _wgrad_bias_raw(x, gy, tuple(weight.shape), ctx.taps, ctx.wparam) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-            if both is not None:
-                gw, gb = both
-            else:
-                first = not ctx.x_enc                                   # (the first layer's plain-FMA kernel: plain operands)
-                gw = _wgrad_raw(x, gy if first else ge, tuple(weight.shape), ctx.taps, gy_encoded=_is_x(gy) and not first, x_encoded=ctx.x_enc,
-                                param=ctx.wparam)
-        if ctx.has_bias and ctx.needs_input_grad[2] and gb is None:
-            gb = _colsum(gy, O)
-        return gx, gw, gb, None, None, None, None, None
+            return None, None, None, None, None
+        return _conv_bwd((ctx.saved_tensors, ctx.m), gy, ctx.needs_input_grad) + (None, None)
 
 
 def conv(x, weight, bias=None):
-    return _Conv.apply(x, weight, bias, False, _cache_ok(), False, None, None)
+    return _Conv.apply(x, weight, bias, False, _cache_ok())
 
 
-CONV_STATS = True      # no longer a switch: conv_stats always takes the epilogue's rows (the name stays for code that reads it)
-
-
-def conv_stats(x, weight, bias=None, want=True, x_encoded=False, dy_link=None):
+def conv_stats(x, weight, bias=None, want=True):
     """conv() that also returns the BatchNorm statistics rows of its output (an empty tensor when the kernel has none) --
-    pass them to bn_act(..., stats=rows) to skip the separate statistics sweep.  fp32x: x_encoded = x was written chunk-encoded by its
-    producer (bn_act(..., enc_out=True)); dy_link = EncLink shared with the BatchNorm behind this conv (see EncLink)."""
-    x16 = getattr(x, "_mu_x16", None) if x_encoded else None      # the fp16 rounding its producer wrote beside the encoded form (bn_act)
-    if not want:
-        return _Conv.apply(x, weight, bias, False, _cache_ok(), x_encoded, dy_link, x16), None
-    return _Conv.apply(x, weight, bias, True, _cache_ok(), x_encoded, dy_link, x16)
+    pass them to bn_act(..., stats=rows) to skip the separate statistics sweep."""
+    return _Conv.apply(x, weight, bias, True, _cache_ok()) if want else (conv(x, weight, bias), None)
 
 
 # ------------------------------------------------------------------------------------------------
 # BatchNorm2d (+ activation, + residual)
 # ------------------------------------------------------------------------------------------------
-class _BNAct(torch.autograd.Function):
-    """act(res + BatchNorm2d(x)): ade_semantic.py:200-201 (BN,GELU), :204,208 (BN, +x, GELU), :219,240 (BN),
-    :285-286 (BN, ReLU).  Training uses batch statistics and updates the running buffers in place."""
-
-    @staticmethod
-    def forward(ctx, x, res, gamma, beta, running_mean, running_var, training, momentum, eps, act, nbt=None, stats=None, res_link=None,
-                enc_out=False, dx_link=None, x16_box=None):
-        x = x.contiguous()
-        ctx.res_link = res_link if (res is not None and res_link is not None and res_link.armed) else None
-        ctx.dx_link = dx_link if (dx_link is not None and _is_x(x)) else None
-        enc_out = bool(enc_out) and _is_x(x)
-        C = x.shape[-1]
-        M = x.numel() // C
-        cv = gamma.numel()
-        g_p, b_p = _pad_vec(gamma, C, 1.0), _pad_vec(beta, C, 0.0)
-        mean = torch.empty(C, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        ws = workspace(_lib.load().mu_bn_workspace_bytes(C), x.device)
-        if training:
-            rm = running_mean if running_mean is not None else None
-            rv = running_var if running_var is not None else None
-            if stats is not None and stats.numel() > 0:          # rows left by the producing conv's epilogue
-                call("mu_bn_train_stats_rows", ptr(stats), stats.shape[0], M, C, ptr(mean), ptr(rstd), ptr(rm), ptr(rv), ptr(nbt), cv,
-                     float(momentum), float(eps), ptr(ws), ws.numel(), stream())
-            else:
-                call("mu_bn_train_stats", ptr(x), M, C, C, ptr(mean), ptr(rstd), ptr(rm), ptr(rv), ptr(nbt), cv, float(momentum), float(eps),
-                     ptr(ws), ws.numel(), dt(x), stream())
-        else:
-            call("mu_bn_eval_stats", ptr(running_mean), ptr(running_var), float(eps), ptr(mean), ptr(rstd), C, cv, stream())
-        y = torch.empty_like(x)
-        if res is not None:
-            res = res.contiguous()
-        if enc_out and x16_box is not None:
-            # fp32x: y as the next 3x3 conv's encoded operand AND its fp16 rounding (what that conv's backward keeps: ops._Conv)
-            y16 = torch.empty(x.shape, dtype=torch.float16, device=x.device)
-            call("mu_bn_act_fwd_enc", ptr(x), ptr(res), ptr(y), ptr(y16), M, C, ptr(mean), ptr(rstd), ptr(g_p), ptr(b_p), act, stream())
-            x16_box.append(y16)
-        else:
-            call("mu_bn_act_fwd", ptr(x), ptr(res), ptr(y), M, C, C, ptr(mean), ptr(rstd), ptr(g_p), ptr(b_p), act,
-                 _lib.MU_F32X if enc_out else dt(x), stream())      # MU_F32X: y written as the next conv's chunk-encoded operand
-        ctx.save_for_backward(x, res, mean, rstd, g_p, b_p)
-        ctx.act, ctx.training, ctx.cv = act, bool(training), cv
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        x, res, mean, rstd, g_p, b_p = ctx.saved_tensors
-        gy = gy.contiguous()
-        C = x.shape[-1]
-        M = x.numel() // C
-        dx = torch.empty_like(x)
-        dres = torch.empty_like(x) if res is not None else None
-        dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
-        dbeta = torch.empty_like(dgamma)
-        ws = workspace(_lib.load().mu_bn_workspace_bytes(C), x.device)
-        enc = ctx.dx_link is not None            # fp32x: dx is the dy of the 3x3 conv in front -- written as ONE scaled fp16 operand, the conv is told (EncLink)
-        if enc:
-            sc = torch.empty(2, dtype=torch.float32, device=x.device)      # {S, 1 / S}, written on the device
-            call("mu_bn_act_bwd_h", ptr(x), ptr(res), ptr(gy), ptr(dx), ptr(dres), M, C, ptr(mean), ptr(rstd), ptr(g_p), ptr(b_p),
-                 ctx.act, int(ctx.training), ptr(dgamma), ptr(dbeta), ptr(sc), ptr(ws), ws.numel(), stream())
-            ctx.dx_link.mark(sc)
-        else:
-            call("mu_bn_act_bwd", ptr(x), ptr(res), ptr(gy), ptr(dx), ptr(dres), M, C, C, ptr(mean), ptr(rstd), ptr(g_p), ptr(b_p),
-                 ctx.act, int(ctx.training), ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), dt(x), stream())
-        if ctx.res_link is not None:             # the residual-branch gradient travels to the backward of x's producer (GradLink)
-            ctx.res_link.put(dres)
-            dres = None
-        return dx, dres, dgamma[:ctx.cv], dbeta[:ctx.cv], None, None, None, None, None, None, None, None, None, None, None, None
+def _bn_train_stats(x, stats, bn, nbt, momentum, mean, rstd):
+    """Batch statistics of x into mean / rstd, from the rows left by the producing conv's epilogue (`stats`) where there are any; bn's
+    running buffers and the step counter `nbt` advance in the same kernel."""
+    C = x.shape[-1]
+    M = x.numel() // C
+    cv, rm, rv = bn.weight.numel(), bn.running_mean, bn.running_var
+    ws = workspace(_lib.load().mu_bn_workspace_bytes(C), x.device)
+    if stats is not None and stats.numel() > 0:
+        call("mu_bn_train_stats_rows", ptr(stats), stats.shape[0], M, C, ptr(mean), ptr(rstd), ptr(rm), ptr(rv), ptr(nbt), cv,
+             float(momentum), float(bn.eps), ptr(ws), ws.numel(), stream())
+    else:
+        call("mu_bn_train_stats", ptr(x), M, C, C, ptr(mean), ptr(rstd), ptr(rm), ptr(rv), ptr(nbt), cv, float(momentum), float(bn.eps),
+             ptr(ws), ws.numel(), dt(x), stream())
 
 
-class _BNPair(torch.autograd.Function):
-    """BatchNorm2d(BatchNorm2d(x)) in training mode as ONE normalisation of x (ade_semantic.py:216-219, 237-240: the BatchNorm behind
-    ConvBlock's last BatchNorm in DownSample / UpSample); see mu_bn_pair_compose in include/maskunet_hip.h for the algebra."""
-
-    @staticmethod
-    def forward(ctx, x, g1, b1, g2, b2, rm1, rv1, nbt1, mom1, eps1, rm2, rv2, nbt2, mom2, eps2, stats, dx_link=None):
-        x = x.contiguous()
-        ctx.dx_link = dx_link if (dx_link is not None and _is_x(x)) else None
-        C = x.shape[-1]
-        M = x.numel() // C
-        cv = g1.numel()
-        g1p, b1p, g2p, b2p = _pad_vec(g1, C, 1.0), _pad_vec(b1, C, 0.0), _pad_vec(g2, C, 1.0), _pad_vec(b2, C, 0.0)
-        dev = x.device
-        mean = torch.empty(C, dtype=torch.float32, device=dev)
-        rstd = torch.empty_like(mean)
-        coef = torch.empty(4, C, dtype=torch.float32, device=dev)      # gamma_eff, xhat_scale, dgamma2_coef, dgamma1_coef
-        ws = workspace(_lib.load().mu_bn_workspace_bytes(C), dev)
-        if stats is not None and stats.numel() > 0:
-            call("mu_bn_train_stats_rows", ptr(stats), stats.shape[0], M, C, ptr(mean), ptr(rstd), ptr(rm1), ptr(rv1), ptr(nbt1), cv,
-                 float(mom1), float(eps1), ptr(ws), ws.numel(), stream())
-        else:
-            call("mu_bn_train_stats", ptr(x), M, C, C, ptr(mean), ptr(rstd), ptr(rm1), ptr(rv1), ptr(nbt1), cv, float(mom1), float(eps1),
-                 ptr(ws), ws.numel(), dt(x), stream())
-        call("mu_bn_pair_compose", ptr(rstd), ptr(g1p), ptr(b1p), ptr(g2p), C, cv, M, float(eps1), float(eps2), float(mom2), ptr(rm2),
-             ptr(rv2), ptr(nbt2), ptr(coef[0]), ptr(coef[1]), ptr(coef[2]), ptr(coef[3]), stream())
-        y = torch.empty_like(x)
-        call("mu_bn_act_fwd", ptr(x), None, ptr(y), M, C, C, ptr(mean), ptr(rstd), ptr(coef[0]), ptr(b2p), ACT_NONE, dt(x), stream())
-        ctx.save_for_backward(x, mean, rstd, coef, b2p)
-        ctx.cv = cv
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        x, mean, rstd, coef, b2p = ctx.saved_tensors
-        gy = gy.contiguous()
-        C = x.shape[-1]
-        M = x.numel() // C
-        dx = torch.empty_like(x)
-        dg = torch.empty(3, C, dtype=torch.float32, device=x.device)      # rows: dgamma2, dgamma1, dbeta1 (= 0), written by the finalize kernel
-        dbeta2 = torch.empty(C, dtype=torch.float32, device=x.device)
-        ws = workspace(_lib.load().mu_bn_workspace_bytes(C), x.device)
-        enc = ctx.dx_link is not None
-        if enc:
-            sc = torch.empty(2, dtype=torch.float32, device=x.device)
-            call("mu_bn_pair_bwd_h", ptr(x), ptr(gy), ptr(dx), M, C, ptr(mean), ptr(rstd), ptr(coef[0]), ptr(b2p), ptr(coef[1]), ptr(coef[2]),
-                 ptr(coef[3]), ptr(dg), ptr(dbeta2), ptr(sc), ptr(ws), ws.numel(), stream())
-            ctx.dx_link.mark(sc)
-        else:
-            call("mu_bn_pair_bwd", ptr(x), ptr(gy), ptr(dx), M, C, C, ptr(mean), ptr(rstd), ptr(coef[0]), ptr(b2p), ptr(coef[1]), ptr(coef[2]),
-                 ptr(coef[3]), ptr(dg), ptr(dbeta2), ptr(ws), ws.numel(), dt(x), stream())
-        cv = ctx.cv
-        return (dx, dg[1, :cv], dg[2, :cv], dg[0, :cv], dbeta2[:cv]) + (None,) * 12
-
-
-BN_PAIR = os.environ.get("MU_BN_PAIR", "1") != "0"          # debug switch: 0 = the two layers one after the other
-
-
-def bn_pair(x, bn1, bn2, stats=None, dx_link=None):
-    """bn2(bn1(x)) for two nn.BatchNorm2d containers applied back to back (no activation, no residual in between)."""
-    both_train = (bn1.training and bn2.training and bn1.running_mean is not None and bn2.running_mean is not None
-                  and bn1.weight is not None and bn2.weight is not None)
-    ok = both_train and BN_PAIR and all(t is not None and t.device == x.device and t.dtype == torch.int64
-                                        for t in (bn1.num_batches_tracked, bn2.num_batches_tracked))
-    if not ok or bn1.momentum is None or bn2.momentum is None:
-        return bn_act(bn_act(x, bn1, ACT_NONE, stats=stats, dx_link=dx_link), bn2, ACT_NONE)
-    return _BNPair.apply(x, bn1.weight, bn1.bias, bn2.weight, bn2.bias, bn1.running_mean, bn1.running_var, bn1.num_batches_tracked,
-                         bn1.momentum, bn1.eps, bn2.running_mean, bn2.running_var, bn2.num_batches_tracked, bn2.momentum, bn2.eps, stats, dx_link)
-
-
-def bn_act(x, bn, act=ACT_NONE, res=None, stats=None, res_link=None, enc_out=False, dx_link=None):
-    """Apply the BatchNorm2d parameter container `bn` (an nn.BatchNorm2d used only for its
-    parameters/buffers/flags) followed by `act`, optionally adding `res` before the activation.
-    `stats`: statistics rows of x from conv_stats() (training mode only; ignored otherwise).
-    `res_link`: GradLink that carries d(res) to the backward of res's producer (maxpool2 / upcat) instead of through autograd."""
+def _bn_act_fwd(x, res, bn, act, stats=None, enc=False):
+    """act(res + BatchNorm2d(x)): ade_semantic.py:200-201 (BN,GELU), :204,208 (BN, +x, GELU), :219,240 (BN), :285-286 (BN, ReLU)
+    -> (y, saved).  bn: the nn.BatchNorm2d parameter container; training uses batch statistics and updates its running buffers in
+    place.  enc (fp32x): y is returned as the _Enc3 of the 3x3 conv behind it, its only reader."""
+    x = x.contiguous()
     training = bn.training or bn.running_mean is None
     # the step counter is bumped by the statistics kernel (one tiny torch kernel per BatchNorm otherwise: 39 per step)
     nbt = bn.num_batches_tracked if (bn.training and bn.num_batches_tracked is not None) else None
@@ -803,12 +651,251 @@ def bn_act(x, bn, act=ACT_NONE, res=None, stats=None, res_link=None, enc_out=Fal
         nbt.add_(1)
         nbt = None
     momentum = 0.1 if bn.momentum is None else bn.momentum
-    box = [] if (enc_out and torch.is_grad_enabled() and _is_x(x)) else None
-    y = _BNAct.apply(x, res, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum, bn.eps, act, nbt,
-                     stats if training else None, res_link, enc_out, dx_link, box)
-    if box:
-        y._mu_x16 = box[0]
-    return y
+    C = x.shape[-1]
+    M = x.numel() // C
+    cv = bn.weight.numel()
+    g_p, b_p = _pad_vec(bn.weight, C, 1.0), _pad_vec(bn.bias, C, 0.0)
+    mean = torch.empty(C, dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    if training:
+        _bn_train_stats(x, stats, bn, nbt, momentum, mean, rstd)
+    else:
+        call("mu_bn_eval_stats", ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps), ptr(mean), ptr(rstd), C, cv, stream())
+    y = torch.empty_like(x)
+    if res is not None:
+        res = res.contiguous()
+    if enc:
+        y16 = torch.empty(x.shape, dtype=torch.float16, device=x.device)
+        call("mu_bn_act_fwd_enc", ptr(x), ptr(res), ptr(y), ptr(y16), M, C, ptr(mean), ptr(rstd), ptr(g_p), ptr(b_p), act, stream())
+        y = _Enc3(y, y16)
+    else:
+        call("mu_bn_act_fwd", ptr(x), ptr(res), ptr(y), M, C, C, ptr(mean), ptr(rstd), ptr(g_p), ptr(b_p), act, dt(x), stream())
+    return y, ((x, res, mean, rstd, g_p, b_p), (act, bool(training), cv))
+
+
+def _dx_out(x, dx_h):
+    """Where a BatchNorm backward writes dx: a plain tensor like x, or (fp32x, dx_h) the _DyH of the 3x3 conv in front -- halves and the
+    scale pair {S, 1 / S}, both written on the device."""
+    if not dx_h:
+        return torch.empty_like(x)
+    return _DyH(torch.empty(x.shape, dtype=torch.float16, device=x.device), torch.empty(2, dtype=torch.float32, device=x.device))
+
+
+def _bn_act_bwd(saved, gy, dx_h=False):
+    """-> (dx, dres, dgamma, dbeta).  dx_h (fp32x): dx is the dy of the 3x3 conv in front and of nothing else -- returned as its _DyH."""
+    (x, res, mean, rstd, g_p, b_p), (act, training, cv) = saved
+    gy = gy.contiguous()
+    C = x.shape[-1]
+    M = x.numel() // C
+    dres = torch.empty_like(x) if res is not None else None
+    dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty_like(dgamma)
+    ws = workspace(_lib.load().mu_bn_workspace_bytes(C), x.device)
+    dx = _dx_out(x, dx_h)
+    if dx_h:
+        call("mu_bn_act_bwd_h", ptr(x), ptr(res), ptr(gy), ptr(dx.h), ptr(dres), M, C, ptr(mean), ptr(rstd), ptr(g_p), ptr(b_p),
+             act, int(training), ptr(dgamma), ptr(dbeta), ptr(dx.scale), ptr(ws), ws.numel(), stream())
+    else:
+        call("mu_bn_act_bwd", ptr(x), ptr(res), ptr(gy), ptr(dx), ptr(dres), M, C, C, ptr(mean), ptr(rstd), ptr(g_p), ptr(b_p),
+             act, int(training), ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), dt(x), stream())
+    return dx, dres, dgamma[:cv], dbeta[:cv]
+
+
+class _BNAct(torch.autograd.Function):
+    """gamma / beta are bn's own tensors, listed for autograd."""
+
+    @staticmethod
+    def forward(ctx, x, res, gamma, beta, bn, act, stats=None):
+        y, (tensors, ctx.m) = _bn_act_fwd(x, res, bn, act, stats)
+        ctx.save_for_backward(*tensors)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        return _bn_act_bwd((ctx.saved_tensors, ctx.m), gy) + (None, None, None)
+
+
+BN_PAIR = os.environ.get("MU_BN_PAIR", "1") != "0"          # debug switch: 0 = the two layers one after the other
+
+
+def _bn_pair_ok(bn1, bn2, x):
+    """Can bn2(bn1(x)) run as one normalisation (both in training mode with every buffer in place)?"""
+    both_train = (bn1.training and bn2.training and bn1.running_mean is not None and bn2.running_mean is not None
+                  and bn1.weight is not None and bn2.weight is not None)
+    ok = both_train and BN_PAIR and all(t is not None and t.device == x.device and t.dtype == torch.int64
+                                        for t in (bn1.num_batches_tracked, bn2.num_batches_tracked))
+    return ok and bn1.momentum is not None and bn2.momentum is not None
+
+
+def _bn_pair_fwd(x, bn1, bn2, stats=None):
+    """BatchNorm2d(BatchNorm2d(x)) in training mode as ONE normalisation of x (ade_semantic.py:216-219, 237-240: the BatchNorm behind
+    ConvBlock's last BatchNorm in DownSample / UpSample); see mu_bn_pair_compose in include/maskunet_hip.h for the algebra."""
+    x = x.contiguous()
+    C = x.shape[-1]
+    M = x.numel() // C
+    cv = bn1.weight.numel()
+    g1p, b1p, g2p, b2p = _pad_vec(bn1.weight, C, 1.0), _pad_vec(bn1.bias, C, 0.0), _pad_vec(bn2.weight, C, 1.0), _pad_vec(bn2.bias, C, 0.0)
+    dev = x.device
+    mean = torch.empty(C, dtype=torch.float32, device=dev)
+    rstd = torch.empty_like(mean)
+    coef = torch.empty(4, C, dtype=torch.float32, device=dev)      # gamma_eff, xhat_scale, dgamma2_coef, dgamma1_coef
+    _bn_train_stats(x, stats, bn1, bn1.num_batches_tracked, bn1.momentum, mean, rstd)
+    call("mu_bn_pair_compose", ptr(rstd), ptr(g1p), ptr(b1p), ptr(g2p), C, cv, M, float(bn1.eps), float(bn2.eps), float(bn2.momentum),
+         ptr(bn2.running_mean), ptr(bn2.running_var), ptr(bn2.num_batches_tracked), ptr(coef[0]), ptr(coef[1]), ptr(coef[2]), ptr(coef[3]),
+         stream())
+    y = torch.empty_like(x)
+    call("mu_bn_act_fwd", ptr(x), None, ptr(y), M, C, C, ptr(mean), ptr(rstd), ptr(coef[0]), ptr(b2p), ACT_NONE, dt(x), stream())
+    return y, ((x, mean, rstd, coef, b2p), cv)
+
+
+def _bn_pair_bwd(saved, gy, dx_h=False):
+    """-> (dx, dgamma1, dbeta1, dgamma2, dbeta2); dx_h as in _bn_act_bwd."""
+    (x, mean, rstd, coef, b2p), cv = saved
+    gy = gy.contiguous()
+    C = x.shape[-1]
+    M = x.numel() // C
+    dg = torch.empty(3, C, dtype=torch.float32, device=x.device)      # rows: dgamma2, dgamma1, dbeta1 (= 0), written by the finalize kernel
+    dbeta2 = torch.empty(C, dtype=torch.float32, device=x.device)
+    ws = workspace(_lib.load().mu_bn_workspace_bytes(C), x.device)
+    dx = _dx_out(x, dx_h)
+    if dx_h:
+        call("mu_bn_pair_bwd_h", ptr(x), ptr(gy), ptr(dx.h), M, C, ptr(mean), ptr(rstd), ptr(coef[0]), ptr(b2p), ptr(coef[1]), ptr(coef[2]),
+             ptr(coef[3]), ptr(dg), ptr(dbeta2), ptr(dx.scale), ptr(ws), ws.numel(), stream())
+    else:
+        call("mu_bn_pair_bwd", ptr(x), ptr(gy), ptr(dx), M, C, C, ptr(mean), ptr(rstd), ptr(coef[0]), ptr(b2p), ptr(coef[1]), ptr(coef[2]),
+             ptr(coef[3]), ptr(dg), ptr(dbeta2), ptr(ws), ws.numel(), dt(x), stream())
+    return dx, dg[1, :cv], dg[2, :cv], dg[0, :cv], dbeta2[:cv]
+
+
+class _BNPair(torch.autograd.Function):
+    """g1 ... b2 are the containers' own tensors, listed for autograd."""
+
+    @staticmethod
+    def forward(ctx, x, g1, b1, g2, b2, bn1, bn2, stats=None):
+        y, (tensors, ctx.cv) = _bn_pair_fwd(x, bn1, bn2, stats)
+        ctx.save_for_backward(*tensors)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        return _bn_pair_bwd((ctx.saved_tensors, ctx.cv), gy) + (None, None, None)
+
+
+def bn_pair(x, bn1, bn2, stats=None):
+    """bn2(bn1(x)) for two nn.BatchNorm2d containers applied back to back (no activation, no residual in between)."""
+    if not _bn_pair_ok(bn1, bn2, x):
+        return bn_act(bn_act(x, bn1, ACT_NONE, stats=stats), bn2, ACT_NONE)
+    return _BNPair.apply(x, bn1.weight, bn1.bias, bn2.weight, bn2.bias, bn1, bn2, stats)
+
+
+def bn_act(x, bn, act=ACT_NONE, res=None, stats=None):
+    """Apply the BatchNorm2d parameter container `bn` (an nn.BatchNorm2d used only for its
+    parameters/buffers/flags) followed by `act`, optionally adding `res` before the activation.
+    `stats`: statistics rows of x from conv_stats() (training mode only; ignored otherwise)."""
+    return _BNAct.apply(x, res, bn.weight, bn.bias, bn, act, stats)
+
+
+# ------------------------------------------------------------------------------------------------
+# a run of consecutive ConvBlocks as ONE autograd node
+# ------------------------------------------------------------------------------------------------
+_keep_graph = getattr(torch._C._autograd, "_get_current_graph_task_keep_graph", lambda: True)      # retain_graph of the running backward pass
+
+
+class _ConvBlocks(torch.autograd.Function):
+    """See conv_blocks.  params: per block (w1, gamma1, beta1, w2, gamma2, beta2), then tail_bn's (gamma, beta) -- the tensors of the
+    descriptions, listed for autograd."""
+
+    @staticmethod
+    def forward(ctx, cfg, x, *params):
+        blocks, tail_bn, res_link, grad_on, cache_ok = cfg
+        x = x.contiguous()
+        need = ctx.needs_input_grad[2:]          # of params
+
+        def req(k):     # does the activation in front of params[k] require grad (it does when anything before it does)
+            return (grad_on or k == 0) and any(ctx.needs_input_grad[:2 + k])
+
+        # THE rule for the encoded forms (fp32x with a backward to come): a tensor whose only reader is a matrix-core conv (> 3 input
+        # channels; the 3-channel stem is a plain-FMA layer) travels in that conv's operand form.  Forward: a BatchNorm output that is
+        # not a residual source and not this node's output, as an _Enc3; backward: the dx of the BatchNorm behind a conv, as a _DyH.
+        enc_on = grad_on and _is_x(x)
+
+        def into(w):
+            return enc_on and w.shape[1] > 3
+
+        units, plan, cur, fold = [], [], x, False
+        for i, (w1, bn1, w2, bn2, residual) in enumerate(blocks):
+            k = 6 * i
+            nxt = blocks[i + 1] if i + 1 < len(blocks) else None
+            n1, n2 = (req(k), need[k], False), (req(k + 3), need[k + 3], False)
+            res = cur if residual else None
+            (y, st), c1 = _conv_fwd(cur, w1, None, bn1.training, cache_ok, n1)       # BatchNorm statistics from the conv epilogue where it has one
+            y, b1 = _bn_act_fwd(y, None, bn1, ACT_GELU, st, enc=into(w2))
+            (y, st), c2 = _conv_fwd(y, w2, None, bn2.training, cache_ok, n2)
+            fold = nxt is None and tail_bn is not None and not residual and _bn_pair_ok(bn2, tail_bn, y)
+            if fold:                # the BatchNorm DownSample / UpSample apply behind the block, folded into its last one
+                cur, b2 = _bn_pair_fwd(y, bn2, tail_bn, st)
+            else:                   # BN, or gelu(x + BN(conv(...)))  (:208)
+                cur, b2 = _bn_act_fwd(y, res, bn2, ACT_GELU if residual else ACT_NONE, st,
+                                      enc=nxt is not None and not nxt[4] and into(nxt[0]))
+            if grad_on:
+                units += [c1, b1, c2, b2]
+                plan.append((residual, n1, into(w1), n2, into(w2)))
+        if tail_bn is not None and not fold:
+            cur, t = _bn_act_fwd(cur, None, tail_bn, ACT_NONE)
+            units.append(t)
+        # block-internal tensors are nobody else's: kept as plain references and dropped while the backward walks past them; the inputs
+        # (x only where a unit kept it plain) go through save_for_backward, which refuses a backward after an in-place change of any of them
+        ctx.save_for_backward(x if any(t is x for s in units[:4] for t in s[0]) else None, *params)
+        ctx.units, ctx.plan, ctx.fold, ctx.tail = units, plan, fold, tail_bn is not None and not fold
+        ctx.link = res_link if (res_link is not None and res_link.armed and blocks[0][4]) else None
+        ctx.is_x = _is_x(x)
+        return cur
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        ctx.saved_tensors
+        _same_mode(ctx.is_x, gy)
+        units = list(ctx.units)
+        if not _keep_graph():
+            ctx.units = None
+        grads = [None] * (len(ctx.needs_input_grad) - 2)
+        if ctx.tail:
+            gy, _, grads[-2], grads[-1] = _bn_act_bwd(units.pop(), gy)
+        for i in reversed(range(len(ctx.plan))):
+            residual, n1, h1, n2, h2 = ctx.plan[i]
+            k, dres = 6 * i, None
+            if ctx.fold and i == len(ctx.plan) - 1:
+                gy, grads[k + 4], grads[k + 5], grads[-2], grads[-1] = _bn_pair_bwd(units.pop(), gy, h2)
+            else:
+                gy, dres, grads[k + 4], grads[k + 5] = _bn_act_bwd(units.pop(), gy, h2)
+            if dres is not None and i == 0 and ctx.link is not None:      # joined inside the backward kernel of x's producer (GradLink)
+                ctx.link.put(dres)
+                dres = None
+            gy, grads[k + 3], _ = _conv_bwd(units.pop(), gy, n2)           # data gradient before weight gradient
+            if gy is None:
+                break
+            gy, _, grads[k + 1], grads[k + 2] = _bn_act_bwd(units.pop(), gy, h1)
+            gy, grads[k], _ = _conv_bwd(units.pop(), gy, n1)
+            if gy is None:
+                break
+            if dres is not None:
+                gy = gy + dres          # a residual source without a taker for its link: the sum autograd would have made
+        return (None, gy, *grads)
+
+
+def conv_blocks(x, blocks, tail_bn=None, res_link=None):
+    """A run of consecutive ConvBlocks (ade_semantic.py:192-210) under grad as one autograd node: per block conv -> BN -> GELU -> conv -> BN
+    [-> + x -> GELU], then tail_bn (the BatchNorm DownSample / UpSample apply behind their last block, :219,240; folded into that block's
+    last BatchNorm where bn_pair would).  blocks: [(conv1 weight, bn1, conv2 weight, bn2, residual)], bn* the nn.BatchNorm2d containers.
+    res_link: ops.GradLink shared with the op that produced x (a residual FIRST block): the gradient of its `x +` branch is joined
+    inside that op's backward kernel.  The parameter gradients of the whole run reach autograd together, when its backward ends."""
+    params = [p for w1, bn1, w2, bn2, _ in blocks for p in (w1, bn1.weight, bn1.bias, w2, bn2.weight, bn2.bias)]
+    if tail_bn is not None:
+        params += [tail_bn.weight, tail_bn.bias]
+    return _ConvBlocks.apply((blocks, tail_bn, res_link, torch.is_grad_enabled(), _cache_ok()), x, *params)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1086,7 +1173,7 @@ class _MaskAttention(torch.autograd.Function):
             qkv = torch.empty((B, H, W, 3 * C), dtype=x.dtype, device=x.device)
             call("mu_conv1x1_fwd_enc_h", ptr(xe), ptr(wprep), ptr(bqkv), ptr(qkv), B * N, C, 3 * C, C, 3 * C, stream())
         else:
-            qkv = _enc_h_(_conv_raw(xe, wprep, bqkv, 3 * C, 1, x_encoded=True))
+            qkv = _enc_h_(_conv_raw(xe, wprep, bqkv, 3 * C, 1))
         out = torch.empty((B, N, C), dtype=x.dtype, device=x.device)
         oattn = torch.empty_like(out)
         lse2 = torch.empty((B, N), dtype=torch.float32, device=x.device)
@@ -1150,13 +1237,13 @@ class _MaskAttention(torch.autograd.Function):
                 gx = torch.empty((B, H, W, C), dtype=x.dtype, device=x.device)
                 call("mu_conv1x1_fwd_add", ptr(dqkv_e), ptr(wd), ptr(dY), ptr(gx), B * N, 3 * C, C, 3 * C, C, mdt(x), stream())
             else:
-                gx = _conv_raw(dqkv_e, wd, None, C, 1, x_encoded=True)
+                gx = _conv_raw(dqkv_e, wd, None, C, 1)
                 call("mu_add", ptr(gx), ptr(dY), ptr(gx), gx.numel(), dt(gx), stream())
         both = None if enc_dqkv else _wgrad_bias_raw(x, dqkv4, (3 * C, C, 1, 1), 1)       # projection weight and bias gradients from one sweep over dqkv
         if both is not None:
             gw, gb = both[0].view(3 * C, C), both[1]
         else:
-            gw = _wgrad_raw(xe, dqkv_e, (3 * C, C, 1, 1), 1, gy_encoded=True, x_encoded=ctx.is_x).view(3 * C, C)
+            gw = _wgrad_raw(xe, dqkv_e, (3 * C, C, 1, 1), 1, gy_enc=True, x_enc=ctx.is_x).view(3 * C, C)
             gb = _colsum(dqkv4, 3 * C, encoded=enc_dqkv)
         if cv != C:                  # gradients of the real (unpadded) parameters
             return (gx, gw[:cv, :cv], gb[:cv], gw[C:C + cv, :cv], gb[C:C + cv], gw[2 * C:2 * C + cv, :cv], gb[2 * C:2 * C + cv],

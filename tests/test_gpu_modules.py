@@ -376,3 +376,99 @@ def test_precision_switch_between_forward_and_backward_is_refused():
     finally:
         maskunet_amd.set_float32_matmul_precision("highest")
 
+
+
+# ------------------------------------------------------------------------------------------------
+# runs of ConvBlocks as one autograd node (ops.conv_blocks): the encoded operands of the fp32x mode stay inside it
+# ------------------------------------------------------------------------------------------------
+def _down_64_128(dtype):
+    import maskunet_amd
+    torch.manual_seed(11)
+    m = maskunet_amd.DownSample(64, 128).cuda().set_compute_dtype(dtype).train()
+    g = torch.Generator().manual_seed(12)
+    return m, torch.randn(2, 64, 32, 32, generator=g).cuda(), torch.randn(2, 128, 16, 16, generator=g).cuda()
+
+
+@pytest.mark.parametrize("mode", ["fp32x", "fp16"])
+def test_partial_then_full_backward_over_a_retained_conv_block_chain(mode):
+    """torch.autograd.grad towards the LAST conv weight over a retained graph, then the full backward: the node of the ConvBlock run
+    keeps what it saved while the graph is retained (and only then), and every gradient equals, bit for bit, the single full backward
+    of a fresh forward."""
+    import maskunet_amd
+    maskunet_amd.set_float32_matmul_precision("high" if mode == "fp32x" else "highest")
+    try:
+        m, x, gy = _down_64_128(torch.float16 if mode == "fp16" else torch.float32)
+        last = m.maxpool_conv[2].conv_block[3].weight
+        xr = x.clone().requires_grad_(True)
+        m(xr).backward(gy)
+        ref = {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}
+        assert "maxpool_conv.1.conv_block.0.weight" in ref and len(ref) == 14
+        m.zero_grad(set_to_none=True)
+        xd = x.clone().requires_grad_(True)
+        y = m(xd)
+        (part,) = torch.autograd.grad(y, [last], gy, retain_graph=True)
+        assert torch.equal(part, ref["maxpool_conv.2.conv_block.3.weight"])
+        y.backward(gy)
+        assert torch.equal(xd.grad, xr.grad)
+        for n, p in m.named_parameters():
+            if n in ref:
+                assert torch.equal(p.grad, ref[n]), n
+        with pytest.raises(RuntimeError):          # the graph was not retained this time: what the node saved is gone
+            y.backward(gy)
+    finally:
+        maskunet_amd.set_float32_matmul_precision("highest")
+
+
+def test_nothing_autograd_can_see_is_encoded_fp32x():
+    """A tensor hook and retain_grad() on the output of each ConvBlock run -- DownSample(64, 128)'s two blocks + BatchNorm, then a
+    residual ConvBlock(128, 128) reading it -- in the fp32x mode see plain finite gradients: the last run's is the gy that was fed in,
+    the inner one's agrees with the same modules in exact fp32 at the fp32 gradient gate of check_golden_module."""
+    import maskunet_amd
+    from maskunet_amd import ops
+    from tests import _gpu_checks as G
+    m, x, _ = _down_64_128(torch.float32)
+    torch.manual_seed(13)
+    blk = maskunet_amd.ConvBlock(128, 128, residual=True).cuda().train()
+    gy = torch.randn(2, 16, 16, 128, device="cuda")
+    seen = {}
+    for precision in ("highest", "high"):
+        maskunet_amd.set_float32_matmul_precision(precision)
+        try:
+            hooks = []
+            y1 = m.forward_nhwc(ops.to_nhwc(x.clone().requires_grad_(True), torch.float32))
+            y2 = blk.forward_nhwc(y1)
+            for t in (y1, y2):
+                t.retain_grad()
+                t.register_hook(lambda g, hooks=hooks: hooks.append(g.clone()))
+            y2.backward(gy)
+            seen[precision] = hooks[::-1]           # (the hook of the later tensor fires first)
+            assert len(hooks) == 2 and all(torch.isfinite(h).all() for h in hooks)
+            assert torch.equal(y1.grad, seen[precision][0]) and torch.equal(y2.grad, seen[precision][1])
+            assert torch.equal(seen[precision][1], gy)
+        finally:
+            maskunet_amd.set_float32_matmul_precision("highest")
+    assert not torch.equal(seen["high"][0], seen["highest"][0])            # the two modes do differ
+    e = G._rel_err(seen["high"][0], seen["highest"][0])
+    assert e <= G.TOL[torch.float32], e
+
+
+def test_fp32x_upsample_step_launch_structure(fp32x, monkeypatch):
+    """One fp32x training step of UpSample(128, 64): every operand between its four matrix-core convs is written in its encoded form by
+    the BatchNorm kernel that produces it -- no stand-alone dy / operand encoding pass except the one of the run's input -- and each
+    conv runs one data-gradient and one one-term weight-gradient launch.  (Counts taken from the commit before the ConvBlock runs
+    became one node: the launches did not change.)"""
+    import collections
+    import maskunet_amd
+    from maskunet_amd import ops
+    torch.manual_seed(0)
+    m = maskunet_amd.UpSample(128, 64).cuda().train()
+    x = torch.randn(2, 64, 16, 16, device="cuda", requires_grad=True)
+    s = torch.randn(2, 64, 32, 32, device="cuda", requires_grad=True)
+    cnt = collections.Counter()
+    raw = ops.call
+    monkeypatch.setattr(ops, "call", lambda name, *a: (cnt.update([name]), raw(name, *a))[1])
+    y = m(x, s)
+    y.backward(torch.randn_like(y))
+    assert cnt["mu_dy_encode_h"] == 0 and cnt["mu_split_encode_h4"] == 0 and cnt["mu_split_encode_h4x"] == 1, cnt
+    assert cnt["mu_conv_dgrad_h"] == 4 and cnt["mu_conv_wgrad_h1"] == 4, cnt
+    assert cnt["mu_bn_act_fwd_enc"] == 3 and cnt["mu_bn_act_bwd_h"] == 3 and cnt["mu_bn_pair_bwd_h"] == 1, cnt
