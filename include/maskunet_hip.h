@@ -621,6 +621,33 @@ int mu_resize_u8_nhwc(const unsigned char* src, int B, int Hs, int Ws, int C, in
 /* the label map: uint8 [B][Hs][Ws] -> int64 [B][Hd][Wd] = torch.from_numpy(cv2.resize(mask, (Wd, Hd), interpolation=cv2.INTER_NEAREST)).long()
  * (:73,78): source index min(floor(d * scale), n - 1) */
 int mu_resize_nearest_u8(const unsigned char* src, int B, int Hs, int Ws, long* dst, int Hd, int Wd, void* stream);
+/* f4, the Pillow half: a RAGGED batch of decoded image bytes -> the network input by Pillow's ANTIALIASED bilinear resample, i.e.
+ * T.ToPILImage() -> T.Resize((Hd, Wd)) -> T.ToTensor() (coco_instance.py:43-47,68) = Image.resize((Wd, Hd), Image.BILINEAR).  Restated from
+ * Pillow's Resample.c and pinned to the bytes of Pillow 12.2.0 (tests/golden/pil/); this text is the specification.
+ * Coefficients of one axis, n_in -> n_out, in fp64 with every operation rounded on its own (NO fused multiply-add), in this order:
+ *   scale = n_in / n_out;  fs = max(scale, 1.0);  support = fs;  ss = 1.0 / fs;  ksize = 2 * ceil(support) + 1
+ *   output index xx:  center = (xx + 0.5) * scale
+ *                     xmin = max((int)(center - support + 0.5), 0);  xmax = min((int)(center + support + 0.5), n_in);  n = xmax - xmin
+ *                     w[x] = max(0, 1 - |(x + xmin - center + 0.5) * ss|) for x < n;  ww = w[0] + w[1] + .. in ascending x;
+ *                     w[x] /= ww if ww != 0;  k[x] = (int)(0.5 + w[x] * 2^22)              ((int) = C truncation; every argument is >= 0)
+ * One pass: out = clamp((2^21 + sum_x src[xmin + x] * k[x]) >> 22, 0, 255) in int32 (no overflow within the limits below).
+ * Two passes: horizontal, then vertical, the intermediate ROUNDED TO uint8 (an axis that keeps its size has k = {2^22, 0}: the identity,
+ * as Pillow skipping that pass).  Channels are independent; C is 1 or 3 (Pillow resizes RGBA premultiplied: refused).  Then ToTensor:
+ * dst [B][Hd][Wd][Cp] = float(byte) / 255.0f by IEEE division, rounded to nearest even for fp16 storage, padding channels zero -- the rule
+ * of mu_u8_to_nhwc.  swap_rb != 0 swaps channels 0 and 2 (cv2.imread bytes).  u8_out (may be NULL) receives the bytes [B][Hd][Wd][C].
+ * Image b is the h * w * C bytes at src + offsets[b], (h, w) = sizes[b][0..1]; offsets int64 [B+1] in bytes and sizes int32 [B][2] are
+ * DEVICE arrays, image starts need no alignment, and the host passes only the bounds max_h, max_w.  An image is REFUSED (valid[b] = 0, all
+ * of its outputs zero, nothing of it read) if h or w lies outside [1, max_h] / [1, max_w]; if h > 100 * w and Hd < h (Pillow 12 resizes
+ * those vertically first; h == 100 * w is inside); or if offsets[b] < 0 or offsets[b+1] - offsets[b] < h * w * C.  valid is uint8 [B].
+ * Limits: B >= 1, 1 <= max_h, max_w <= 16384, Hd * Wd <= 65536, C in {1, 3}, Cp % 32 == 0, Cp >= C, dtype MU_F32 or MU_F16.  A null
+ * pointer (u8_out apart), a scalar outside the limits or a workspace shorter than mu_pil_resize_workspace_bytes (host only; -1 for
+ * arguments outside the limits) returns MU_ERR_ARG without touching the GPU.  Every output byte is written on every call.  Two launches
+ * (coefficient tables into the workspace, then the resample), stream-ordered, no atomics, no host synchronisation: bit-identical from run
+ * to run and capturable in a graph. */
+long mu_pil_resize_workspace_bytes(int B, int max_h, int max_w, int Hd, int Wd);
+int mu_pil_resize_u8_nhwc(const unsigned char* src, const long* offsets, const int* sizes, int B, int C, int max_h, int max_w, int swap_rb,
+                          void* dst, unsigned char* u8_out, unsigned char* valid, int Hd, int Wd, int Cp, int dtype, void* workspace,
+                          long workspace_bytes, void* stream);
 /* f2: optim.AdamW step (ade_semantic.py:379,401) for every parameter in one launch.  table: device array of `ntensors` entries
  * {float* p; const float* g; float* m; float* v; long n; long step;} (48 bytes; g may be NULL = no gradient this step; step = that
  * tensor's own count of attempted updates including this one, torch keeps one counter per parameter); block_tensor/block_chunk:

@@ -14,6 +14,7 @@ from .matching import InstanceAP, Matches, PanopticQuality, match_instances
 from .metrics import SemanticBatch, SemanticMetrics, metrics_from_counts, semantic_eval
 from .rle import RLEs, decode_rle, encode_rle, rle_counts_from_string, rle_string_from_counts
 from .coco import CocoMasks, coco_masks
+from .images import PackedImages, pack_images, resize_pil_to_nhwc
 from .ops import resize_labels_u8, resize_u8_to_nhwc
 from .optim import FusedAdamW
 from .graph import GraphedStep
@@ -26,5 +27,5 @@ __all__ = ["ConvBlock", "DownSample", "UpSample", "Mask2FormerAttention", "UNet"
            "instances_from_labels", "generate_instance_mask", "Instances", "instances_from_embeddings", "match_instances", "Matches",
            "InstanceAP", "PanopticQuality", "RLEs", "encode_rle", "decode_rle", "rle_counts_from_string", "rle_string_from_counts",
            "coco_masks", "CocoMasks", "instances_from_id_map", "semantic_eval", "SemanticBatch", "SemanticMetrics",
-           "metrics_from_counts"]
+           "metrics_from_counts", "resize_pil_to_nhwc", "pack_images", "PackedImages"]
 __version__ = "0.1.0"

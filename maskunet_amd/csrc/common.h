@@ -204,6 +204,9 @@ template <> struct Vec16<h16> {
     __device__ __forceinline__ void zero() { v = (h16x8)(h16)0; }
 };
 
+// ToTensor of one image byte: byte / 255 by IEEE division, as .div(255) on the host (the store then rounds to the storage type)
+__device__ __forceinline__ float mu_u8_unit(int v) { return (float)v / 255.0f; }
+
 __device__ __forceinline__ float mu_gelu(float x) {
     return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
 }

@@ -388,14 +388,32 @@ class UNet(_HipModule):
         self._check_device(x)
         return self.forward_nhwc(ops.to_nhwc(x, self.compute_dtype))[0]
 
-    def forward_u8(self, images_u8_hwc, bgr=False):
+    def forward_u8(self, images_u8_hwc, bgr=False, resample="cv2", check=False):
         """Forward from decoded image bytes: uint8 [B,H,W,3] (HWC) of ANY size, standing in for the reference's pipeline
         ``forward(ToTensor(cv2.resize(img, (hw, hw), interpolation=cv2.INTER_LINEAR)))`` (ade_semantic.py:72-76,85); ``bgr=True`` also
         applies ``cv2.cvtColor(img, cv2.COLOR_BGR2RGB)`` (:65), i.e. takes what cv2.imread returns.  The resize is the RESTATED OpenCV
         4.10 8-bit algorithm (11-bit fixed-point coefficients, 2x2 area shortcut; its CPU restatement lives with the test
         infrastructure) -- exact against that restatement, NOT pinned to bytes produced by a real cv2 build (cv2 is not installed here and not vendored by the reference:
         SURVEY 8-f4 stays "partial" for this half).  ToTensor's division by 255 is exact.  Images that already have the network's size
-        skip the resize (cv2.resize to the same size is the identity)."""
+        skip the resize (cv2.resize to the same size is the identity).
+
+        ``resample="pil"`` stands in for the COCO instance loader instead, ``forward(ToTensor(Resize((hw, hw))(ToPILImage(img))))``
+        (coco_instance.py:43-47,68): Pillow's antialiased bilinear resize, pinned to Pillow's own bytes (images.resize_pil_to_nhwc).
+        There ``images_u8_hwc`` may also be a list of device images of different sizes, [h, w, 3] each.  An image that kernel refuses
+        (taller than 100 widths) enters the network as zeros; ``check=True`` raises for it instead, which costs a synchronisation with
+        the device -- without it nothing here waits for the GPU."""
+        if resample == "pil":
+            from . import images as _images
+            packed = _images.pack_images(images_u8_hwc)
+            self._check_device(packed.data)
+            H, W = int(self.norm.normalized_shape[1]), int(self.norm.normalized_shape[2])
+            x, valid = _images.resize_pil_to_nhwc(packed, (H, W), self.compute_dtype, bgr=bgr)
+            if check and not bool(valid.all()):
+                raise RuntimeError(f"maskunet_amd: the Pillow resize refused images {(valid == 0).nonzero().flatten().tolist()} (size outside "
+                                   "the contract: taller than 100 widths)")
+            return self._finish(self.forward_nhwc(x))
+        if resample != "cv2":
+            raise ValueError(f'resample must be "cv2" or "pil", got {resample!r}')
         self._check_device(images_u8_hwc)
         H, W = int(self.norm.normalized_shape[1]), int(self.norm.normalized_shape[2])
         if tuple(images_u8_hwc.shape[1:3]) == (H, W) and not bgr:
