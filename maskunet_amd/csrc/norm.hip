@@ -439,6 +439,24 @@ static inline int ew_grid(long total, int cv) {
     g = (g + m - 1) / m * m;
     return (int)g;
 }
+// launch geometry of the statistics sweeps: cv 16-byte vectors per row of C elements (N per vector), rpi rows per block iteration,
+// the [rpi][C][2] fp64 LDS slab.  More than one block's threads per row: MU_ERR_SHAPE
+struct StatGeom { int cv, rpi; size_t lds; };
+static inline int stat_geom(int C, int N, StatGeom& sg) {
+    sg.cv = C / N;
+    if (sg.cv > 256) return MU_ERR_SHAPE;
+    sg.rpi = 256 / sg.cv;
+    sg.lds = (size_t)sg.rpi * C * 2 * sizeof(double);
+    return MU_OK;
+}
+// storage dispatch: f(T{}) with T the element type behind `dtype`; any other dtype is MU_ERR_ARG (MU_F32X, where an entry point takes
+// it, is that entry point's own case)
+template <typename F>
+static inline int with_storage(int dtype, F&& f) {
+    if (dtype == MU_F32) return f(float{});
+    if (dtype == MU_F16) return f(h16{});
+    return MU_ERR_ARG;
+}
 
 __global__ void colsum_final_kernel(const double* __restrict__ part, int nblk, int C, float* __restrict__ out) {
     const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -501,43 +519,43 @@ extern "C" int mu_colsum(const void* x, long M, int C, long ld, float* out, void
     if (ws_bytes < mu_colsum_workspace_bytes(C)) return MU_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int nblk = stat_blocks(M);
-    if (dtype == MU_F32) {
-        const int cv = C / 4;
-        if (cv > 256) return MU_ERR_SHAPE;
-        bn_partial_kernel<float, 0><<<nblk, 256, (size_t)(256 / cv) * C * 2 * sizeof(double), st>>>((const float*)x, nullptr, nullptr, nullptr, M, C, ld, nullptr, nullptr, nullptr, nullptr, 0, (double*)workspace);
-    } else if (dtype == MU_F16) {
-        const int cv = C / 8;
-        if (cv > 256) return MU_ERR_SHAPE;
-        bn_partial_kernel<h16, 0><<<nblk, 256, (size_t)(256 / cv) * C * 2 * sizeof(double), st>>>((const h16*)x, nullptr, nullptr, nullptr, M, C, ld, nullptr, nullptr, nullptr, nullptr, 0, (double*)workspace);
-    } else if (dtype == MU_F32X) {                           // x chunk-encoded (mu_split_encode form, or written so by mu_attn_bwd_phases)
-        const int cv = C / 4;
-        if (cv > 256 || ld % 4) return MU_ERR_SHAPE;
-        colsum_enc_partial_kernel<<<nblk, 256, (size_t)(256 / cv) * C * sizeof(double), st>>>((const uint4*)x, M, C, ld, (double*)workspace);
-    } else return MU_ERR_ARG;
+    StatGeom sg;
+    if (dtype == MU_F32X) {                                  // x chunk-encoded (mu_split_encode form, or written so by mu_attn_bwd_phases)
+        if (stat_geom(C, 4, sg) || ld % 4) return MU_ERR_SHAPE;
+        colsum_enc_partial_kernel<<<nblk, 256, sg.lds / 2, st>>>((const uint4*)x, M, C, ld, (double*)workspace);   // LDS [rpi][C]
+    } else {
+        const int rc = with_storage(dtype, [&](auto tag) -> int {
+            using T = decltype(tag);
+            if (int e = stat_geom(C, Vec16<T>::N, sg)) return e;
+            bn_partial_kernel<T, 0><<<nblk, 256, sg.lds, st>>>((const T*)x, nullptr, nullptr, nullptr, M, C, ld, nullptr, nullptr, nullptr, nullptr, 0, (double*)workspace);
+            return MU_OK;
+        });
+        if (rc) return rc;
+    }
     colsum_final_kernel<<<mu_cdiv(C, 4), 256, 0, st>>>((const double*)workspace, nblk, C, out);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
 
-// fp64 partial slab | s1, s2 (the apply pass's per-channel means) | A (mu_bn_pair_bwd: the single-layer dgamma nobody outside reads)
-// ... | bound[C] | per-block, per-channel (max|dz|, max|xhat|) of the backward statistics sweep (mu_bn_act_bwd_h)
-extern "C" long mu_bn_workspace_bytes(int C) {
-    return (long)MU_STAT_MAXBLK * C * 2 * sizeof(double) + 4L * C * sizeof(float) + (long)MU_STAT_MAXBLK * C * 2 * sizeof(float);
-}
+// The BatchNorm workspace: the one description of its layout (mu_bn_workspace_bytes is bytes(); nothing else offsets into it)
+struct BnWs {
+    double* part;   // [MU_STAT_MAXBLK][C][2] fp64 partial sums of the statistics sweeps: (block, channel, 2)
+    float* s1;      // [C] the apply pass's per-channel means: dbeta / M
+    float* s2;      // [C]                                     xscale * dgamma / M
+    float* A;       // [C] mu_bn_pair_bwd: the single-layer dgamma nobody outside reads
+    float* bound;   // [C] mu_bn_act_bwd_h: per-channel bound of |dx|
+    float* pmax;    // [MU_STAT_MAXBLK][C][2] mu_bn_act_bwd_h: per-block, per-channel (max|dz|, max|xhat|) of the backward statistics sweep
+    static constexpr long vec_off(int C) { return (long)MU_STAT_MAXBLK * C * 2 * sizeof(double); }
+    static constexpr long pmax_off(int C) { return vec_off(C) + 4L * C * sizeof(float); }
+    static constexpr long bytes(int C) { return (long)MU_STAT_MAXBLK * C * 2 * sizeof(double) + 4L * C * sizeof(float) + (long)MU_STAT_MAXBLK * C * 2 * sizeof(float); }
+    BnWs(void* ws, int C) : part((double*)ws), s1((float*)((char*)ws + vec_off(C))), s2(s1 + C), A(s2 + C), bound(A + C),
+                            pmax((float*)((char*)ws + pmax_off(C))) {}
+};
+// the last region ends at bytes(), the size external callers allocate by
+static_assert(BnWs::pmax_off(8) + MU_STAT_MAXBLK * 8 * 2 * sizeof(float) == BnWs::bytes(8) &&
+              BnWs::pmax_off(152) + MU_STAT_MAXBLK * 152 * 2 * sizeof(float) == BnWs::bytes(152), "BatchNorm workspace layout");
 
-template <typename T>
-static int bn_train_stats_t(const T* x, long M, int C, long ld, float* mean, float* rstd, float* rmean, float* rvar, long* nbt,
-                            int c_valid, float momentum, float eps, void* ws, hipStream_t st) {
-    constexpr int N = Vec16<T>::N;
-    int cv = C / N;
-    if (cv > 256) return MU_ERR_SHAPE;
-    int rpi = 256 / cv;
-    int nblk = stat_blocks(M);
-    size_t lds = (size_t)rpi * C * 2 * sizeof(double);
-    bn_partial_kernel<T, 0><<<nblk, 256, lds, st>>>(x, nullptr, nullptr, nullptr, M, C, ld, nullptr, nullptr, nullptr, nullptr, 0, (double*)ws);
-    bn_fwd_final_kernel<false><<<mu_cdiv(C, 4), 256, 0, st>>>((const double*)ws, nblk, C, M, eps, momentum, mean, rstd, rmean, rvar, c_valid, nbt);
-    return MU_OK;
-}
+extern "C" long mu_bn_workspace_bytes(int C) { return BnWs::bytes(C); }
 
 extern "C" int mu_bn_train_stats(const void* x, long M, int C, long ld, float* mean, float* rstd, float* running_mean,
                                  float* running_var, long* num_batches_tracked, int c_valid, float momentum, float eps,
@@ -545,13 +563,18 @@ extern "C" int mu_bn_train_stats(const void* x, long M, int C, long ld, float* m
     if (!x || !mean || !rstd || !workspace || M <= 0 || C <= 0 || C % 8 || ld < C) return MU_ERR_ARG;
     if (ws_bytes < mu_bn_workspace_bytes(C)) return MU_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (dtype == MU_F32) rc = bn_train_stats_t<float>((const float*)x, M, C, ld, mean, rstd, running_mean, running_var, num_batches_tracked, c_valid, momentum, eps, workspace, st);
-    else if (dtype == MU_F16) rc = bn_train_stats_t<h16>((const h16*)x, M, C, ld, mean, rstd, running_mean, running_var, num_batches_tracked, c_valid, momentum, eps, workspace, st);
-    else return MU_ERR_ARG;
-    if (rc) return rc;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    double* part = BnWs(workspace, C).part;
+    const int nblk = stat_blocks(M);
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        StatGeom sg;
+        if (int e = stat_geom(C, Vec16<T>::N, sg)) return e;
+        bn_partial_kernel<T, 0><<<nblk, 256, sg.lds, st>>>((const T*)x, nullptr, nullptr, nullptr, M, C, ld, nullptr, nullptr, nullptr, nullptr, 0, part);
+        bn_fwd_final_kernel<false><<<mu_cdiv(C, 4), 256, 0, st>>>(part, nblk, C, M, eps, momentum, mean, rstd, running_mean, running_var, c_valid,
+                                                            num_batches_tracked);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 // Statistics from the conv epilogue's per-tile rows: part[rows][C][2] floats (sum, sum of squares of the fp16 outputs).
@@ -643,12 +666,14 @@ extern "C" int mu_bn_eval_fold(const float* running_mean1, const float* running_
         default:          { constexpr int A_ = MU_ACT_NONE; CALL; } break; \
     }
 template <typename T, bool ENC>
-static void bn_act_fwd_launch(const T* x, const T* res, T* y, long M, int C, long ld, const float* mean, const float* rstd,
-                              const float* gamma, const float* beta, int act, hipStream_t st, h16* y16 = nullptr) {
+static int bn_act_fwd_launch(const T* x, const T* res, T* y, long M, int C, long ld, const float* mean, const float* rstd,
+                             const float* gamma, const float* beta, int act, hipStream_t st, h16* y16 = nullptr) {
     constexpr int N = Vec16<T>::N;
     const int grid = ew_grid(M * (C / N), C / N);
     if (res) { MU_BN_ACT_SWITCH(act, (bn_act_fwd_kernel<T, ENC, A_, 1><<<grid, 256, 0, st>>>(x, res, y, M, C, ld, mean, rstd, gamma, beta, act, y16))) }
     else     { MU_BN_ACT_SWITCH(act, (bn_act_fwd_kernel<T, ENC, A_, 0><<<grid, 256, 0, st>>>(x, res, y, M, C, ld, mean, rstd, gamma, beta, act, y16))) }
+    MU_CHECK_LAUNCH();
+    return MU_OK;
 }
 
 // fp32x: mu_bn_act_fwd(MU_F32X) with the second output y16 (M rows of C halves, row stride C; contiguous input rows: ld == C)
@@ -656,9 +681,7 @@ extern "C" int mu_bn_act_fwd_enc(const void* x, const void* res, void* y_enc, vo
                                  const float* gamma, const float* beta, int act, void* stream) {
     if (!x || !y_enc || !y16 || !mean || !rstd || !gamma || !beta || M <= 0 || C <= 0 || C % 8) return MU_ERR_ARG;
     if (act != MU_ACT_NONE && act != MU_ACT_GELU && act != MU_ACT_RELU) return MU_ERR_ARG;
-    bn_act_fwd_launch<float, true>((const float*)x, (const float*)res, (float*)y_enc, M, C, C, mean, rstd, gamma, beta, act, (hipStream_t)stream, (h16*)y16);
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    return bn_act_fwd_launch<float, true>((const float*)x, (const float*)res, (float*)y_enc, M, C, C, mean, rstd, gamma, beta, act, (hipStream_t)stream, (h16*)y16);
 }
 
 extern "C" int mu_bn_act_fwd(const void* x, const void* res, void* y, long M, int C, long ld, const float* mean, const float* rstd,
@@ -666,70 +689,75 @@ extern "C" int mu_bn_act_fwd(const void* x, const void* res, void* y, long M, in
     if (!x || !y || !mean || !rstd || !gamma || !beta || M <= 0 || C <= 0 || C % 8 || ld < C) return MU_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (act != MU_ACT_NONE && act != MU_ACT_GELU && act != MU_ACT_RELU) return MU_ERR_ARG;
-    if (dtype == MU_F32)
-        bn_act_fwd_launch<float, false>((const float*)x, (const float*)res, (float*)y, M, C, ld, mean, rstd, gamma, beta, act, st);
-    else if (dtype == MU_F32X)      // fp32 storage, y written chunk-encoded (it only feeds a convolution in the fp32x mode)
-        bn_act_fwd_launch<float, true>((const float*)x, (const float*)res, (float*)y, M, C, ld, mean, rstd, gamma, beta, act, st);
-    else if (dtype == MU_F16)
-        bn_act_fwd_launch<h16, false>((const h16*)x, (const h16*)res, (h16*)y, M, C, ld, mean, rstd, gamma, beta, act, st);
-    else return MU_ERR_ARG;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    if (dtype == MU_F32X)           // fp32 storage, y written chunk-encoded (it only feeds a convolution in the fp32x mode)
+        return bn_act_fwd_launch<float, true>((const float*)x, (const float*)res, (float*)y, M, C, ld, mean, rstd, gamma, beta, act, st);
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        return bn_act_fwd_launch<T, false>((const T*)x, (const T*)res, (T*)y, M, C, ld, mean, rstd, gamma, beta, act, st);
+    });
 }
 
+// One BatchNorm backward: what the four entry points below hand to bn_bwd_launch
 template <typename T>
-static int bn_act_bwd_t(const T* x, const T* res, const T* g, T* dx, T* dres, long M, int C, long ld, const float* mean,
-                        const float* rstd, const float* gamma, const float* beta, int act, int training, float* dgamma,
-                        float* dbeta, void* ws, hipStream_t st, const float* xscale = nullptr, bool enc = false, const float* pc2 = nullptr,
-                        const float* pc1 = nullptr, float* pair_grads = nullptr, float* dy_scale = nullptr) {
-    constexpr int N = Vec16<T>::N;
-    int cv = C / N;
-    if (cv > 256) return MU_ERR_SHAPE;
-    int rpi = 256 / cv;
+struct BnBwd {
+    const T *x, *res, *g;                           // res (and dres) may be NULL
+    T *dx, *dres;
+    long M; int C; long ld;
+    const float *mean, *rstd, *gamma, *beta;
+    int act, training;
+    float *dgamma, *dbeta;
+    const float* xscale = nullptr;                  // BatchNorm pair: the factor of the xhat term
+    const float *pc2 = nullptr, *pc1 = nullptr;     // BatchNorm pair: dgamma2 / dgamma1 coefficients of ...
+    float* pair_grads = nullptr;                    // ... [3][C] dgamma2, dgamma1, dbeta1
+    float* dy_scale = nullptr;                      // ENC: {S, 1 / S} of the fp16 dx rows
+};
+
+// Partial sweep, finalize, apply.  The entry points have refused null pointers, an unpaired res / dres and bad M, C, C % 8, ld
+// (MU_ERR_ARG), then a short workspace (MU_ERR_WORKSPACE), then an unknown dtype (MU_ERR_ARG); here follow too many channel vectors
+// (MU_ERR_SHAPE), an unknown activation (MU_ERR_ARG) and an encoded request without dy_scale or with ld != C (MU_ERR_ARG).  Nothing
+// is launched before the last check has passed.  ENC: dx as fp16 rows under one scale -- fp32 storage only.
+template <typename T, bool ENC>
+static int bn_bwd_launch(const BnBwd<T>& a, const BnWs& ws, hipStream_t st) {
+    static_assert(!ENC || sizeof(T) == 4, "fp16 dx rows come from fp32 storage");
+    StatGeom sg;
+    if (int e = stat_geom(a.C, Vec16<T>::N, sg)) return e;
+    if (a.act != MU_ACT_NONE && a.act != MU_ACT_GELU && a.act != MU_ACT_RELU) return MU_ERR_ARG;
+    if (ENC && (!a.dy_scale || a.ld != a.C)) return MU_ERR_ARG;                    // fp16 dx rows: contiguous rows
     // the backward statistics kernel holds 3 blocks per CU (136 VGPRs): 768 resident blocks = one whole round (1024 would leave a
     // second round one third full)
-    int nblk = stat_blocks(M);
+    int nblk = stat_blocks(a.M);
     if (nblk > 768) nblk = 768;
-    size_t lds = (size_t)rpi * C * 2 * sizeof(double);
-    double* part = (double*)ws;
-    float* s1 = (float*)((char*)ws + (size_t)MU_STAT_MAXBLK * C * 2 * sizeof(double));
-    float* s2 = s1 + C;
-    float* bound = s1 + 3 * (size_t)C;
-    float* pmax = bound + C;
-    if (act != MU_ACT_NONE && act != MU_ACT_GELU && act != MU_ACT_RELU) return MU_ERR_ARG;
-    if (enc && (sizeof(T) != 4 || !dy_scale || ld != C)) return MU_ERR_ARG;      // fp16 dx rows: fp32 storage, contiguous rows
-    if (res) {                      // d(residual) == dz exactly, so it doubles as the dz buffer
-        if constexpr (sizeof(T) == 4) {
-            if (enc) {
-                MU_BN_ACT_SWITCH(act, (bn_partial_kernel<T, 1, A_, 1, true><<<nblk, 256, lds, st>>>(x, g, res, dres, M, C, ld, mean, rstd, gamma, beta, act, part, pmax)))
-                bn_bwd_final_kernel<<<mu_cdiv(C, 4), 256, 0, st>>>(part, nblk, C, M, training, dgamma, dbeta, s1, s2, xscale, nullptr, nullptr, nullptr, pmax, gamma, rstd, bound);
-                bn_bwd_apply_kernel<T, false, true><<<ew_grid(M * cv, cv), 256, 0, st>>>(x, dres, dx, M, C, ld, mean, rstd, gamma, beta, act, s1, s2, bound, dy_scale);
-                return MU_OK;
-            }
-        }
-        MU_BN_ACT_SWITCH(act, (bn_partial_kernel<T, 1, A_, 1><<<nblk, 256, lds, st>>>(x, g, res, dres, M, C, ld, mean, rstd, gamma, beta, act, part)))
-        bn_bwd_final_kernel<<<mu_cdiv(C, 4), 256, 0, st>>>(part, nblk, C, M, training, dgamma, dbeta, s1, s2, xscale);
-        bn_bwd_apply_kernel<T, false><<<ew_grid(M * cv, cv), 256, 0, st>>>(x, dres, dx, M, C, ld, mean, rstd, gamma, beta, act, s1, s2);
+    const int agrid = ew_grid(a.M * sg.cv, sg.cv);
+    float* pmax = ENC ? ws.pmax : nullptr;
+    float* bound = ENC ? ws.bound : nullptr;
+    if (a.res) {                    // d(residual) == dz exactly, so it doubles as the dz buffer
+        MU_BN_ACT_SWITCH(a.act, (bn_partial_kernel<T, 1, A_, 1, ENC><<<nblk, 256, sg.lds, st>>>(a.x, a.g, a.res, a.dres, a.M, a.C, a.ld, a.mean, a.rstd, a.gamma, a.beta, a.act, ws.part, pmax)))
     } else {                        // no residual: nothing is written by the statistics sweep, dz is recomputed in the apply pass
-        if constexpr (sizeof(T) == 4) {
-            if (enc) {
-                MU_BN_ACT_SWITCH(act, (bn_partial_kernel<T, 1, A_, 0, true><<<nblk, 256, lds, st>>>(x, g, nullptr, nullptr, M, C, ld, mean, rstd, gamma, beta, act, part, pmax)))
-                bn_bwd_final_kernel<<<mu_cdiv(C, 4), 256, 0, st>>>(part, nblk, C, M, training, dgamma, dbeta, s1, s2, xscale, pc2, pc1, pair_grads, pmax, gamma, rstd, bound);
-                MU_BN_ACT_SWITCH(act, (bn_bwd_apply_kernel<T, true, true, A_><<<ew_grid(M * cv, cv), 256, 0, st>>>(x, g, dx, M, C, ld, mean, rstd, gamma, beta, act, s1, s2, bound, dy_scale)))
-                return MU_OK;
-            }
-        }
-        MU_BN_ACT_SWITCH(act, (bn_partial_kernel<T, 1, A_, 0><<<nblk, 256, lds, st>>>(x, g, nullptr, nullptr, M, C, ld, mean, rstd, gamma, beta, act, part)))
-        bn_bwd_final_kernel<<<mu_cdiv(C, 4), 256, 0, st>>>(part, nblk, C, M, training, dgamma, dbeta, s1, s2, xscale, pc2, pc1, pair_grads);
-        MU_BN_ACT_SWITCH(act, (bn_bwd_apply_kernel<T, true, false, A_><<<ew_grid(M * cv, cv), 256, 0, st>>>(x, g, dx, M, C, ld, mean, rstd, gamma, beta, act, s1, s2)))
+        MU_BN_ACT_SWITCH(a.act, (bn_partial_kernel<T, 1, A_, 0, ENC><<<nblk, 256, sg.lds, st>>>(a.x, a.g, nullptr, nullptr, a.M, a.C, a.ld, a.mean, a.rstd, a.gamma, a.beta, a.act, ws.part, pmax)))
     }
+    bn_bwd_final_kernel<<<mu_cdiv(a.C, 4), 256, 0, st>>>(ws.part, nblk, a.C, a.M, a.training, a.dgamma, a.dbeta, ws.s1, ws.s2, a.xscale, a.pc2, a.pc1, a.pair_grads,
+                                                         pmax, ENC ? a.gamma : nullptr, ENC ? a.rstd : nullptr, bound);
+    if (a.res) bn_bwd_apply_kernel<T, false, ENC><<<agrid, 256, 0, st>>>(a.x, a.dres, a.dx, a.M, a.C, a.ld, a.mean, a.rstd, a.gamma, a.beta, a.act, ws.s1, ws.s2, bound, a.dy_scale);
+    else { MU_BN_ACT_SWITCH(a.act, (bn_bwd_apply_kernel<T, true, ENC, A_><<<agrid, 256, 0, st>>>(a.x, a.g, a.dx, a.M, a.C, a.ld, a.mean, a.rstd, a.gamma, a.beta, a.act, ws.s1, ws.s2, bound, a.dy_scale))) }
+    MU_CHECK_LAUNCH();
     return MU_OK;
 }
 
 extern "C" int mu_bn_act_bwd_scaled(const void* x, const void* res, const void* grad_out, void* dx, void* dres, long M, int C, long ld,
                                     const float* mean, const float* rstd, const float* gamma, const float* beta, int act, int training,
                                     float* dgamma, float* dbeta, const float* xhat_scale, void* workspace, long ws_bytes, int dtype,
-                                    void* stream);
+                                    void* stream) {
+    if (!x || !grad_out || !dx || !mean || !rstd || !gamma || !beta || !dgamma || !dbeta || !workspace) return MU_ERR_ARG;
+    if ((res != nullptr) != (dres != nullptr)) return MU_ERR_ARG;
+    if (M <= 0 || C <= 0 || C % 8 || ld < C) return MU_ERR_ARG;
+    if (ws_bytes < BnWs::bytes(C)) return MU_ERR_WORKSPACE;
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        BnBwd<T> a{(const T*)x, (const T*)res, (const T*)grad_out, (T*)dx, (T*)dres, M, C, ld, mean, rstd, gamma, beta, act, training, dgamma, dbeta};
+        a.xscale = xhat_scale;
+        return bn_bwd_launch<T, false>(a, BnWs(workspace, C), (hipStream_t)stream);
+    });
+}
 
 extern "C" int mu_bn_act_bwd(const void* x, const void* res, const void* grad_out, void* dx, void* dres, long M, int C, long ld,
                              const float* mean, const float* rstd, const float* gamma, const float* beta, int act, int training,
@@ -786,26 +814,6 @@ extern "C" int mu_bn_pair_compose(const float* rstd1, const float* gamma1, const
     return MU_OK;
 }
 
-extern "C" int mu_bn_act_bwd_scaled(const void* x, const void* res, const void* grad_out, void* dx, void* dres, long M, int C, long ld,
-                                    const float* mean, const float* rstd, const float* gamma, const float* beta, int act, int training,
-                                    float* dgamma, float* dbeta, const float* xhat_scale, void* workspace, long ws_bytes, int dtype,
-                                    void* stream) {
-    if (!x || !grad_out || !dx || !mean || !rstd || !gamma || !beta || !dgamma || !dbeta || !workspace) return MU_ERR_ARG;
-    if ((res != nullptr) != (dres != nullptr)) return MU_ERR_ARG;
-    if (M <= 0 || C <= 0 || C % 8 || ld < C) return MU_ERR_ARG;
-    if (ws_bytes < mu_bn_workspace_bytes(C)) return MU_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (dtype == MU_F32)
-        rc = bn_act_bwd_t<float>((const float*)x, (const float*)res, (const float*)grad_out, (float*)dx, (float*)dres, M, C, ld, mean, rstd, gamma, beta, act, training, dgamma, dbeta, workspace, st, xhat_scale);
-    else if (dtype == MU_F16)
-        rc = bn_act_bwd_t<h16>((const h16*)x, (const h16*)res, (const h16*)grad_out, (h16*)dx, (h16*)dres, M, C, ld, mean, rstd, gamma, beta, act, training, dgamma, dbeta, workspace, st, xhat_scale);
-    else return MU_ERR_ARG;
-    if (rc) return rc;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
-}
-
 extern "C" int mu_bn_pair_bwd(const void* x, const void* grad_out, void* dx, long M, int C, long ld, const float* mean, const float* rstd,
                               const float* gamma_eff, const float* beta2, const float* xhat_scale, const float* dgamma2_coef,
                               const float* dgamma1_coef, float* pair_grads, float* dbeta2, void* workspace, long ws_bytes, int dtype,
@@ -814,18 +822,14 @@ extern "C" int mu_bn_pair_bwd(const void* x, const void* grad_out, void* dx, lon
         !dbeta2 || !workspace)
         return MU_ERR_ARG;
     if (M <= 0 || C <= 0 || C % 8 || ld < C) return MU_ERR_ARG;
-    if (ws_bytes < mu_bn_workspace_bytes(C)) return MU_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    float* A = (float*)((char*)workspace + (size_t)MU_STAT_MAXBLK * C * 2 * sizeof(double)) + 2 * (size_t)C;
-    int rc;
-    if (dtype == MU_F32)
-        rc = bn_act_bwd_t<float>((const float*)x, nullptr, (const float*)grad_out, (float*)dx, nullptr, M, C, ld, mean, rstd, gamma_eff, beta2, MU_ACT_NONE, 1, A, dbeta2, workspace, st, xhat_scale, false, dgamma2_coef, dgamma1_coef, pair_grads);
-    else if (dtype == MU_F16)
-        rc = bn_act_bwd_t<h16>((const h16*)x, nullptr, (const h16*)grad_out, (h16*)dx, nullptr, M, C, ld, mean, rstd, gamma_eff, beta2, MU_ACT_NONE, 1, A, dbeta2, workspace, st, xhat_scale, false, dgamma2_coef, dgamma1_coef, pair_grads);
-    else return MU_ERR_ARG;
-    if (rc) return rc;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    if (ws_bytes < BnWs::bytes(C)) return MU_ERR_WORKSPACE;
+    const BnWs ws(workspace, C);
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        BnBwd<T> a{(const T*)x, nullptr, (const T*)grad_out, (T*)dx, nullptr, M, C, ld, mean, rstd, gamma_eff, beta2, MU_ACT_NONE, 1, ws.A, dbeta2};
+        a.xscale = xhat_scale; a.pc2 = dgamma2_coef; a.pc1 = dgamma1_coef; a.pair_grads = pair_grads;
+        return bn_bwd_launch<T, false>(a, ws, (hipStream_t)stream);
+    });
 }
 
 // fp32x (round 6): the same backward passes with dx written as ONE power-of-two-scaled fp16 operand -- dx is the dy of the 3x3
@@ -841,12 +845,10 @@ extern "C" int mu_bn_act_bwd_h(const void* x, const void* res, const void* grad_
     if (!x || !grad_out || !dx_h || !mean || !rstd || !gamma || !beta || !dgamma || !dbeta || !dy_scale || !workspace) return MU_ERR_ARG;
     if ((res != nullptr) != (dres != nullptr)) return MU_ERR_ARG;
     if (M <= 0 || C <= 0 || C % 8) return MU_ERR_ARG;
-    if (ws_bytes < mu_bn_workspace_bytes(C)) return MU_ERR_WORKSPACE;
-    int rc = bn_act_bwd_t<float>((const float*)x, (const float*)res, (const float*)grad_out, (float*)dx_h, (float*)dres, M, C, C, mean, rstd, gamma,
-                                 beta, act, training, dgamma, dbeta, workspace, (hipStream_t)stream, nullptr, true, nullptr, nullptr, nullptr, dy_scale);
-    if (rc) return rc;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    if (ws_bytes < BnWs::bytes(C)) return MU_ERR_WORKSPACE;
+    BnBwd<float> a{(const float*)x, (const float*)res, (const float*)grad_out, (float*)dx_h, (float*)dres, M, C, C, mean, rstd, gamma, beta, act, training, dgamma, dbeta};
+    a.dy_scale = dy_scale;
+    return bn_bwd_launch<float, true>(a, BnWs(workspace, C), (hipStream_t)stream);
 }
 
 extern "C" int mu_bn_pair_bwd_h(const void* x, const void* grad_out, void* dx_h, long M, int C, const float* mean, const float* rstd,
@@ -857,14 +859,11 @@ extern "C" int mu_bn_pair_bwd_h(const void* x, const void* grad_out, void* dx_h,
         !dbeta2 || !dy_scale || !workspace)
         return MU_ERR_ARG;
     if (M <= 0 || C <= 0 || C % 8) return MU_ERR_ARG;
-    if (ws_bytes < mu_bn_workspace_bytes(C)) return MU_ERR_WORKSPACE;
-    float* A = (float*)((char*)workspace + (size_t)MU_STAT_MAXBLK * C * 2 * sizeof(double)) + 2 * (size_t)C;
-    int rc = bn_act_bwd_t<float>((const float*)x, nullptr, (const float*)grad_out, (float*)dx_h, nullptr, M, C, C, mean, rstd, gamma_eff, beta2,
-                                 MU_ACT_NONE, 1, A, dbeta2, workspace, (hipStream_t)stream, xhat_scale, true, dgamma2_coef, dgamma1_coef, pair_grads,
-                                 dy_scale);
-    if (rc) return rc;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    if (ws_bytes < BnWs::bytes(C)) return MU_ERR_WORKSPACE;
+    const BnWs ws(workspace, C);
+    BnBwd<float> a{(const float*)x, nullptr, (const float*)grad_out, (float*)dx_h, nullptr, M, C, C, mean, rstd, gamma_eff, beta2, MU_ACT_NONE, 1, ws.A, dbeta2};
+    a.xscale = xhat_scale; a.pc2 = dgamma2_coef; a.pc1 = dgamma1_coef; a.pair_grads = pair_grads; a.dy_scale = dy_scale;
+    return bn_bwd_launch<float, true>(a, ws, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -989,56 +988,50 @@ __global__ __launch_bounds__(256) void lns_bwd_apply_kernel(const T* __restrict_
     }
 }
 
-extern "C" long mu_ln_sample_workspace_bytes(int B) { return (long)B * LN_CHUNKS * 2 * sizeof(double) + 2L * B * sizeof(float); }
+// The per-sample LayerNorm workspace: the one description of its layout (mu_ln_sample_workspace_bytes is bytes())
+struct LnWs {
+    double* part;   // [B][LN_CHUNKS][2] fp64 partial sums: (sample, chunk, 2)
+    float* m1;      // [B] backward: mean of dy*w
+    float* m2;      // [B] backward: mean of dy*w*xhat
+    static constexpr long m_off(int B) { return (long)B * LN_CHUNKS * 2 * sizeof(double); }
+    static constexpr long bytes(int B) { return (long)B * LN_CHUNKS * 2 * sizeof(double) + 2L * B * sizeof(float); }
+    LnWs(void* ws, int B) : part((double*)ws), m1((float*)((char*)ws + m_off(B))), m2(m1 + B) {}
+};
+static_assert(LnWs::m_off(1) + 2 * sizeof(float) == LnWs::bytes(1) && LnWs::m_off(7) + 2 * 7 * sizeof(float) == LnWs::bytes(7), "LayerNorm workspace layout");
 
-template <typename T>
-static int lns_fwd_t(const T* x, const float* w, const float* b, T* y, float* mean, float* rstd, int B, long L, float eps, void* ws,
-                     hipStream_t st) {
-    constexpr int N = Vec16<T>::N;
-    dim3 grid(LN_CHUNKS, B);
-    lns_partial_kernel<T, 0><<<grid, 256, 0, st>>>(x, nullptr, nullptr, nullptr, nullptr, L, (double*)ws);
-    lns_final_kernel<<<mu_cdiv(B, 4), 256, 0, st>>>((const double*)ws, LN_CHUNKS, L, eps, 0, mean, rstd, B);
-    long nvec = L / N;
-    int g = (int)((nvec + 255) / 256 > 8192 ? 8192 : (nvec + 255) / 256);
-    lns_fwd_apply_kernel<T><<<g, 256, 0, st>>>(x, w, b, mean, rstd, y, L, B);
-    return MU_OK;
-}
+extern "C" long mu_ln_sample_workspace_bytes(int B) { return LnWs::bytes(B); }
+
+// apply passes: blocks of 256 threads, one 16-byte vector (N elements) per thread and trip, at most 8192 blocks
+static inline int lns_apply_grid(long L, int N) { const long g = (L / N + 255) / 256; return (int)(g > 8192 ? 8192 : g); }
 
 extern "C" int mu_ln_sample_fwd(const void* x, const float* w, const float* b, void* y, float* mean, float* rstd, int B, long L,
                                 float eps, void* workspace, long ws_bytes, int dtype, void* stream) {
     if (!x || !w || !b || !y || !mean || !rstd || !workspace || B <= 0 || L <= 0 || L % 8) return MU_ERR_ARG;
-    if (ws_bytes < mu_ln_sample_workspace_bytes(B)) return MU_ERR_WORKSPACE;
+    if (ws_bytes < LnWs::bytes(B)) return MU_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MU_F32) lns_fwd_t<float>((const float*)x, w, b, (float*)y, mean, rstd, B, L, eps, workspace, st);
-    else if (dtype == MU_F16) lns_fwd_t<h16>((const h16*)x, w, b, (h16*)y, mean, rstd, B, L, eps, workspace, st);
-    else return MU_ERR_ARG;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
-}
-
-template <typename T>
-static int lns_bwd_t(const T* x, const T* dy, const float* w, const float* mean, const float* rstd, T* dx, float* dw, float* db,
-                     int B, long L, void* ws, hipStream_t st) {
-    constexpr int N = Vec16<T>::N;
-    dim3 grid(LN_CHUNKS, B);
-    float* m1 = (float*)((char*)ws + (size_t)B * LN_CHUNKS * 2 * sizeof(double));
-    float* m2 = m1 + B;
-    lns_partial_kernel<T, 1><<<grid, 256, 0, st>>>(x, dy, w, mean, rstd, L, (double*)ws);
-    lns_final_kernel<<<mu_cdiv(B, 4), 256, 0, st>>>((const double*)ws, LN_CHUNKS, L, 0.f, 1, m1, m2, B);
-    long nvec = L / N;
-    int g = (int)((nvec + 255) / 256 > 8192 ? 8192 : (nvec + 255) / 256);
-    lns_bwd_apply_kernel<T><<<g, 256, 0, st>>>(x, dy, w, mean, rstd, m1, m2, dx, dw, db, L, B);
-    return MU_OK;
+    const LnWs ws(workspace, B);
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        lns_partial_kernel<T, 0><<<dim3(LN_CHUNKS, B), 256, 0, st>>>((const T*)x, nullptr, nullptr, nullptr, nullptr, L, ws.part);
+        lns_final_kernel<<<mu_cdiv(B, 4), 256, 0, st>>>(ws.part, LN_CHUNKS, L, eps, 0, mean, rstd, B);
+        lns_fwd_apply_kernel<T><<<lns_apply_grid(L, Vec16<T>::N), 256, 0, st>>>((const T*)x, w, b, mean, rstd, (T*)y, L, B);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 extern "C" int mu_ln_sample_bwd(const void* x, const void* dy, const float* w, const float* mean, const float* rstd, void* dx,
                                 float* dw, float* db, int B, long L, void* workspace, long ws_bytes, int dtype, void* stream) {
     if (!x || !dy || !w || !mean || !rstd || !dx || !dw || !db || !workspace || B <= 0 || L <= 0 || L % 8) return MU_ERR_ARG;
-    if (ws_bytes < mu_ln_sample_workspace_bytes(B)) return MU_ERR_WORKSPACE;
+    if (ws_bytes < LnWs::bytes(B)) return MU_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MU_F32) lns_bwd_t<float>((const float*)x, (const float*)dy, w, mean, rstd, (float*)dx, dw, db, B, L, workspace, st);
-    else if (dtype == MU_F16) lns_bwd_t<h16>((const h16*)x, (const h16*)dy, w, mean, rstd, (h16*)dx, dw, db, B, L, workspace, st);
-    else return MU_ERR_ARG;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    const LnWs ws(workspace, B);
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        lns_partial_kernel<T, 1><<<dim3(LN_CHUNKS, B), 256, 0, st>>>((const T*)x, (const T*)dy, w, mean, rstd, L, ws.part);
+        lns_final_kernel<<<mu_cdiv(B, 4), 256, 0, st>>>(ws.part, LN_CHUNKS, L, 0.f, 1, ws.m1, ws.m2, B);
+        lns_bwd_apply_kernel<T><<<lns_apply_grid(L, Vec16<T>::N), 256, 0, st>>>((const T*)x, (const T*)dy, w, mean, rstd, ws.m1, ws.m2, (T*)dx, dw, db, L, B);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }

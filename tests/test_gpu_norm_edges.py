@@ -568,6 +568,55 @@ def test_bn_act_bwd_refusals():
     _refused("MU_ERR_SHAPE", "mu_bn_act_bwd", xw, None, xw, dxw, None, 1, 1032, 1032, *ow, NONE, 1, dgw, dbw, wsw, nw, MU_F32, outs=(dxw, dgw, dbw))
 
 
+def test_bn_act_bwd_refusal_precedence():
+    """an unknown activation at every backward entry point that takes one, and two faults at once: a short workspace is reported before
+    the activation, too many channel vectors before the activation, an unknown dtype and a short workspace at the pair entry points.
+    Every output still holds the sentinel; the same buffers with nothing wrong then give the reference's results."""
+    M, C, BAD_ACT = 4, 8, 3
+    assert BAD_ACT not in (NONE, GELU, RELU)
+    ws, n = _bn_ws(C)
+    dg, db, sc = _out(C, torch.float32, "dgamma"), _out(C, torch.float32, "dbeta"), _out(2, torch.float32, "dy_scale")
+    pg, db2 = _out(3 * C, torch.float32, "pair_grads"), _out(C, torch.float32, "dbeta2")
+    for storage in ("f32", "f16"):
+        T = TORCH[storage]
+        x, res, go, mean, rstd, gamma, beta = bwd_inputs(storage, C, M, NONE, True)
+        X, G, RES = _in(x, T, "x"), _in(go, T, "grad_out"), _in(res, T, "res")
+        ops = [_in(v, torch.float32, k) for v, k in ((mean, "mean"), (rstd, "rstd"), (gamma, "gamma"), (beta, "beta"))]
+        dx, dres = _out(M * C, T, "dx"), _out(M * C, T, "dres")
+        outs = (dx, dres, dg, db, pg, sc)
+        _refused("MU_ERR_ARG", "mu_bn_act_bwd", X, RES, G, dx, dres, M, C, C, *ops, BAD_ACT, 1, dg, db, ws, n, CODE[storage], outs=outs)
+        if storage == "f32":
+            xs = _in(np.ones(C, dtype=np.float32), torch.float32, "xhat_scale")
+            _refused("MU_ERR_ARG", "mu_bn_act_bwd_scaled", X, RES, G, dx, dres, M, C, C, *ops, BAD_ACT, 1, dg, db, xs, ws, n, MU_F32, outs=outs)
+            _refused("MU_ERR_ARG", "mu_bn_act_bwd_h", X, RES, G, dx, dres, M, C, *ops, BAD_ACT, 1, dg, db, sc, ws, n, outs=outs)
+            _refused("MU_ERR_WORKSPACE", "mu_bn_act_bwd", X, RES, G, dx, dres, M, C, C, *ops, BAD_ACT, 1, dg, db, ws, n - 1, MU_F32, outs=outs)   # size first
+        ref = R.bn_act_bwd(x, res, go, mean, rstd, gamma, beta, NONE, 1, None, storage)
+        _compare_bwd(f"refusal precedence, valid {storage}", _bwd_call(storage, x, res, go, mean, rstd, gamma, beta, NONE, 1, None, C), ref,
+                     R.bn_act_bwd_bounds(ref, NONE, storage))
+    # cv = 258 vectors per row: the width is reported before the activation
+    CW = 1032
+    xw = _in(np.zeros((1, CW), dtype=np.float32), torch.float32, "x")
+    ow = [_in(np.ones(CW, dtype=np.float32), torch.float32, "op") for _ in range(4)]
+    dxw, dgw, dbw = _out(CW, torch.float32, "dx"), _out(CW, torch.float32, "dgamma"), _out(CW, torch.float32, "dbeta")
+    wsw, nw = _bn_ws(CW)
+    _refused("MU_ERR_SHAPE", "mu_bn_act_bwd", xw, None, xw, dxw, None, 1, CW, CW, *ow, BAD_ACT, 1, dgw, dbw, wsw, nw, MU_F32, outs=(dxw, dgw, dbw))
+    # the pair entry points
+    x, go, mean, rstd, geff, beta2, xs, c2, c1 = pair_inputs("f32", C, M)
+    X, G = _in(x, torch.float32, "x"), _in(go, torch.float32, "grad_out")
+    ops = [_in(v, torch.float32, k) for v, k in ((mean, "mean"), (rstd, "rstd"), (geff, "gamma_eff"), (beta2, "beta2"), (xs, "xhat_scale"),
+                                                 (c2, "dgamma2_coef"), (c1, "dgamma1_coef"))]
+    dx = _out(M * C, torch.float32, "dx")
+    outs = (dx, dg, db, pg, db2, sc)
+    _refused("MU_ERR_ARG", "mu_bn_pair_bwd", X, G, dx, M, C, C, *ops, pg, db2, ws, n, MU_F32X, outs=outs)
+    _refused("MU_ERR_WORKSPACE", "mu_bn_pair_bwd", X, G, dx, M, C, C, *ops, pg, db2, ws, n - 1, MU_F32, outs=outs)
+    _refused("MU_ERR_WORKSPACE", "mu_bn_pair_bwd_h", X, G, dx, M, C, *ops, pg, db2, sc, ws, n - 1, outs=outs)
+    _call("mu_bn_pair_bwd", X, G, dx, M, C, C, *ops, pg, db2, ws, n, MU_F32)
+    ref = R.bn_act_bwd(x, None, go, mean, rstd, geff, beta2, NONE, 1, xs, "f32")
+    b = R.bn_act_bwd_bounds(ref, NONE, "f32")
+    _check("refusal precedence, valid pair dx", np.abs(_rows(dx, M, C, C, "dx") - ref["dx"]), b["dx"])
+    _compare_pair_grads("refusal precedence, valid pair", _vec(pg).reshape(3, C), _vec(db2), ref, b, c2, c1, C)
+
+
 # ================================================================================================
 # pair: mu_bn_pair_compose, mu_bn_pair_bwd
 # ================================================================================================
