@@ -102,7 +102,8 @@ int mu_cast(const void* src, int src_dtype, void* dst, int dst_dtype, long n, vo
  * mode 2: both in one launch, dst = the mode-0 block followed by the mode-1 block [taps][cols_pad][rows_pad].
  * dtype MU_F32X: fp32-sized blocks in their operand encodings (see MU_F32X) -- taps = 1: both blocks bf16 chunk-encoded; taps = 9: the
  * forward block fp16 chunk-encoded (x 2^6), the data-gradient block as "HL" rows for mu_conv_dgrad_h: each row (tap, in) of the padded
- * output-channel count n becomes [n fp16 lo | n fp16 hi] of 2^6 w (the same bytes). */
+ * output-channel count n becomes [n fp16 lo | n fp16 hi] of 2^6 w (the same bytes).  MU_F32X needs rows_pad % 4 == 0 and
+ * cols_pad % 4 == 0, and with taps = 9 and mode != 0 that n <= 8192: MU_ERR_SHAPE otherwise, before anything is written to dst. */
 int mu_prep_weight(const float* w_oihw, void* dst, int dtype, int O, int I, int taps, int rows_pad, int cols_pad, int mode,
                    void* stream);
 

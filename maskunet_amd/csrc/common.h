@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/maskunet_hip.h"
 
@@ -19,6 +20,24 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 static inline int mu_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// blocks of a grid-stride launch: ceil(total / per_block), at least 1 and at most `cap`
+static inline int mu_grid(long total, long per_block, long cap) {
+    const long g = (total + per_block - 1) / per_block;
+    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+// storage dispatch (host): f(T{}) with T the element type behind `dtype`; any other dtype is MU_ERR_ARG (MU_F32X, where an entry point
+// takes it, is that entry point's own case)
+template <typename F>
+static inline int with_storage(int dtype, F&& f) {
+    if (dtype == MU_F32) return f(float{});
+    if (dtype == MU_F16) return f(h16{});
+    return MU_ERR_ARG;
+}
+// the same for a (source, destination) pair: f(TS{}, TD{})
+template <typename F>
+static inline int with_storage2(int src_dtype, int dst_dtype, F&& f) {
+    return with_storage(src_dtype, [&](auto s) -> int { return with_storage(dst_dtype, [&](auto d) -> int { return f(s, d); }); });
+}
 
 // ------------------------------------------------------------------------------------------
 // MU_F32X ("fp32x"): fp32 STORAGE, matrix products on the bf16 matrix cores with every fp32 operand split into two bf16 parts,

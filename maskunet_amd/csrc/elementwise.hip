@@ -82,37 +82,17 @@ extern "C" int mu_transpose_pad(const void* src, int src_dtype, long src_ld, voi
                                 int batch, int R, int C, int R_pad, void* stream) {
     if (!src || !dst || batch <= 0 || R <= 0 || C <= 0 || src_ld < C || R_pad < R || dst_ld < R_pad) return MU_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    const size_t es = src_dtype == MU_F32 ? 4 : 2, ed = dst_dtype == MU_F32 ? 4 : 2;
-    const bool vec = ((size_t)src % (4 * es) == 0) && ((size_t)dst % (4 * ed) == 0) && src_ld % 4 == 0 && dst_ld % 4 == 0 &&
-                     ((long)R * src_ld) % 4 == 0 && ((long)C * dst_ld) % 4 == 0;
-    if (vec) {
-        dim3 grid(mu_cdiv(C, 64), mu_cdiv(R_pad, 64), batch), block(256);
-        if (src_dtype == MU_F32 && dst_dtype == MU_F32)
-            transpose_vec_kernel<float, float><<<grid, block, 0, st>>>((const float*)src, src_ld, (float*)dst, dst_ld, R, C, R_pad);
-        else if (src_dtype == MU_F32 && dst_dtype == MU_F16)
-            transpose_vec_kernel<float, h16><<<grid, block, 0, st>>>((const float*)src, src_ld, (h16*)dst, dst_ld, R, C, R_pad);
-        else if (src_dtype == MU_F16 && dst_dtype == MU_F32)
-            transpose_vec_kernel<h16, float><<<grid, block, 0, st>>>((const h16*)src, src_ld, (float*)dst, dst_ld, R, C, R_pad);
-        else if (src_dtype == MU_F16 && dst_dtype == MU_F16)
-            transpose_vec_kernel<h16, h16><<<grid, block, 0, st>>>((const h16*)src, src_ld, (h16*)dst, dst_ld, R, C, R_pad);
-        else
-            return MU_ERR_ARG;
+    return with_storage2(src_dtype, dst_dtype, [&](auto stag, auto dtag) -> int {
+        using TS = decltype(stag);
+        using TD = decltype(dtag);
+        const bool vec = ((size_t)src % (4 * sizeof(TS)) == 0) && ((size_t)dst % (4 * sizeof(TD)) == 0) && src_ld % 4 == 0 && dst_ld % 4 == 0 &&
+                         ((long)R * src_ld) % 4 == 0 && ((long)C * dst_ld) % 4 == 0;
+        const dim3 grid(mu_cdiv(C, 64), mu_cdiv(R_pad, 64), batch);
+        if (vec) transpose_vec_kernel<TS, TD><<<grid, 256, 0, st>>>((const TS*)src, src_ld, (TD*)dst, dst_ld, R, C, R_pad);
+        else transpose_kernel<TS, TD><<<grid, 256, 0, st>>>((const TS*)src, src_ld, (TD*)dst, dst_ld, R, C, R_pad);
         MU_CHECK_LAUNCH();
         return MU_OK;
-    }
-    dim3 grid(mu_cdiv(C, 64), mu_cdiv(R_pad, 64), batch), block(256);
-    if (src_dtype == MU_F32 && dst_dtype == MU_F32)
-        transpose_kernel<float, float><<<grid, block, 0, st>>>((const float*)src, src_ld, (float*)dst, dst_ld, R, C, R_pad);
-    else if (src_dtype == MU_F32 && dst_dtype == MU_F16)
-        transpose_kernel<float, h16><<<grid, block, 0, st>>>((const float*)src, src_ld, (h16*)dst, dst_ld, R, C, R_pad);
-    else if (src_dtype == MU_F16 && dst_dtype == MU_F32)
-        transpose_kernel<h16, float><<<grid, block, 0, st>>>((const h16*)src, src_ld, (float*)dst, dst_ld, R, C, R_pad);
-    else if (src_dtype == MU_F16 && dst_dtype == MU_F16)
-        transpose_kernel<h16, h16><<<grid, block, 0, st>>>((const h16*)src, src_ld, (h16*)dst, dst_ld, R, C, R_pad);
-    else
-        return MU_ERR_ARG;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    });
 }
 
 extern "C" int mu_transpose(const void* src, int src_dtype, long src_ld, void* dst, int dst_dtype, long dst_ld,
@@ -179,40 +159,34 @@ __global__ __launch_bounds__(256) void encode_hl_rows_kernel(float* rows, long n
         __syncthreads();
     }
 }
-static inline int enc_grid(long n16) { long g = (n16 + 1023) / 1024; return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g)); }
 
 extern "C" int mu_prep_weight(const float* w_oihw, void* dst, int dtype, int O, int I, int taps, int rows_pad,
                               int cols_pad, int mode, void* stream) {
     if (!w_oihw || !dst || O <= 0 || I <= 0 || (taps != 1 && taps != 9)) return MU_ERR_ARG;
     if (mode < 0 || mode > 2) return MU_ERR_ARG;
     if (mode != 1 ? (rows_pad < O || cols_pad < I) : (rows_pad < I || cols_pad < O)) return MU_ERR_ARG;
-    long n = (long)taps * rows_pad * cols_pad * (mode == 2 ? 2 : 1);
-    int grid = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+    const bool enc = dtype == MU_F32X;                       // the fp32 layout first, then encoded in place
+    const long n1 = (long)taps * rows_pad * cols_pad, n = n1 * (mode == 2 ? 2 : 1);      // one block, all of them
+    // the data-gradient block's rows run over the layer's OUTPUT channels: rows_pad long in mode 2, cols_pad (as the caller named the
+    // padded output count) in mode 1
+    const int len = mode == 2 ? rows_pad : cols_pad;
+    if (enc && (rows_pad % 4 || cols_pad % 4)) return MU_ERR_SHAPE;
+    if (enc && taps != 1 && mode != 0 && len > 8192) return MU_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MU_F32 || dtype == MU_F32X)
-        prep_weight_kernel<float><<<grid, 256, 0, st>>>(w_oihw, (float*)dst, O, I, taps, rows_pad, cols_pad, mode);
-    else if (dtype == MU_F16)
-        prep_weight_kernel<h16><<<grid, 256, 0, st>>>(w_oihw, (h16*)dst, O, I, taps, rows_pad, cols_pad, mode);
-    else
-        return MU_ERR_ARG;
-    if (dtype == MU_F32X) {
-        if (rows_pad % 4 || cols_pad % 4) return MU_ERR_SHAPE;
-        const long n1 = (long)taps * rows_pad * cols_pad;    // one block
+    const int rc = with_storage(enc ? MU_F32 : dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        prep_weight_kernel<T><<<mu_grid(n, 256, 2048), 256, 0, st>>>(w_oihw, (T*)dst, O, I, taps, rows_pad, cols_pad, mode);
+        return MU_OK;
+    });
+    if (rc) return rc;
+    if (enc) {
         const float sh = (float)(1 << MU_XH_WSHIFT);
         float* d = (float*)dst;
         if (taps == 1) {
-            split_encode_kernel<<<enc_grid(n / 4), 256, 0, st>>>((const f32x4*)d, (uint4*)d, n / 4);
+            split_encode_kernel<<<mu_grid(n / 4, 1024, 8192), 256, 0, st>>>((const f32x4*)d, (uint4*)d, n / 4);
         } else {
-            if (mode != 1) split_encode_h4_kernel<<<enc_grid(n1 / 4), 256, 0, st>>>((const f32x4*)d, (uint4*)d, n1 / 4, sh);
-            if (mode != 0) {
-                // the data-gradient block's rows run over the layer's OUTPUT channels: rows_pad long in mode 2, cols_pad (as the caller
-                // named the padded output count) in mode 1
-                float* d1 = mode == 2 ? d + n1 : d;
-                const int len = mode == 2 ? rows_pad : cols_pad;
-                const long nrows = n1 / len;
-                if (len > 8192) return MU_ERR_SHAPE;
-                encode_hl_rows_kernel<<<(int)(nrows < 4096 ? nrows : 4096), 256, 0, st>>>(d1, nrows, len, sh);
-            }
+            if (mode != 1) split_encode_h4_kernel<<<mu_grid(n1 / 4, 1024, 8192), 256, 0, st>>>((const f32x4*)d, (uint4*)d, n1 / 4, sh);
+            if (mode != 0) encode_hl_rows_kernel<<<mu_grid(n1 / len, 1, 4096), 256, 0, st>>>(mode == 2 ? d + n1 : d, n1 / len, len, sh);
         }
     }
     MU_CHECK_LAUNCH();
@@ -297,7 +271,7 @@ __global__ __launch_bounds__(256) void prep_weights_multi_kernel(const long* __r
 
 extern "C" int mu_prep_weights_multi(const void* jobs, int njobs, long ntiles, void* dst_base, int dtype, void* stream) {
     if (!jobs || !dst_base || njobs <= 0 || njobs > MU_PREP_MAX_JOBS || ntiles <= 0) return MU_ERR_ARG;
-    const int grid = (int)(ntiles < 4096 ? ntiles : 4096);
+    const int grid = mu_grid(ntiles, 1, 4096);
     hipStream_t st = (hipStream_t)stream;
     if (dtype == MU_F32) prep_weights_multi_kernel<float><<<grid, 256, 0, st>>>((const long*)jobs, njobs, ntiles, (float*)dst_base);
     else if (dtype == MU_F32X) prep_weights_multi_kernel<float, true><<<grid, 256, 0, st>>>((const long*)jobs, njobs, ntiles, (float*)dst_base);
@@ -314,15 +288,14 @@ __global__ void cast_kernel(const TS* __restrict__ s, TD* __restrict__ d, long n
 }
 extern "C" int mu_cast(const void* src, int src_dtype, void* dst, int dst_dtype, long n, void* stream) {
     if (!src || !dst || n <= 0) return MU_ERR_ARG;
-    int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
     hipStream_t st = (hipStream_t)stream;
-    if (src_dtype == MU_F32 && dst_dtype == MU_F16) cast_kernel<float, h16><<<grid, 256, 0, st>>>((const float*)src, (h16*)dst, n);
-    else if (src_dtype == MU_F16 && dst_dtype == MU_F32) cast_kernel<h16, float><<<grid, 256, 0, st>>>((const h16*)src, (float*)dst, n);
-    else if (src_dtype == MU_F32 && dst_dtype == MU_F32) cast_kernel<float, float><<<grid, 256, 0, st>>>((const float*)src, (float*)dst, n);
-    else if (src_dtype == MU_F16 && dst_dtype == MU_F16) cast_kernel<h16, h16><<<grid, 256, 0, st>>>((const h16*)src, (h16*)dst, n);
-    else return MU_ERR_ARG;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    return with_storage2(src_dtype, dst_dtype, [&](auto stag, auto dtag) -> int {
+        using TS = decltype(stag);
+        using TD = decltype(dtag);
+        cast_kernel<TS, TD><<<mu_grid(n, 256, 4096), 256, 0, st>>>((const TS*)src, (TD*)dst, n);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -374,14 +347,14 @@ __global__ __launch_bounds__(256) void split_encode_h4x_kernel(const f32x4* __re
 extern "C" int mu_split_encode_h4x(const void* src, void* dst, void* dst16, long n_elems, void* stream) {
     if (!src || !dst || !dst16 || src == dst || n_elems <= 0 || n_elems % 4) return MU_ERR_ARG;
     const long n16 = n_elems / 4;
-    split_encode_h4x_kernel<<<enc_grid(n16), 256, 0, (hipStream_t)stream>>>((const f32x4*)src, (uint4*)dst, (uint2*)dst16, n16);
+    split_encode_h4x_kernel<<<mu_grid(n16, 1024, 8192), 256, 0, (hipStream_t)stream>>>((const f32x4*)src, (uint4*)dst, (uint2*)dst16, n16);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
 extern "C" int mu_split_encode_h4(const void* src, void* dst, long n_elems, void* stream) {
     if (!src || !dst || n_elems <= 0 || n_elems % 4) return MU_ERR_ARG;
     const long n16 = n_elems / 4;
-    split_encode_h4_kernel<<<enc_grid(n16), 256, 0, (hipStream_t)stream>>>((const f32x4*)src, (uint4*)dst, n16, 1.0f);
+    split_encode_h4_kernel<<<mu_grid(n16, 1024, 8192), 256, 0, (hipStream_t)stream>>>((const f32x4*)src, (uint4*)dst, n16, 1.0f);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
@@ -429,11 +402,10 @@ extern "C" int mu_dy_encode_h(const void* dy, void* dy_h, float* dy_scale, long 
     if (!dy || !dy_h || !dy_scale || !workspace || n_elems <= 0 || n_elems % 4 || dy == dy_h) return MU_ERR_ARG;
     if (ws_bytes < mu_dy_encode_h_workspace_bytes()) return MU_ERR_WORKSPACE;
     const long n16 = n_elems / 4;
-    long g = (n16 + 1023) / 1024;
-    const int nb = (int)(g < 1 ? 1 : (g > MU_DYH_MAXBLK ? MU_DYH_MAXBLK : g));
+    const int nb = mu_grid(n16, 1024, MU_DYH_MAXBLK);
     hipStream_t st = (hipStream_t)stream;
     dyh_max_kernel<<<nb, 256, 0, st>>>((const f32x4*)dy, n16, (float*)workspace);
-    dyh_convert_kernel<<<enc_grid(n16), 256, 0, st>>>((const f32x4*)dy, n16, (const float*)workspace, nb, (h16x4*)dy_h, dy_scale);
+    dyh_convert_kernel<<<mu_grid(n16, 1024, 8192), 256, 0, st>>>((const f32x4*)dy, n16, (const float*)workspace, nb, (h16x4*)dy_h, dy_scale);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
@@ -441,9 +413,7 @@ extern "C" int mu_dy_encode_h(const void* dy, void* dy_h, float* dy_scale, long 
 extern "C" int mu_split_encode(const void* src, void* dst, long n_elems, void* stream) {
     if (!src || !dst || n_elems <= 0 || n_elems % 4) return MU_ERR_ARG;
     const long n16 = n_elems / 4;
-    long g = (n16 + 1023) / 1024;
-    g = g < 1 ? 1 : (g > 8192 ? 8192 : g);
-    split_encode_kernel<<<(int)g, 256, 0, (hipStream_t)stream>>>((const f32x4*)src, (uint4*)dst, n16);
+    split_encode_kernel<<<mu_grid(n16, 1024, 8192), 256, 0, (hipStream_t)stream>>>((const f32x4*)src, (uint4*)dst, n16);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
@@ -520,11 +490,6 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ 
     }
 }
 
-static inline int ew_grid(long total) {
-    long g = (total + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
-}
-
 // nn.MaxPool2d(2) floors odd sizes (ade_semantic.py:216): the last row / column of an odd H / W belongs to no window, so its
 // gradient is zero (plus dx_add where the tensor has a second consumer).  One thread per 16-byte vector of the uncovered pixels.
 template <typename T>
@@ -550,15 +515,13 @@ __global__ __launch_bounds__(256) void maxpool_tail_kernel(const T* __restrict__
 extern "C" int mu_maxpool2_fwd(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream) {
     if (!x || !y || B <= 0 || H < 2 || W < 2 || C % 8) return MU_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MU_F32) {
-        long total = (long)B * (H / 2) * (W / 2) * (C / 4);
-        maxpool_fwd_kernel<float><<<ew_grid(total), 256, 0, st>>>((const float*)x, (float*)y, B, H, W, C);
-    } else if (dtype == MU_F16) {
-        long total = (long)B * (H / 2) * (W / 2) * (C / 8);
-        maxpool_fwd_kernel<h16><<<ew_grid(total), 256, 0, st>>>((const h16*)x, (h16*)y, B, H, W, C);
-    } else return MU_ERR_ARG;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        const long total = (long)B * (H / 2) * (W / 2) * (C / Vec16<T>::N);
+        maxpool_fwd_kernel<T><<<mu_grid(total, 256, 8192), 256, 0, st>>>((const T*)x, (T*)y, B, H, W, C);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 extern "C" int mu_maxpool2_bwd_acc(const void* x, const void* dy, const void* dy2, const void* dx_add, void* dx, int B, int H, int W, int C,
@@ -566,19 +529,15 @@ extern "C" int mu_maxpool2_bwd_acc(const void* x, const void* dy, const void* dy
     if (!x || !dy || !dx || B <= 0 || H < 2 || W < 2 || C % 8) return MU_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     const long tail = (long)B * ((H & 1) * W + (H & ~1) * (W & 1));
-    if (dtype == MU_F32) {
-        long total = (long)B * (H / 2) * (W / 2) * (C / 4);
-        maxpool_bwd_kernel<float><<<ew_grid(total), 256, 0, st>>>((const float*)x, (const float*)dy, (const float*)dy2, (const float*)dx_add,
-                                                                  (float*)dx, B, H, W, C);
-        if (tail) maxpool_tail_kernel<float><<<ew_grid(tail * (C / 4)), 256, 0, st>>>((const float*)dx_add, (float*)dx, B, H, W, C);
-    } else if (dtype == MU_F16) {
-        long total = (long)B * (H / 2) * (W / 2) * (C / 8);
-        maxpool_bwd_kernel<h16><<<ew_grid(total), 256, 0, st>>>((const h16*)x, (const h16*)dy, (const h16*)dy2, (const h16*)dx_add, (h16*)dx,
-                                                                B, H, W, C);
-        if (tail) maxpool_tail_kernel<h16><<<ew_grid(tail * (C / 8)), 256, 0, st>>>((const h16*)dx_add, (h16*)dx, B, H, W, C);
-    } else return MU_ERR_ARG;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        const int cv = C / Vec16<T>::N;
+        const long total = (long)B * (H / 2) * (W / 2) * cv;
+        maxpool_bwd_kernel<T><<<mu_grid(total, 256, 8192), 256, 0, st>>>((const T*)x, (const T*)dy, (const T*)dy2, (const T*)dx_add, (T*)dx, B, H, W, C);
+        if (tail) maxpool_tail_kernel<T><<<mu_grid(tail * cv, 256, 8192), 256, 0, st>>>((const T*)dx_add, (T*)dx, B, H, W, C);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 extern "C" int mu_maxpool2_bwd(const void* x, const void* dy, void* dx, int B, int H, int W, int C, int dtype, void* stream) {
@@ -939,16 +898,14 @@ extern "C" int mu_upcat_compact_fwd(const void* x, const void* skip, void* y, in
     if (!x || !skip || !y || B <= 0 || h <= 0 || w <= 0) return MU_ERR_ARG;
     if (Cx_valid <= 0 || Cs_valid <= 0 || Cx_valid > Cx_ld || Cs_valid > Cs_ld || Cx_valid + Cs_valid > Ct_ld) return MU_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-    long total = (long)B * 4 * h * w * Ct_ld;
-    if (dtype == MU_F32)
-        upcat_compact_fwd_kernel<float><<<ew_grid(total), 256, 0, st>>>((const float*)x, (const float*)skip, (float*)y, B, h, w, Cx_ld,
-                                                                        Cx_valid, Cs_ld, Cs_valid, Ct_ld);
-    else if (dtype == MU_F16)
-        upcat_compact_fwd_kernel<h16><<<ew_grid(total), 256, 0, st>>>((const h16*)x, (const h16*)skip, (h16*)y, B, h, w, Cx_ld, Cx_valid,
-                                                                      Cs_ld, Cs_valid, Ct_ld);
-    else return MU_ERR_ARG;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    const long total = (long)B * 4 * h * w * Ct_ld;
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        upcat_compact_fwd_kernel<T><<<mu_grid(total, 256, 8192), 256, 0, st>>>((const T*)x, (const T*)skip, (T*)y, B, h, w, Cx_ld, Cx_valid, Cs_ld,
+                                                                               Cs_valid, Ct_ld);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 extern "C" int mu_upcat_compact_bwd(const void* dy, void* dx, void* dskip, int B, int h, int w, int Cx_ld, int Cx_valid, int Cs_ld,
@@ -956,53 +913,50 @@ extern "C" int mu_upcat_compact_bwd(const void* dy, void* dx, void* dskip, int B
     if (!dy || !dx || !dskip || B <= 0 || h <= 0 || w <= 0) return MU_ERR_ARG;
     if (Cx_valid <= 0 || Cs_valid <= 0 || Cx_valid > Cx_ld || Cs_valid > Cs_ld || Cx_valid + Cs_valid > Ct_ld) return MU_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-    long total = (long)B * 4 * h * w * Cs_ld + (long)B * h * w * Cx_ld;
-    if (dtype == MU_F32)
-        upcat_compact_bwd_kernel<float><<<ew_grid(total), 256, 0, st>>>((const float*)dy, (float*)dx, (float*)dskip, B, h, w, Cx_ld,
-                                                                        Cx_valid, Cs_ld, Cs_valid, Ct_ld);
-    else if (dtype == MU_F16)
-        upcat_compact_bwd_kernel<h16><<<ew_grid(total), 256, 0, st>>>((const h16*)dy, (h16*)dx, (h16*)dskip, B, h, w, Cx_ld, Cx_valid,
-                                                                      Cs_ld, Cs_valid, Ct_ld);
-    else return MU_ERR_ARG;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    const long total = (long)B * 4 * h * w * Cs_ld + (long)B * h * w * Cx_ld;
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        upcat_compact_bwd_kernel<T><<<mu_grid(total, 256, 8192), 256, 0, st>>>((const T*)dy, (T*)dx, (T*)dskip, B, h, w, Cx_ld, Cx_valid, Cs_ld,
+                                                                               Cs_valid, Ct_ld);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 extern "C" int mu_upcat_fwd(const void* x, const void* skip, void* y, int B, int h, int w, int Cx, int Cs, int dtype, void* stream) {
     if (!x || !skip || !y || B <= 0 || h <= 0 || w <= 0 || Cx % 8 || Cs % 8) return MU_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MU_F32) {
-        long total = (long)B * 4 * h * w * ((Cx + Cs) / 4);
-        upcat_fwd_kernel<float><<<ew_grid(total), 256, 0, st>>>((const float*)x, (const float*)skip, (float*)y, B, h, w, Cx, Cs);
-    } else if (dtype == MU_F16) {
-        long total = (long)B * 4 * h * w * ((Cx + Cs) / 8);
-        const int cv = (Cx + Cs) / 8;
-        if (cv <= 256 && 256 % cv == 0 && (long)B * 2 * h < (1 << 30))
-            upcat_fwd_rows_kernel<h16, 4><<<B * 2 * h < 16384 ? B * 2 * h : 16384, 256, 0, st>>>((const h16*)x, (const h16*)skip, (h16*)y, B, h, w, Cx, Cs);
-        else
-            upcat_fwd_kernel<h16><<<ew_grid(total), 256, 0, st>>>((const h16*)x, (const h16*)skip, (h16*)y, B, h, w, Cx, Cs);
-    } else return MU_ERR_ARG;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        const int cv = (Cx + Cs) / Vec16<T>::N;
+        bool rows = false;                                     // a block per output row: fp16 only
+        if constexpr (std::is_same_v<T, h16>) {
+            rows = cv <= 256 && 256 % cv == 0 && (long)B * 2 * h < (1 << 30);
+            if (rows) upcat_fwd_rows_kernel<h16, 4><<<B * 2 * h < 16384 ? B * 2 * h : 16384, 256, 0, st>>>((const h16*)x, (const h16*)skip, (h16*)y, B, h, w, Cx, Cs);
+        }
+        if (!rows) upcat_fwd_kernel<T><<<mu_grid((long)B * 4 * h * w * cv, 256, 8192), 256, 0, st>>>((const T*)x, (const T*)skip, (T*)y, B, h, w, Cx, Cs);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 extern "C" int mu_upcat_bwd_acc(const void* dy, const void* dy2, void* dx, void* dskip, int B, int h, int w, int Cx, int Cs, int dtype,
                                 void* stream) {
     if (!dy || !dx || !dskip || B <= 0 || h <= 0 || w <= 0 || Cx % 8 || Cs % 8) return MU_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MU_F32) {
-        long total = (long)B * 4 * h * w * (Cs / 4) + (long)B * h * w * (Cx / 4);
-        upcat_bwd_kernel<float><<<ew_grid(total), 256, 0, st>>>((const float*)dy, (const float*)dy2, (float*)dx, (float*)dskip, B, h, w, Cx, Cs);
-    } else if (dtype == MU_F16) {
-        long total = (long)B * 4 * h * w * (Cs / 8) + (long)B * h * w * (Cx / 8);
-        const int cvs = Cs / 8, cvx = Cx / 8;
-        if (cvs <= 256 && 256 % cvs == 0 && cvx <= 256 && 256 % cvx == 0 && (long)B * 3 * h < (1 << 30))
-            upcat_bwd_rows_kernel<h16><<<B * 3 * h, 256, 0, st>>>((const h16*)dy, (const h16*)dy2, (h16*)dx, (h16*)dskip, B, h, w, Cx, Cs);
-        else
-            upcat_bwd_kernel<h16><<<ew_grid(total), 256, 0, st>>>((const h16*)dy, (const h16*)dy2, (h16*)dx, (h16*)dskip, B, h, w, Cx, Cs);
-    } else return MU_ERR_ARG;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        const int cvs = Cs / Vec16<T>::N, cvx = Cx / Vec16<T>::N;
+        bool rows = false;                                     // a block per row of dskip and of dx: fp16 only
+        if constexpr (std::is_same_v<T, h16>) {
+            rows = cvs <= 256 && 256 % cvs == 0 && cvx <= 256 && 256 % cvx == 0 && (long)B * 3 * h < (1 << 30);
+            if (rows) upcat_bwd_rows_kernel<h16><<<B * 3 * h, 256, 0, st>>>((const h16*)dy, (const h16*)dy2, (h16*)dx, (h16*)dskip, B, h, w, Cx, Cs);
+        }
+        const long total = (long)B * 4 * h * w * cvs + (long)B * h * w * cvx;
+        if (!rows) upcat_bwd_kernel<T><<<mu_grid(total, 256, 8192), 256, 0, st>>>((const T*)dy, (const T*)dy2, (T*)dx, (T*)dskip, B, h, w, Cx, Cs);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 extern "C" int mu_upcat_bwd(const void* dy, void* dx, void* dskip, int B, int h, int w, int Cx, int Cs, int dtype, void* stream) {
@@ -1052,27 +1006,23 @@ __global__ __launch_bounds__(256) void dropout_kernel(const T* __restrict__ x, T
 }
 
 extern "C" int mu_dropout_step(const void* x, void* y, long n, float p, unsigned long long seed, const unsigned long long* seed_step,
-                               const unsigned char* mask, unsigned char* mask_out, int dtype, void* stream);
+                               const unsigned char* mask, unsigned char* mask_out, int dtype, void* stream) {
+    if (!x || !y || n <= 0 || p < 0.f || p >= 1.f) return MU_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const float scale = 1.0f / (1.0f - p);
+    return with_storage(dtype, [&](auto tag) -> int {         // an unknown dtype is refused before a partial vector is
+        using T = decltype(tag);
+        constexpr int N = Vec16<T>::N;
+        if (n % N) return MU_ERR_SHAPE;
+        dropout_kernel<T><<<mu_grid(n / N, 256, 8192), 256, 0, st>>>((const T*)x, (T*)y, n / N, p, scale, seed, mask, mask_out, seed_step);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
+}
 
 extern "C" int mu_dropout(const void* x, void* y, long n, float p, unsigned long long seed, const unsigned char* mask,
                           unsigned char* mask_out, int dtype, void* stream) {
     return mu_dropout_step(x, y, n, p, seed, nullptr, mask, mask_out, dtype, stream);
-}
-
-extern "C" int mu_dropout_step(const void* x, void* y, long n, float p, unsigned long long seed, const unsigned long long* seed_step,
-                               const unsigned char* mask, unsigned char* mask_out, int dtype, void* stream) {
-    if (!x || !y || n <= 0 || p < 0.f || p >= 1.f) return MU_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    float scale = 1.0f / (1.0f - p);
-    if (dtype == MU_F32) {
-        if (n % 4) return MU_ERR_SHAPE;
-        dropout_kernel<float><<<ew_grid(n / 4), 256, 0, st>>>((const float*)x, (float*)y, n / 4, p, scale, seed, mask, mask_out, seed_step);
-    } else if (dtype == MU_F16) {
-        if (n % 8) return MU_ERR_SHAPE;
-        dropout_kernel<h16><<<ew_grid(n / 8), 256, 0, st>>>((const h16*)x, (h16*)y, n / 8, p, scale, seed, mask, mask_out, seed_step);
-    } else return MU_ERR_ARG;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1092,11 +1042,14 @@ __global__ __launch_bounds__(256) void add_kernel(const T* __restrict__ a, const
 extern "C" int mu_add(const void* a, const void* b, void* out, long n, int dtype, void* stream) {
     if (!a || !b || !out || n <= 0) return MU_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MU_F32) { if (n % 4) return MU_ERR_SHAPE; add_kernel<float><<<ew_grid(n / 4), 256, 0, st>>>((const float*)a, (const float*)b, (float*)out, n / 4); }
-    else if (dtype == MU_F16) { if (n % 8) return MU_ERR_SHAPE; add_kernel<h16><<<ew_grid(n / 8), 256, 0, st>>>((const h16*)a, (const h16*)b, (h16*)out, n / 8); }
-    else return MU_ERR_ARG;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    return with_storage(dtype, [&](auto tag) -> int {         // an unknown dtype is refused before a partial vector is
+        using T = decltype(tag);
+        constexpr int N = Vec16<T>::N;
+        if (n % N) return MU_ERR_SHAPE;
+        add_kernel<T><<<mu_grid(n / N, 256, 8192), 256, 0, st>>>((const T*)a, (const T*)b, (T*)out, n / N);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1119,11 +1072,12 @@ __global__ __launch_bounds__(256) void u8_to_nhwc_kernel(const uint8_t* __restri
 extern "C" int mu_u8_to_nhwc(const unsigned char* src, void* dst, long npix, int C, int Cp, int dtype, void* stream) {
     if (!src || !dst || npix <= 0 || C <= 0 || Cp < C || Cp % 8) return MU_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MU_F32) u8_to_nhwc_kernel<float><<<ew_grid(npix * (Cp / 4)), 256, 0, st>>>(src, (float*)dst, npix, C, Cp);
-    else if (dtype == MU_F16) u8_to_nhwc_kernel<h16><<<ew_grid(npix * (Cp / 8)), 256, 0, st>>>(src, (h16*)dst, npix, C, Cp);
-    else return MU_ERR_ARG;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        u8_to_nhwc_kernel<T><<<mu_grid(npix * (Cp / Vec16<T>::N), 256, 8192), 256, 0, st>>>(src, (T*)dst, npix, C, Cp);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1211,13 +1165,13 @@ extern "C" int mu_prep_qkv(const float* wq, const float* wk, const float* wv, co
                            float* bias, int dtype, int C, void* stream) {
     if (!wq || !wk || !wv || !bq || !bk || !bv || !dst || !bias || C <= 0 || C % 32) return MU_ERR_ARG;
     const long n = 6L * C * C + 3 * C;
-    const int grid = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MU_F32) prep_qkv_kernel<float><<<grid, 256, 0, st>>>(wq, wk, wv, bq, bk, bv, (float*)dst, bias, C);
-    else if (dtype == MU_F16) prep_qkv_kernel<h16><<<grid, 256, 0, st>>>(wq, wk, wv, bq, bk, bv, (h16*)dst, bias, C);
-    else return MU_ERR_ARG;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        prep_qkv_kernel<T><<<mu_grid(n, 256, 2048), 256, 0, st>>>(wq, wk, wv, bq, bk, bv, (T*)dst, bias, C);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1296,12 +1250,13 @@ extern "C" int mu_resize_u8_nhwc(const unsigned char* src, int B, int Hs, int Ws
     // exactly what cv::resize derives from dsize: inv_scale = dsize / ssize, scale = 1 / inv_scale (doubles)
     const double scale_x = 1.0 / ((double)Wd / (double)Ws), scale_y = 1.0 / ((double)Hd / (double)Hs);
     hipStream_t st = (hipStream_t)stream;
-    const long total = (long)B * Hd * Wd;
-    if (dtype == MU_F32) resize_linear_u8_kernel<float><<<ew_grid(total), 256, 0, st>>>(src, B, Hs, Ws, C, swap_rb, scale_x, scale_y, (float*)dst, u8_out, Hd, Wd, Cp);
-    else if (dtype == MU_F16) resize_linear_u8_kernel<h16><<<ew_grid(total), 256, 0, st>>>(src, B, Hs, Ws, C, swap_rb, scale_x, scale_y, (h16*)dst, u8_out, Hd, Wd, Cp);
-    else return MU_ERR_ARG;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    const int grid = mu_grid((long)B * Hd * Wd, 256, 8192);
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        resize_linear_u8_kernel<T><<<grid, 256, 0, st>>>(src, B, Hs, Ws, C, swap_rb, scale_x, scale_y, (T*)dst, u8_out, Hd, Wd, Cp);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 // label map: uint8 [B][Hs][Ws] -> int64 [B][Hd][Wd], cv2.INTER_NEAREST + torch.from_numpy(mask).long() (ade_semantic.py:73,78)
@@ -1320,7 +1275,7 @@ __global__ __launch_bounds__(256) void resize_nearest_u8_kernel(const uint8_t* _
 extern "C" int mu_resize_nearest_u8(const unsigned char* src, int B, int Hs, int Ws, long* dst, int Hd, int Wd, void* stream) {
     if (!src || !dst || B <= 0 || Hs <= 0 || Ws <= 0 || Hd <= 0 || Wd <= 0) return MU_ERR_ARG;
     const double ifx = 1.0 / ((double)Wd / (double)Ws), ify = 1.0 / ((double)Hd / (double)Hs);
-    resize_nearest_u8_kernel<<<ew_grid((long)B * Hd * Wd), 256, 0, (hipStream_t)stream>>>(src, B, Hs, Ws, ifx, ify, dst, Hd, Wd);
+    resize_nearest_u8_kernel<<<mu_grid((long)B * Hd * Wd, 256, 8192), 256, 0, (hipStream_t)stream>>>(src, B, Hs, Ws, ifx, ify, dst, Hd, Wd);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }

@@ -177,30 +177,27 @@ extern "C" int mu_ce_fwd(const void* logits, const long* labels, long M, int Cp,
     if (!logits || !labels || !lse || !loss || !count || !workspace || M <= 0 || C <= 0 || Cp < C || Cp % 8) return MU_ERR_ARG;
     if (ws_bytes < mu_ce_workspace_bytes()) return MU_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    int nblk = (int)((M + 31) / 32 < CE_MAXBLK ? (M + 31) / 32 : CE_MAXBLK);
-    if (dtype == MU_F16) ce_fwd_kernel<h16><<<nblk, 256, 0, st>>>((const h16*)logits, labels, M, Cp, C, ignore_index, lse, (double*)workspace);
-    else if (dtype == MU_F32) ce_fwd_kernel<float><<<nblk, 256, 0, st>>>((const float*)logits, labels, M, Cp, C, ignore_index, lse, (double*)workspace);
-    else return MU_ERR_ARG;
-    ce_final_kernel<<<1, 64, 0, st>>>((const double*)workspace, nblk, loss, count);
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    const int nblk = mu_grid(M, 32, CE_MAXBLK);
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        ce_fwd_kernel<T><<<nblk, 256, 0, st>>>((const T*)logits, labels, M, Cp, C, ignore_index, lse, (double*)workspace);
+        ce_final_kernel<<<1, 64, 0, st>>>((const double*)workspace, nblk, loss, count);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 extern "C" int mu_ce_bwd(const void* logits, const long* labels, const float* lse, const float* count, const float* grad_out,
                          float grad_scale, long M, int Cp, int C, long ignore_index, void* dlogits, int dtype, void* stream) {
     if (!logits || !labels || !lse || !count || !grad_out || !dlogits || M <= 0 || C <= 0 || Cp < C || Cp % 8) return MU_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MU_F16) {
-        long total = M * (Cp / 8);
-        int g = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-        ce_bwd_kernel<h16><<<g, 256, 0, st>>>((const h16*)logits, labels, lse, count, grad_out, grad_scale, M, Cp, C, ignore_index, (h16*)dlogits);
-    } else if (dtype == MU_F32) {
-        long total = M * (Cp / 4);
-        int g = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-        ce_bwd_kernel<float><<<g, 256, 0, st>>>((const float*)logits, labels, lse, count, grad_out, grad_scale, M, Cp, C, ignore_index, (float*)dlogits);
-    } else return MU_ERR_ARG;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        const int g = mu_grid(M * (Cp / Vec16<T>::N), 256, 8192);
+        ce_bwd_kernel<T><<<g, 256, 0, st>>>((const T*)logits, labels, lse, count, grad_out, grad_scale, M, Cp, C, ignore_index, (T*)dlogits);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -342,26 +339,21 @@ extern "C" int mu_ce_nchw_fwd(const void* logits, const long* labels, int B, int
     if (!logits || !labels || !lse || !loss || !count || !workspace || B <= 0 || C <= 0 || HW <= 0) return MU_ERR_ARG;
     if (ws_bytes < mu_ce_workspace_bytes()) return MU_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const bool v4 = HW % 4 == 0;
-    const long groups = (long)B * (v4 ? HW / 4 : HW);
-    const int nblk = (int)((groups + 255) / 256 < CE_MAXBLK ? (groups + 255) / 256 : CE_MAXBLK);
-    if (dtype == MU_F32) {
-        if (v4) ce_nchw_fwd_t<float, 4>(logits, labels, B, C, HW, ignore_index, lse, (double*)workspace, nblk, st);
-        else ce_nchw_fwd_t<float, 1>(logits, labels, B, C, HW, ignore_index, lse, (double*)workspace, nblk, st);
-    } else if (dtype == MU_F16) {
-        if (v4) ce_nchw_fwd_t<h16, 4>(logits, labels, B, C, HW, ignore_index, lse, (double*)workspace, nblk, st);
-        else ce_nchw_fwd_t<h16, 1>(logits, labels, B, C, HW, ignore_index, lse, (double*)workspace, nblk, st);
-    } else return MU_ERR_ARG;
-    ce_final_kernel<<<1, 64, 0, st>>>((const double*)workspace, nblk, loss, count);
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    const bool v4 = HW % 4 == 0;                              // a lane owns four pixels, or one
+    const int nblk = mu_grid((long)B * (v4 ? HW / 4 : HW), 256, CE_MAXBLK);
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        (v4 ? ce_nchw_fwd_t<T, 4> : ce_nchw_fwd_t<T, 1>)(logits, labels, B, C, HW, ignore_index, lse, (double*)workspace, nblk, st);
+        ce_final_kernel<<<1, 64, 0, st>>>((const double*)workspace, nblk, loss, count);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 template <typename T, int VEC>
 static void ce_nchw_bwd_t(const void* logits, const long* labels, const float* lse, const float* count, const float* gout, float gscale, int B,
                           int C, long HW, long ignore_index, void* dlogits, hipStream_t st) {
-    const long groups = (long)B * (HW / VEC);
-    const int nblk = (int)((groups + 255) / 256 < 4096 ? (groups + 255) / 256 : 4096);
+    const int nblk = mu_grid((long)B * (HW / VEC), 256, 4096);
     ce_nchw_bwd_kernel<T, VEC><<<nblk, 256, 0, st>>>((const T*)logits, labels, lse, count, gout, gscale, B, C, HW, ignore_index, (T*)dlogits);
 }
 
@@ -369,16 +361,12 @@ extern "C" int mu_ce_nchw_bwd(const void* logits, const long* labels, const floa
                               float grad_scale, int B, int C, long HW, long ignore_index, void* dlogits, int dtype, void* stream) {
     if (!logits || !labels || !lse || !count || !grad_out || !dlogits || B <= 0 || C <= 0 || HW <= 0) return MU_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    const bool v4 = HW % 4 == 0;
-    if (dtype == MU_F32) {
-        if (v4) ce_nchw_bwd_t<float, 4>(logits, labels, lse, count, grad_out, grad_scale, B, C, HW, ignore_index, dlogits, st);
-        else ce_nchw_bwd_t<float, 1>(logits, labels, lse, count, grad_out, grad_scale, B, C, HW, ignore_index, dlogits, st);
-    } else if (dtype == MU_F16) {
-        if (v4) ce_nchw_bwd_t<h16, 4>(logits, labels, lse, count, grad_out, grad_scale, B, C, HW, ignore_index, dlogits, st);
-        else ce_nchw_bwd_t<h16, 1>(logits, labels, lse, count, grad_out, grad_scale, B, C, HW, ignore_index, dlogits, st);
-    } else return MU_ERR_ARG;
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        (HW % 4 == 0 ? ce_nchw_bwd_t<T, 4> : ce_nchw_bwd_t<T, 1>)(logits, labels, lse, count, grad_out, grad_scale, B, C, HW, ignore_index, dlogits, st);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -430,14 +418,14 @@ extern "C" int mu_mean_iou(const void* logits, const long* labels, long M, int C
     if (!logits || !labels || !counts || !out || M <= 0 || C <= 0 || C > 4096 || inner <= 0) return MU_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(counts, 0, (size_t)3 * C * sizeof(unsigned int), st) != hipSuccess) return MU_ERR_LAUNCH;
-    int g = (int)((M + 255) / 256 > 2048 ? 2048 : (M + 255) / 256);
-    size_t lds = (size_t)3 * C * sizeof(unsigned int);
-    if (dtype == MU_F16) iou_count_kernel<h16><<<g, 256, lds, st>>>((const h16*)logits, labels, M, C, inner, outer_stride, c_stride, p_stride, counts);
-    else if (dtype == MU_F32) iou_count_kernel<float><<<g, 256, lds, st>>>((const float*)logits, labels, M, C, inner, outer_stride, c_stride, p_stride, counts);
-    else return MU_ERR_ARG;
-    iou_final_kernel<<<1, 64, 0, st>>>(counts, C, smooth, out);
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    const size_t lds = (size_t)3 * C * sizeof(unsigned int);
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        iou_count_kernel<T><<<mu_grid(M, 256, 2048), 256, lds, st>>>((const T*)logits, labels, M, C, inner, outer_stride, c_stride, p_stride, counts);
+        iou_final_kernel<<<1, 64, 0, st>>>(counts, C, smooth, out);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------

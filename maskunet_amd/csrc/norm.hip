@@ -449,14 +449,6 @@ static inline int stat_geom(int C, int N, StatGeom& sg) {
     sg.lds = (size_t)sg.rpi * C * 2 * sizeof(double);
     return MU_OK;
 }
-// storage dispatch: f(T{}) with T the element type behind `dtype`; any other dtype is MU_ERR_ARG (MU_F32X, where an entry point takes
-// it, is that entry point's own case)
-template <typename F>
-static inline int with_storage(int dtype, F&& f) {
-    if (dtype == MU_F32) return f(float{});
-    if (dtype == MU_F16) return f(h16{});
-    return MU_ERR_ARG;
-}
 
 __global__ void colsum_final_kernel(const double* __restrict__ part, int nblk, int C, float* __restrict__ out) {
     const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;

@@ -22,7 +22,7 @@ DTYPES = [pytest.param(F32, id="fp32"), pytest.param(F16, id="fp16")]
 NP = {F32: np.float32, F16: np.float16}
 VEC = {F32: 4, F16: 8}                      # elements of a 16-byte vector
 CODE = {F32: 0, F16: 1}                     # MU_F32 / MU_F16
-GRID_CAP = 8192 * 256                       # vectors one pass of ew_grid covers
+GRID_CAP = 8192 * 256                       # vectors one pass of the 8192-block grid covers
 
 
 def _note(what, err, bound):
@@ -85,6 +85,32 @@ def _raw_status(name, *args):
 
 
 MU_ERR_SHAPE = -2
+MU_F32X, BAD_DTYPE = 2, 99                  # fp32 storage with encoded matrix operands (only the weight preparations take it); no dtype
+
+
+def _refused(code, name, *args, outs):
+    """the entry point returns `code` before it launches anything: every output still holds the sentinel, every band is intact"""
+    from maskunet_amd import _lib
+    with pytest.raises(RuntimeError, match=code):
+        _lib.call(name, *[a.p if isinstance(a, Guarded) else a for a in args], _lib.stream())
+    torch.cuda.synchronize()
+    for a in list(args) + list(outs):
+        if isinstance(a, Guarded):
+            a.check()
+    for o in outs:
+        assert bool((o.t == o.sent).all()), (name, code, o.name)
+
+
+def _dtype_gate(name, args_of, outs, code, bad=(MU_F32X, BAD_DTYPE)):
+    """args_of(c): the arguments with c as the dtype.  Every code of `bad` is MU_ERR_ARG with `outs` untouched; then the valid call on
+    the same buffers (the caller compares the outputs)."""
+    for c in bad:
+        _refused("MU_ERR_ARG", name, *args_of(c), outs=outs)
+    call(name, *args_of(code))
+
+
+def _small_ints(gen, shape, dt):
+    return gen.integers(-3, 4, shape).astype(NP[dt])
 
 
 # ================================================================================================
@@ -501,3 +527,229 @@ def test_cast(src, dst, n):
     out = _out((n,), dst, "dst")
     call("mu_cast", _in(x, src, "src"), CODE[src], out, CODE[dst], n)
     _exact(f"cast {NP[src].__name__} -> {NP[dst].__name__} n={n}", _result(out, (n,)), ref)
+
+
+# ================================================================================================
+# the host layer of every dtype-taking entry point, at its smallest shape: MU_F32X (where the entry point takes no encoded operand) and
+# an unknown dtype are MU_ERR_ARG before anything is launched -- the outputs still hold the sentinel -- and the valid call on the same
+# buffers gives the reference bit for bit.  Small-integer inputs where the kernel accumulates, so that "bit for bit" holds there too.
+# ================================================================================================
+@pytest.mark.parametrize("dt", DTYPES)
+def test_dtype_gate_maxpool(dt):
+    shape, small = (1, 2, 2, 8), (1, 1, 1, 8)
+    gen = np.random.default_rng(501)
+    x, dy, dy2, dx_add = _small_ints(gen, shape, dt), _small_ints(gen, small, dt), _small_ints(gen, small, dt), _small_ints(gen, shape, dt)
+    xg, g1, g2, ga = _in(x, dt, "x"), _in(dy, dt, "dy"), _in(dy2, dt, "dy2"), _in(dx_add, dt, "dx_add")
+    y, dx, dx2 = _out(small, dt, "y"), _out(shape, dt, "dx"), _out(shape, dt, "dx (plain)")
+    _refused("MU_ERR_ARG", "mu_maxpool2_fwd", None, y, 1, 2, 2, 8, BAD_DTYPE, outs=[y])
+    _dtype_gate("mu_maxpool2_fwd", lambda c: (xg, y, 1, 2, 2, 8, c), [y], CODE[dt])
+    _exact("gate maxpool y", _result(y, small), R.maxpool2_fwd(x), signed_zero=False)
+    _dtype_gate("mu_maxpool2_bwd_acc", lambda c: (xg, g1, g2, ga, dx, 1, 2, 2, 8, c), [dx], CODE[dt])
+    _exact("gate maxpool dx+dy2+dx_add", _result(dx, shape), R.maxpool2_bwd(x, dy, dy2, dx_add), signed_zero=False)
+    _dtype_gate("mu_maxpool2_bwd", lambda c: (xg, g1, dx2, 1, 2, 2, 8, c), [dx2], CODE[dt])
+    _exact("gate maxpool dx", _result(dx2, shape), R.maxpool2_bwd(x, dy), signed_zero=False)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_dtype_gate_upcat(dt):
+    """B = 1, h = w = 1, Cx = Cs = 8: the fp16 calls go by rows, the fp32 ones by elements; every weight is 1, so dx is an exact sum"""
+    gen = np.random.default_rng(502)
+    x, skip = _small_ints(gen, (1, 1, 1, 8), dt), _small_ints(gen, (1, 2, 2, 8), dt)
+    dy, dy2 = _small_ints(gen, (1, 2, 2, 16), dt), _small_ints(gen, (1, 2, 2, 16), dt)
+    xg, sg, g1, g2 = _in(x, dt, "x"), _in(skip, dt, "skip"), _in(dy, dt, "dy"), _in(dy2, dt, "dy2")
+    y = _out((1, 2, 2, 16), dt, "y")
+    _dtype_gate("mu_upcat_fwd", lambda c: (xg, sg, y, 1, 1, 1, 8, 8, c), [y], CODE[dt])
+    _exact("gate upcat y", _result(y, (1, 2, 2, 16)), R.upcat_fwd(x, skip))
+    for name, second in (("mu_upcat_bwd_acc", dy2), ("mu_upcat_bwd", None)):
+        dx, dskip = _out((1, 1, 1, 8), dt, "dx"), _out((1, 2, 2, 8), dt, "dskip")
+        grads = (g1, g2) if second is not None else (g1,)
+        _dtype_gate(name, lambda c: (*grads, dx, dskip, 1, 1, 1, 8, 8, c), [dx, dskip], CODE[dt])
+        rskip, ref64, _ = R.upcat_bwd(dy, second, 1, 1, 8, 8)
+        assert (ref64 == ref64.astype(NP[dt])).all()
+        _exact(f"gate {name} dskip", _result(dskip, rskip.shape), rskip)
+        _exact(f"gate {name} dx", _result(dx, ref64.shape), ref64.astype(NP[dt]))
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_dtype_gate_upcat_compact(dt):
+    """3 of 8 channels of x and 5 of 8 of skip into 8; NaN in every pad channel of the inputs"""
+    gen = np.random.default_rng(503)
+    x, skip, dy = _small_ints(gen, (1, 1, 1, 8), dt), _small_ints(gen, (1, 2, 2, 8), dt), _small_ints(gen, (1, 2, 2, 8), dt)
+    x[..., 3:], skip[..., 5:] = np.nan, np.nan
+    y, dx, dskip = _out((1, 2, 2, 8), dt, "y"), _out((1, 1, 1, 8), dt, "dx"), _out((1, 2, 2, 8), dt, "dskip")
+    dims = (1, 1, 1, 8, 3, 8, 5, 8)
+    xg, sg, gg = _in(x, dt, "x"), _in(skip, dt, "skip"), _in(dy, dt, "dy")
+    _dtype_gate("mu_upcat_compact_fwd", lambda c: (xg, sg, y, *dims, c), [y], CODE[dt])
+    _exact("gate compact y", _result(y, (1, 2, 2, 8)), R.upcat_fwd(x, skip, 3, 5, 8))
+    _dtype_gate("mu_upcat_compact_bwd", lambda c: (gg, dx, dskip, *dims, c), [dx, dskip], CODE[dt])
+    rskip, ref64, _ = R.upcat_bwd(dy, None, 1, 1, None, None, 3, 5, 8, 8)
+    assert (ref64 == ref64.astype(NP[dt])).all()
+    _exact("gate compact dskip", _result(dskip, rskip.shape), rskip)
+    _exact("gate compact dx", _result(dx, ref64.shape), ref64.astype(NP[dt]))
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_dtype_gate_dropout_and_add(dt):
+    """one vector each.  An unknown dtype with a partial vector (n = 3) or with a null pointer is MU_ERR_ARG; the partial vector alone
+    is MU_ERR_SHAPE."""
+    n = VEC[dt]
+    gen = np.random.default_rng(504)
+    x, b = _normal(gen, (n,), dt, 3.0), _normal(gen, (n,), dt, 3.0)
+    mask = np.array([1, 0, 1, 1, 0, 1, 0, 0][:n], dtype=np.uint8)
+    xg, bg, mg = _in(x, dt, "x"), _in(b, dt, "b"), _in(mask, torch.uint8, "mask")
+    ref = np.where(mask != 0, x.astype(np.float32) * _scale(0.3), np.float32(0)).astype(NP[dt])
+    for name, extra in (("mu_dropout_step", (None,)), ("mu_dropout", ())):
+        y, mo = _out((n,), dt, "y"), _out((n,), torch.uint8, "mask_out")
+        for c in (MU_F32X, BAD_DTYPE):
+            _refused("MU_ERR_ARG", name, xg, y, 3, 0.3, 1, *extra, mg, mo, c, outs=[y, mo])
+        _refused("MU_ERR_ARG", name, None, y, n, 0.3, 1, *extra, mg, mo, BAD_DTYPE, outs=[y, mo])
+        _refused("MU_ERR_SHAPE", name, xg, y, 3, 0.3, 1, *extra, mg, mo, CODE[dt], outs=[y, mo])
+        _dtype_gate(name, lambda c: (xg, y, n, 0.3, 1, *extra, mg, mo, c), [y, mo], CODE[dt])
+        _exact(f"gate {name} y", _result(y, (n,)), ref)
+        _exact(f"gate {name} mask_out", _result(mo, (n,)), mask)
+    out = _out((n,), dt, "out")
+    for c in (MU_F32X, BAD_DTYPE):
+        _refused("MU_ERR_ARG", "mu_add", xg, bg, out, 3, c, outs=[out])
+    _refused("MU_ERR_ARG", "mu_add", None, bg, out, n, BAD_DTYPE, outs=[out])
+    _refused("MU_ERR_SHAPE", "mu_add", xg, bg, out, 3, CODE[dt], outs=[out])
+    _dtype_gate("mu_add", lambda c: (xg, bg, out, n, c), [out], CODE[dt])
+    _exact("gate add", _result(out, (n,)), _add_ref(x, b))
+
+
+def _unit(u8, dt):
+    """ToTensor of image bytes: byte / 255 by fp32 division, rounded to the dtype"""
+    return (u8.astype(np.float32) / np.float32(255)).astype(NP[dt])
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_dtype_gate_image_inputs(dt):
+    """mu_u8_to_nhwc on one pixel (3 of 8 channels), mu_resize_u8_nhwc 2 x 2 -> 1 x 1 (cv::resize's INTER_AREA shortcut)"""
+    from oracle import cv2_resize_oracle
+    px = np.array([0, 37, 255], dtype=np.uint8)
+    src, dst = _in(px, torch.uint8, "src"), _out((8,), dt, "dst")
+    _dtype_gate("mu_u8_to_nhwc", lambda c: (src, dst, 1, 3, 8, c), [dst], CODE[dt])
+    _exact("gate u8_to_nhwc", _result(dst, (8,)), np.concatenate([_unit(px, dt), np.zeros(5, NP[dt])]))
+    img = np.array([[[10, 20, 30], [40, 50, 60]], [[70, 80, 90], [100, 110, 121]]], dtype=np.uint8)
+    src, dst, u8 = _in(img, torch.uint8, "src"), _out((8,), dt, "dst"), _out((3,), torch.uint8, "u8_out")
+    _dtype_gate("mu_resize_u8_nhwc", lambda c: (src, 1, 2, 2, 3, 0, dst, u8, 1, 1, 8, c), [dst, u8], CODE[dt])
+    want = cv2_resize_oracle.resize_linear_u8(img, (1, 1)).reshape(3)
+    assert want.tolist() == [55, 65, 75]                      # (a + b + c + d + 2) >> 2
+    _exact("gate resize u8_out", _result(u8, (3,)), want)
+    _exact("gate resize dst", _result(dst, (8,)), np.concatenate([_unit(want, dt), np.zeros(5, NP[dt])]))
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_dtype_gate_prep_qkv(dt):
+    C = 32
+    gen = np.random.default_rng(506)
+    ws = [gen.standard_normal((C, C), dtype=np.float32) for _ in range(3)]
+    bs = [gen.standard_normal(C, dtype=np.float32) for _ in range(3)]
+    ins = [_in(a, F32, n) for a, n in zip(ws + bs, ("wq", "wk", "wv", "bq", "bk", "bv"))]
+    dst, bias = _out((6 * C * C,), dt, "dst"), _out((3 * C,), F32, "bias")
+    _dtype_gate("mu_prep_qkv", lambda c: (*ins, dst, bias, c, C), [dst, bias], CODE[dt])
+    w = np.concatenate(ws).astype(NP[dt])                      # [3C, C]: the forward block; its transpose is the data-gradient block
+    _exact("gate prep_qkv dst", _result(dst, (6 * C * C,)), np.concatenate([w.reshape(-1), w.T.reshape(-1)]))
+    _exact("gate prep_qkv bias", _result(bias, (3 * C,)), np.concatenate(bs))
+
+
+PAIRS = [(F32, F32), (F32, F16), (F16, F32), (F16, F16)]
+
+
+@pytest.mark.parametrize("R_,C_", [(1, 4), (3, 5)], ids=["1x4-vector", "3x5-scalar"])
+def test_dtype_gate_transpose_and_cast(R_, C_):
+    """1 x 4 with every pointer and leading dimension a multiple of four elements: the vector kernel; 3 x 5 with src_ld = 5: the scalar
+    one.  All four (source, destination) pairs, and a bad member on either side of a pair."""
+    Rp = (R_ + 3) // 4 * 4 if C_ % 4 == 0 else R_
+    gen = np.random.default_rng(507 + R_)
+    for sdt, ddt in PAIRS:
+        x = _normal(gen, (R_, C_), sdt, 4.0)
+        src = _in(x, sdt, "src")
+        dst = _out((C_, Rp), ddt, "dst")
+        bad = [(b, CODE[ddt]) for b in (MU_F32X, BAD_DTYPE)] + [(CODE[sdt], b) for b in (MU_F32X, BAD_DTYPE)]
+        for s, d in bad:
+            _refused("MU_ERR_ARG", "mu_transpose_pad", src, s, C_, dst, d, Rp, 1, R_, C_, Rp, outs=[dst])
+        call("mu_transpose_pad", src, CODE[sdt], C_, dst, CODE[ddt], Rp, 1, R_, C_, Rp)
+        ref = np.zeros((C_, Rp), dtype=NP[ddt])
+        ref[:, :R_] = x.T.astype(np.float32).astype(NP[ddt])
+        _exact(f"gate transpose_pad {R_}x{C_} {sdt}->{ddt}", _result(dst, (C_, Rp)), ref)
+        if Rp == R_:
+            dst = _out((C_, R_), ddt, "dst")
+            for s, d in bad:
+                _refused("MU_ERR_ARG", "mu_transpose", src, s, C_, dst, d, R_, 1, R_, C_, outs=[dst])
+            call("mu_transpose", src, CODE[sdt], C_, dst, CODE[ddt], R_, 1, R_, C_)
+            _exact(f"gate transpose {R_}x{C_} {sdt}->{ddt}", _result(dst, (C_, R_)), ref)
+        n = R_ * C_
+        out = _out((n,), ddt, "dst")
+        for s, d in bad:
+            _refused("MU_ERR_ARG", "mu_cast", src, s, out, d, n, outs=[out])
+        _refused("MU_ERR_ARG", "mu_cast", None, BAD_DTYPE, out, CODE[ddt], n, outs=[out])
+        call("mu_cast", src, CODE[sdt], out, CODE[ddt], n)
+        _exact(f"gate cast n={n} {sdt}->{ddt}", _result(out, (n,)), x.reshape(-1).astype(np.float32).astype(NP[ddt]))
+
+
+# ================================================================================================
+# mu_prep_weight / mu_prep_weights_multi: OIHW fp32 -> [tap][rows_pad][cols_pad]; these two take MU_F32X (operands encoded in place)
+#   forward        dst[t][o][i]     = w[o][i][t]
+#   data gradient  dst[T-1-t][i][o] = w[o][i][t]
+# MU_F32X, 9 taps: the forward block as 16-byte chunks [4 fp16 hi | 4 fp16 lo] of 64 w, the data-gradient block as rows
+# [rows_pad fp16 lo | rows_pad fp16 hi] of 64 w; hi = fp16(64 w), lo = fp16(64 w - hi).
+# ================================================================================================
+def _prep_ref(w, mode):
+    O, I, T = w.shape
+    return np.ascontiguousarray(w.transpose(2, 0, 1) if mode == 0 else w[:, :, ::-1].transpose(2, 1, 0))
+
+
+def _hi_lo(v):
+    s = v.astype(np.float32) * np.float32(64)
+    hi = s.astype(np.float16)
+    return hi, (s - hi.astype(np.float32)).astype(np.float16)
+
+
+def _weights_4x4(seed):
+    """multiples of 1/8 plus, in half of the places, 2^-12: 64 w then needs a lo half (2^-6, a normal fp16)"""
+    gen = np.random.default_rng(seed)
+    w = gen.integers(-16, 17, (4, 4, 9)).astype(np.float32) / np.float32(8)
+    return w + gen.integers(0, 2, w.shape).astype(np.float32) * np.float32(2.0 ** -12)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_dtype_gate_prep_weight(dt):
+    w = _weights_4x4(508)
+    wg = _in(w, F32, "w")
+    for mode in (0, 1, 2):
+        dst = _out((9 * 16 * (2 if mode == 2 else 1),), dt, "dst")
+        _dtype_gate("mu_prep_weight", lambda c: (wg, dst, c, 4, 4, 9, 4, 4, mode), [dst], CODE[dt], bad=(BAD_DTYPE,))
+        ref = np.concatenate([_prep_ref(w, m).reshape(-1) for m in ((0, 1) if mode == 2 else (mode,))]).astype(NP[dt])
+        _exact(f"gate prep_weight mode {mode}", _result(dst, ref.shape), ref)
+    # the many-layers form: one job, one 32 x 32 tile
+    jobs = np.array([wg.p, 0, 0, 4, 4, 9, 32, 32, 0, 0], dtype=np.int64)
+    jg, dst = _in(jobs, torch.int64, "jobs"), _out((9 * 32 * 32,), dt, "dst")
+    _dtype_gate("mu_prep_weights_multi", lambda c: (jg, 1, 1, dst, c), [dst], CODE[dt], bad=(BAD_DTYPE,))
+    ref = np.zeros((9, 32, 32), dtype=NP[dt])
+    ref[:, :4, :4] = _prep_ref(w, 0)
+    _exact("gate prep_weights_multi", _result(dst, ref.shape), ref)
+
+
+def test_prep_weight_fp32x_encodes_in_place():
+    w = _weights_4x4(509)
+    wg = _in(w, F32, "w")
+    hi0, lo0 = _hi_lo(_prep_ref(w, 0).reshape(-1, 4))          # chunks of four along the input channels
+    hi1, lo1 = _hi_lo(_prep_ref(w, 1).reshape(-1, 4))          # rows of rows_pad = 4 output channels
+    assert (lo0 != 0).any() and (lo1 != 0).any()
+    fwd, dgrad = np.concatenate([hi0, lo0], axis=1).reshape(-1), np.concatenate([lo1, hi1], axis=1).reshape(-1)
+    for mode, ref in ((0, fwd), (2, np.concatenate([fwd, dgrad]))):
+        dst = _out((ref.size // 2,), F32, "dst")
+        call("mu_prep_weight", wg, dst, MU_F32X, 4, 4, 9, 4, 4, mode)
+        got = dst.host().view(np.float16)
+        _exact(f"prep_weight fp32x mode {mode}", got, ref)
+
+
+def test_prep_weight_fp32x_refuses_before_it_launches():
+    """rows_pad or cols_pad no multiple of four, and a data-gradient row longer than 8192: MU_ERR_SHAPE with dst untouched"""
+    wg = _in(_weights_4x4(510), F32, "w")
+    for rp, cp in ((6, 4), (4, 6)):
+        dst = _out((9 * rp * cp,), F32, "dst")
+        _refused("MU_ERR_SHAPE", "mu_prep_weight", wg, dst, MU_F32X, 4, 4, 9, rp, cp, 0, outs=[dst])
+    w1 = _in(np.ones((1, 1, 9), dtype=np.float32), F32, "w")
+    dst = _out((9 * 4 * 8196,), F32, "dst")
+    _refused("MU_ERR_SHAPE", "mu_prep_weight", w1, dst, MU_F32X, 1, 1, 9, 4, 8196, 1, outs=[dst])

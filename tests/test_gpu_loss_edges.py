@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from tests import _loss_reference as R
+from tests._device_buffers import Guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -357,6 +358,77 @@ def test_mean_iou_layout_keyword_on_the_ambiguous_shape():
         maskunet_amd.mean_iou(xd, ld, C, layout="hwcn")
     with pytest.raises(RuntimeError):
         maskunet_amd.mean_iou(xd[..., :24].contiguous(), ld, C, layout="nhwc")        # fewer channels than classes
+
+
+# ================================================================================================
+# the dtype gate of the cross-entropy and IoU entry points: MU_F32X and an unknown dtype are MU_ERR_ARG before anything is launched --
+# lse, loss, count and the gradient still hold the sentinel; a short workspace is named first (MU_ERR_WORKSPACE)
+# ================================================================================================
+BAD_DTYPES = [pytest.param(2, id="MU_F32X"), pytest.param(99, id="99")]
+
+
+def _refused(code, name, *args, outs):
+    from maskunet_amd import _lib
+    with pytest.raises(RuntimeError, match=code):
+        _lib.call(name, *[a.p if isinstance(a, Guarded) else a for a in args], _lib.stream())
+    torch.cuda.synchronize()
+    for a in list(args) + list(outs):
+        if isinstance(a, Guarded):
+            a.check()
+    for o in outs:
+        assert bool((o.t == o.sent).all()), (name, code, o.name)
+
+
+def _ce_operands(n_logits, n_pix):
+    """fp32-sized buffers (an fp16 reading of them is shorter): logits, labels, lse, loss, count, grad_out, dlogits, workspace"""
+    from maskunet_amd import _lib
+    g = {"logits": Guarded(n_logits, F32, np.zeros(n_logits, np.float32), "logits"),
+         "labels": Guarded(n_pix, torch.int64, np.zeros(n_pix, np.int64), "labels"),
+         "gout": Guarded(1, F32, np.ones(1, np.float32), "grad_out")}
+    for name, n in (("lse", n_pix), ("loss", 1), ("count", 1), ("dlogits", n_logits)):
+        g[name] = Guarded(n, F32, name=name)
+    nws = _lib.load().mu_ce_workspace_bytes()
+    g["ws"] = Guarded(nws, torch.uint8, name="workspace")
+    return g, nws
+
+
+@pytest.mark.parametrize("bad", BAD_DTYPES)
+def test_ce_nhwc_dtype_gate(bad):
+    M, C, Cp = 1, 2, 8
+    g, nws = _ce_operands(M * Cp, M)
+    fwd_outs = [g["lse"], g["loss"], g["count"], g["ws"]]
+    _refused("MU_ERR_ARG", "mu_ce_fwd", g["logits"], g["labels"], M, Cp, C, -100, g["lse"], g["loss"], g["count"], g["ws"], nws, bad, outs=fwd_outs)
+    _refused("MU_ERR_WORKSPACE", "mu_ce_fwd", g["logits"], g["labels"], M, Cp, C, -100, g["lse"], g["loss"], g["count"], g["ws"], nws - 1, bad,
+             outs=fwd_outs)
+    g["lse"].t.zero_()                                         # the backward's inputs
+    g["count"].t.fill_(1.0)
+    _refused("MU_ERR_ARG", "mu_ce_bwd", g["logits"], g["labels"], g["lse"], g["count"], g["gout"], 1.0, M, Cp, C, -100, g["dlogits"], bad,
+             outs=[g["dlogits"]])
+
+
+@pytest.mark.parametrize("HW", [3, 4], ids=["1px-per-lane", "4px-per-lane"])
+@pytest.mark.parametrize("bad", BAD_DTYPES)
+def test_ce_nchw_dtype_gate(bad, HW):
+    B, C = 1, 2
+    g, nws = _ce_operands(B * C * HW, B * HW)
+    fwd_outs = [g["lse"], g["loss"], g["count"], g["ws"]]
+    _refused("MU_ERR_ARG", "mu_ce_nchw_fwd", g["logits"], g["labels"], B, C, HW, -100, g["lse"], g["loss"], g["count"], g["ws"], nws, bad,
+             outs=fwd_outs)
+    _refused("MU_ERR_WORKSPACE", "mu_ce_nchw_fwd", g["logits"], g["labels"], B, C, HW, -100, g["lse"], g["loss"], g["count"], g["ws"], nws - 1, bad,
+             outs=fwd_outs)
+    g["lse"].t.zero_()
+    g["count"].t.fill_(1.0)
+    _refused("MU_ERR_ARG", "mu_ce_nchw_bwd", g["logits"], g["labels"], g["lse"], g["count"], g["gout"], 1.0, B, C, HW, -100, g["dlogits"], bad,
+             outs=[g["dlogits"]])
+
+
+@pytest.mark.parametrize("bad", BAD_DTYPES)
+def test_mean_iou_dtype_gate(bad):
+    """`out` stays untouched.  (The counts are cleared before the dtype is looked at, on a refused call too: they are scratch.)"""
+    M, C, Cp = 1, 2, 8
+    g, _ = _ce_operands(M * Cp, M)
+    counts, out = Guarded(3 * C, torch.int32, name="counts"), Guarded(1, F32, name="out")
+    _refused("MU_ERR_ARG", "mu_mean_iou", g["logits"], g["labels"], M, C, M, 0, 1, Cp, 1e-6, counts, out, bad, outs=[out])
 
 
 # ================================================================================================
