@@ -6,6 +6,10 @@ pair are zero and the dy scale of the fp32x backward is a power of two.  A corre
 returns the CPU reference BIT FOR BIT; one wrong index is off by at least 1.  Each case checks these preconditions on the reference
 alone before any GPU call (and thins x by a seeded fraction where a shape breaks one).
 
+What zero lo halves cannot show -- the three split products of fp32x, the two-term gradients on HL rows and pair columns, the low
+mantissa bits of exact fp32 -- is held bit for bit by tests/test_gpu_conv_exact_pairs.py, on operands a + b 2^-14 whose lo halves are
+alive; it imports the comparator, the guarded buffers and the entries below.
+
 Cases: tests/_conv_cases.LAYERS, one pytest id per (entry, dtype, kernel, shape); the kernel name comes from the mu_conv_*_plan
 queries.  Memory discipline in every case: outputs pre-filled with NaN, row padding (ld - C columns) and 4 KiB guard bands before and
 after every output and the workspace hold a sentinel that must survive, workspaces have exactly the queried size and start as NaN.
