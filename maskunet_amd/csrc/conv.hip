@@ -1779,6 +1779,54 @@ __global__ __launch_bounds__(512, 1) void conv_nt5_kernel(const h16* __restrict_
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// host layer of the forward-shaped entries
+// ------------------------------------------------------------------------------------------
+// Pixel geometry of a call, computed once: the selection functions and every launcher read the tile counts from here, so the rows of
+// statistics a plan reports and the grid that writes them come from the same numbers.
+struct ConvGeom {
+    int B, H, W;
+    long M;                 // pixels
+    long t16, t8;           // whole 16 x 16 / 8 x 16 pixel tiles (the halo-tile kernels; their plans require H % 16 / H % 8 and W % 16)
+    int pb128, pb256;       // blocks of 128 / 256 pixels (the shape-agnostic kernels)
+};
+static ConvGeom conv_geom_rows(long M) { return {1, 1, (int)M, M, 0, 0, (int)((M + 127) / 128), (int)((M + 255) / 256)}; }
+static ConvGeom conv_geom(int B, int H, int W) {
+    ConvGeom g = conv_geom_rows((long)B * H * W);
+    g.B = B, g.H = H, g.W = W;
+    g.t16 = (long)B * (H / 16) * (W / 16);
+    g.t8 = (long)B * (H / 8) * (W / 16);
+    return g;
+}
+
+// The dtype x taps dispatch of the conv entry points: f(T{}, tap_c<TAPS>{}) with T the operand type of the kernels.  MU_F32X is fp32
+// storage in one of two encodings, and this is the one place that says which: 3x3 layers run on fp16 pairs (xh32), 1x1 layers on bf16
+// pairs (xf32).  An unknown dtype or tap count is MU_ERR_ARG.
+template <int TAPS> using tap_c = std::integral_constant<int, TAPS>;
+template <int TAPS, typename F>
+static inline int with_conv_storage(int dtype, F&& f) {
+    if (dtype != MU_F32X) return with_storage(dtype, f);
+    if constexpr (TAPS == 9) return f(xh32{});
+    else return f(xf32{});
+}
+template <typename F>
+static inline int with_conv_type(int dtype, int taps, F&& f) {
+    if (taps == 9) return with_conv_storage<9>(dtype, [&](auto t) -> int { return f(t, tap_c<9>{}); });
+    if (taps == 1) return with_conv_storage<1>(dtype, [&](auto t) -> int { return f(t, tap_c<1>{}); });
+    return MU_ERR_ARG;
+}
+
+// The argument check of the forward-shaped entries, and their refusal order: null pointers and non-positive sizes (`args_ok`, the
+// entry's own list: MU_ERR_ARG), then channel counts and row strides (MU_ERR_SHAPE: Cin a multiple of 32, Cout of `cout_mult`, strides
+// that hold a row, x_ld a multiple of 8 elements and y_ld of `y_ld_mult`), then what only that entry has -- a statistics buffer on a
+// shape without statistics rows (MU_ERR_SHAPE, before taps is looked at), then taps / act / dtype (MU_ERR_ARG).  Nothing is launched
+// before the last check has passed.
+static int conv_io_check(bool args_ok, int Cin, int Cout, long x_ld, long y_ld, int cout_mult = 32, int y_ld_mult = 8) {
+    if (!args_ok) return MU_ERR_ARG;
+    if (Cin <= 0 || Cout <= 0 || Cin % 32 || Cout % cout_mult || x_ld < Cin || y_ld < Cout || x_ld % 8 || y_ld % y_ld_mult) return MU_ERR_SHAPE;
+    return MU_OK;
+}
+
 // The 3x3 forward plan: which halo-tile kernel of conv_fwd_launch<T, 9> serves the shape (K3_NONE: the shape is not on the halo-tile
 // path), and how many rows of per-tile BatchNorm statistics its epilogue writes when it is handed stat_part (0: no statistics epilogue).
 // mu_conv_stats_rows reads the same plan, so the statistics rows always describe the kernel that runs.
@@ -1787,10 +1835,10 @@ struct Conv3x3Plan {
     Conv3x3Kernel kernel;
     int stat_rows;
 };
-static Conv3x3Plan conv3x3_pick(int B, int H, int W, int Cin, int Cout, int dtype, bool with_stats) {
-    const int es = dtype == MU_F16 ? 2 : 4;
-    if ((Cin * es) % 128 || W % 16) return {K3_NONE, 0};
-    const long t16 = (long)B * (H / 16) * (W / 16);          // 16 x 16 tiles: the ping-pong kernels write one row per tile and wave group
+static Conv3x3Plan conv3x3_pick(const ConvGeom& g, int Cin, int Cout, int dtype, bool with_stats) {
+    const int es = dtype == MU_F16 ? 2 : 4, H = g.H;
+    if ((Cin * es) % 128 || g.W % 16) return {K3_NONE, 0};
+    const long t16 = g.t16;                                  // the ping-pong kernels write one row per 16 x 16 tile and wave group
     const int rows16 = (int)(t16 * 4);
     if (dtype == MU_F16) {
         // (two tiles per block at least: below 512 tiles, one of the two wave groups would idle)
@@ -1809,7 +1857,7 @@ static Conv3x3Plan conv3x3_pick(int B, int H, int W, int Cin, int Cout, int dtyp
     // idle, where the generic kernel's 8 x 16 pixel tiles still fill it (61 vs 72 us in-process)
     if (dtype == MU_F32X && Cout % 128 == 0 && H % 16 == 0 && t16 * (Cout / 128) >= 192) return {K3_NT4X, rows16};
     if (H % 8) return {K3_NONE, 0};
-    const int t8 = B * (H / 8) * (W / 16);                  // 8 x 16 tiles: one row per tile and wave row
+    const int t8 = (int)g.t8;                                // 8 x 16 tiles: one row per tile and wave row
     if (Cout % 128 == 0) return {K3_NT3_128, t8 * 2};
     // the three-slot weight ring pays for its longer prologue from two 64-channel chunks on (see conv_nt3_body)
     if (Cout % 64 == 0) return {Cin * es >= 256 ? K3_NT3_64_RING : K3_NT3_64, t8 * 4};
@@ -1817,7 +1865,7 @@ static Conv3x3Plan conv3x3_pick(int B, int H, int W, int Cin, int Cout, int dtyp
 }
 
 // Plan ids of the other conv entry points (mu_conv_*_plan; names: mu_conv_plan_name).  0 = no kernel serves the arguments.  Every launch
-// function below switches on its *_pick, so a query and the launch it describes cannot disagree.
+// function below -- conv_wgrad_impl included -- switches on its *_pick, so a query and the launch it describes cannot disagree.
 // Forward (mu_conv_fwd / mu_conv_fwd_stats): the Conv3x3Kernel values for the halo-tile kernels, then the shape-agnostic kernels.
 enum ConvFwdKernel {
     KF_WIDE192_SB = K3_NT3_64 + 1,      // fp16 1x1, Cout % 192 == 0, Cin == 64: single-stage form, row-staged epilogue
@@ -1828,10 +1876,10 @@ enum ConvFwdKernel {
     KF_GEN128, KF_GEN64, KF_GEN32,      // generic register-staged kernel
     KF_COUNT
 };
-static int conv_fwd_pick(int B, int H, int W, int Cin, int Cout, int taps, int dtype, bool with_stats) {
+static int conv_fwd_pick(const ConvGeom& g, int Cin, int Cout, int taps, int dtype, bool with_stats) {
     const int es = dtype == MU_F16 ? 2 : 4;
     if (taps == 9) {
-        const Conv3x3Kernel k3 = conv3x3_pick(B, H, W, Cin, Cout, dtype, with_stats).kernel;
+        const Conv3x3Kernel k3 = conv3x3_pick(g, Cin, Cout, dtype, with_stats).kernel;
         if (k3 != K3_NONE) return k3;
     }
     if (taps == 1 && dtype == MU_F16) {
@@ -1847,10 +1895,9 @@ static int conv_fwd_pick(int B, int H, int W, int Cin, int Cout, int taps, int d
 
 // Inference epilogue (mu_conv_fwd_fused)
 enum ConvFusedKernel { FF_NONE, FF_NT4F, FF_NT3F_128, FF_NT3F_64, FF_HEAD160, FF_DMA128, FF_DMA64, FF_GEN128, FF_GEN64, FF_GEN32, FF_COUNT };
-static ConvFusedKernel conv_fused_pick(int B, int H, int W, int Cin, int Cout, int taps, int dtype) {
-    (void)B;
-    const int es = dtype == MU_F16 ? 2 : 4;
-    if (taps == 9 && (Cin * es) % 128 == 0 && W % 16 == 0) {
+static ConvFusedKernel conv_fused_pick(const ConvGeom& g, int Cin, int Cout, int taps, int dtype) {
+    const int es = dtype == MU_F16 ? 2 : 4, H = g.H;
+    if (taps == 9 && (Cin * es) % 128 == 0 && g.W % 16 == 0) {
         if (dtype == MU_F16 && Cout % 128 == 0 && H % 16 == 0 && Cin % 64 == 0) return FF_NT4F;
         if (Cout % 128 == 0 && H % 8 == 0) return FF_NT3F_128;
         if (Cout % 64 == 0 && H % 8 == 0) return FF_NT3F_64;
@@ -1860,28 +1907,28 @@ static ConvFusedKernel conv_fused_pick(int B, int H, int W, int Cin, int Cout, i
     return Cout % 128 == 0 ? FF_GEN128 : Cout % 64 == 0 ? FF_GEN64 : FF_GEN32;
 }
 
+template <typename T> constexpr int conv_dtype_of = sizeof(T) == 2 ? MU_F16 : mu_is_split<T>::value ? MU_F32X : MU_F32;
+
 // The same dispatch for the inference epilogue y = act(conv * scale + bias + res): FEPI instantiations of the non-persistent kernels
 // (the persistent ping-pong kernel counts its epilogue's memory operations in hand-placed vmcnt waits and takes no epilogue loads).
 template <typename T, int TAPS>
-static int conv_fwd_fused_launch(const T* x, const T* w, const float* scale, const float* bias, const T* res, int act, T* y, int B, int H, int W,
-                                 int Cin, int Cout, long x_ld, long y_ld, hipStream_t st) {
-    const long M = (long)B * H * W;
-    const int npb = (int)((M + 127) / 128);
-    constexpr int dtype = sizeof(T) == 2 ? MU_F16 : mu_is_split<T>::value ? MU_F32X : MU_F32;
-    switch (conv_fused_pick(B, H, W, Cin, Cout, TAPS, dtype)) {
+static void conv_fwd_fused_launch(const T* x, const T* w, const float* scale, const float* bias, const T* res, int act, T* y, const ConvGeom& g,
+                                  int Cin, int Cout, long x_ld, long y_ld, hipStream_t st) {
+    const int B = g.B, H = g.H, W = g.W, npb = g.pb128, t16 = (int)g.t16, t8 = (int)g.t8;
+    switch (conv_fused_pick(g, Cin, Cout, TAPS, conv_dtype_of<T>)) {
     case FF_NONE:
         break;
     case FF_NT4F:
         if constexpr (sizeof(T) == 2 && TAPS == 9)
-            conv_nt4f_kernel<<<B * (H / 16) * (W / 16) * (Cout / 128), 512, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
+            conv_nt4f_kernel<<<t16 * (Cout / 128), 512, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
         break;
     case FF_NT3F_128:
         if constexpr (TAPS == 9)
-            conv_nt3f_kernel<T, 4, 4, 2><<<B * (H / 8) * (W / 16) * (Cout / 128), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
+            conv_nt3f_kernel<T, 4, 4, 2><<<t8 * (Cout / 128), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
         break;
     case FF_NT3F_64:
         if constexpr (TAPS == 9)
-            conv_nt3f_kernel<T, 4, 2, 1><<<B * (H / 8) * (W / 16) * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
+            conv_nt3f_kernel<T, 4, 2, 1><<<t8 * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
         break;
     case FF_HEAD160:                                                     // the 150-class head: one tile spans all output channels
         if constexpr (TAPS == 1 && sizeof(T) == 2)
@@ -1891,7 +1938,7 @@ static int conv_fwd_fused_launch(const T* x, const T* w, const float* scale, con
         conv_nt2_kernel<T, 4, 4, 2, TAPS, false, true><<<npb * (Cout / 128), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, res, scale, act);
         break;
     case FF_DMA64:
-        conv_nt2_kernel<T, 4, 4, 1, TAPS, false, true><<<(int)((M + 255) / 256) * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, res, scale, act);
+        conv_nt2_kernel<T, 4, 4, 1, TAPS, false, true><<<g.pb256 * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, res, scale, act);
         break;
     case FF_GEN128:
         conv_nt_kernel<T, 4, 4, 2, TAPS, true><<<npb * (Cout / 128), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld, scale, res, act);
@@ -1905,18 +1952,14 @@ static int conv_fwd_fused_launch(const T* x, const T* w, const float* scale, con
     case FF_COUNT:
         break;
     }
-    return MU_OK;
 }
 
 template <typename T, int TAPS>
-static int conv_fwd_launch(const T* x, const T* w, const float* bias, T* y, int B, int H, int W, int Cin, int Cout, long x_ld,
-                           long y_ld, hipStream_t st, float* stat_part = nullptr) {
-    const long M = (long)B * H * W;
-    const int npb = (int)((M + 127) / 128);
+static void conv_fwd_launch(const T* x, const T* w, const float* bias, T* y, const ConvGeom& g, int Cin, int Cout, long x_ld, long y_ld,
+                            hipStream_t st, float* stat_part = nullptr) {
+    const int B = g.B, H = g.H, W = g.W, npb = g.pb128, t16 = (int)g.t16, t8 = (int)g.t8;
     // (the plan names the fp16 kernels for h16 only, conv_nt4x_kernel for xh32 only and the wide 1x1 tiles for the types that have them)
-    constexpr int dtype = sizeof(T) == 2 ? MU_F16 : mu_is_split<T>::value ? MU_F32X : MU_F32;
-    const int t16 = B * (H / 16) * (W / 16), t8 = B * (H / 8) * (W / 16);
-    switch (conv_fwd_pick(B, H, W, Cin, Cout, TAPS, dtype, stat_part != nullptr)) {
+    switch (conv_fwd_pick(g, Cin, Cout, TAPS, conv_dtype_of<T>, stat_part != nullptr)) {
     case K3_NT5:
         if constexpr (sizeof(T) == 2 && TAPS == 9)
             conv_nt5_kernel<<<t16 < 256 ? t16 : 256, 512, 0, st>>>((const h16*)x, (const h16*)w, bias, (h16*)y, B, H, W, x_ld, y_ld, stat_part, 64);
@@ -1965,7 +2008,7 @@ static int conv_fwd_launch(const T* x, const T* w, const float* bias, T* y, int 
         conv_nt2_kernel<T, 4, 4, 2, TAPS><<<npb * (Cout / 128), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
         break;
     case KF_DMA64:
-        conv_nt2_kernel<T, 4, 4, 1, TAPS><<<(int)((M + 255) / 256) * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
+        conv_nt2_kernel<T, 4, 4, 1, TAPS><<<g.pb256 * (Cout / 64), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
         break;
     case KF_GEN128:
         conv_nt_kernel<T, 4, 4, 2, TAPS><<<npb * (Cout / 128), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
@@ -1977,14 +2020,13 @@ static int conv_fwd_launch(const T* x, const T* w, const float* bias, T* y, int 
         conv_nt_kernel<T, 2, 2, 1, TAPS><<<npb * (Cout / 32), 256, 0, st>>>(x, w, bias, y, B, H, W, Cin, Cout, x_ld, y_ld);
         break;
     }
-    return MU_OK;
 }
 
 // Rows of per-tile BatchNorm statistics mu_conv_fwd_stats writes for this layer shape (0: the kernel that serves it has no
 // statistics epilogue -- run mu_bn_train_stats on the output instead): the count of the 3x3 forward plan (conv3x3_pick).
 extern "C" int mu_conv_stats_rows(int B, int H, int W, int Cin, int Cout, int taps, int dtype) {
     if (taps != 9 || B <= 0 || (dtype != MU_F16 && dtype != MU_F32X)) return 0;
-    return conv3x3_pick(B, H, W, Cin, Cout, dtype, true).stat_rows;
+    return conv3x3_pick(conv_geom(B, H, W), Cin, Cout, dtype, true).stat_rows;
 }
 
 static bool conv_plan_args_ok(int B, int H, int W, int Cin, int Cout, int taps, int dtype) {
@@ -1997,61 +2039,43 @@ static bool conv_plan_args_ok(int B, int H, int W, int Cin, int Cout, int taps, 
 extern "C" int mu_conv_fwd_plan(int B, int H, int W, int Cin, int Cout, int taps, int dtype, int with_stats) {
     if (!conv_plan_args_ok(B, H, W, Cin, Cout, taps, dtype)) return 0;
     if (with_stats && mu_conv_stats_rows(B, H, W, Cin, Cout, taps, dtype) == 0) return 0;
-    return conv_fwd_pick(B, H, W, Cin, Cout, taps, dtype, with_stats != 0);
+    return conv_fwd_pick(conv_geom(B, H, W), Cin, Cout, taps, dtype, with_stats != 0);
 }
 extern "C" int mu_conv_fwd_fused_plan(int B, int H, int W, int Cin, int Cout, int taps, int dtype) {
     if (!conv_plan_args_ok(B, H, W, Cin, Cout, taps, dtype)) return 0;
-    return conv_fused_pick(B, H, W, Cin, Cout, taps, dtype);
+    return conv_fused_pick(conv_geom(B, H, W), Cin, Cout, taps, dtype);
 }
 
 extern "C" int mu_conv_fwd_stats(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin, int Cout,
                                  int taps, long x_ld, long y_ld, int dtype, float* stat_part, void* stream) {
-    if (!x || !w || !y || B <= 0 || H <= 0 || W <= 0) return MU_ERR_ARG;
-    if (Cin <= 0 || Cout <= 0 || Cin % 32 || Cout % 32 || x_ld < Cin || y_ld < Cout || x_ld % 8 || y_ld % 8) return MU_ERR_SHAPE;
+    if (const int rc = conv_io_check(x && w && y && B > 0 && H > 0 && W > 0, Cin, Cout, x_ld, y_ld)) return rc;
     if (stat_part && mu_conv_stats_rows(B, H, W, Cin, Cout, taps, dtype) == 0) return MU_ERR_SHAPE;
-    if (!stat_part) return mu_conv_fwd(x, w, bias, y, B, H, W, Cin, Cout, taps, x_ld, y_ld, dtype, stream);
-    if (dtype == MU_F32X) conv_fwd_launch<xh32, 9>((const xh32*)x, (const xh32*)w, bias, (xh32*)y, B, H, W, Cin, Cout, x_ld, y_ld, (hipStream_t)stream, stat_part);
-    else conv_fwd_launch<h16, 9>((const h16*)x, (const h16*)w, bias, (h16*)y, B, H, W, Cin, Cout, x_ld, y_ld, (hipStream_t)stream, stat_part);
-    MU_CHECK_LAUNCH();
-    return MU_OK;
-}
-
-extern "C" int mu_conv_fwd_fused(const void* x, const void* w, const float* scale, const float* bias, const void* res, int act, void* y, int B,
-                                 int H, int W, int Cin, int Cout, int taps, long x_ld, long y_ld, int dtype, void* stream) {
-    if (!x || !w || !y || B <= 0 || H <= 0 || W <= 0) return MU_ERR_ARG;
-    if (Cin <= 0 || Cout <= 0 || Cin % 32 || Cout % 32 || x_ld < Cin || y_ld < Cout || x_ld % 8 || y_ld % 8) return MU_ERR_SHAPE;
-    if ((taps != 1 && taps != 9) || act < MU_ACT_NONE || act > MU_ACT_RELU) return MU_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MU_F16) {
-        if (taps == 9) conv_fwd_fused_launch<h16, 9>((const h16*)x, (const h16*)w, scale, bias, (const h16*)res, act, (h16*)y, B, H, W, Cin, Cout, x_ld, y_ld, st);
-        else conv_fwd_fused_launch<h16, 1>((const h16*)x, (const h16*)w, scale, bias, (const h16*)res, act, (h16*)y, B, H, W, Cin, Cout, x_ld, y_ld, st);
-    } else if (dtype == MU_F32) {
-        if (taps == 9) conv_fwd_fused_launch<float, 9>((const float*)x, (const float*)w, scale, bias, (const float*)res, act, (float*)y, B, H, W, Cin, Cout, x_ld, y_ld, st);
-        else conv_fwd_fused_launch<float, 1>((const float*)x, (const float*)w, scale, bias, (const float*)res, act, (float*)y, B, H, W, Cin, Cout, x_ld, y_ld, st);
-    } else if (dtype == MU_F32X) {
-        if (taps == 9) conv_fwd_fused_launch<xh32, 9>((const xh32*)x, (const xh32*)w, scale, bias, (const xh32*)res, act, (xh32*)y, B, H, W, Cin, Cout, x_ld, y_ld, st);
-        else conv_fwd_fused_launch<xf32, 1>((const xf32*)x, (const xf32*)w, scale, bias, (const xf32*)res, act, (xf32*)y, B, H, W, Cin, Cout, x_ld, y_ld, st);
-    } else return MU_ERR_ARG;
+    const int rc = with_conv_type(dtype, taps, [&](auto t, auto tc) -> int {
+        using T = decltype(t);
+        conv_fwd_launch<T, decltype(tc)::value>((const T*)x, (const T*)w, bias, (T*)y, conv_geom(B, H, W), Cin, Cout, x_ld, y_ld, (hipStream_t)stream, stat_part);
+        return MU_OK;
+    });
+    if (rc) return rc;
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
 
 extern "C" int mu_conv_fwd(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int Cin, int Cout, int taps,
                            long x_ld, long y_ld, int dtype, void* stream) {
-    if (!x || !w || !y || B <= 0 || H <= 0 || W <= 0) return MU_ERR_ARG;
-    if (Cin <= 0 || Cout <= 0 || Cin % 32 || Cout % 32 || x_ld < Cin || y_ld < Cout || x_ld % 8 || y_ld % 8) return MU_ERR_SHAPE;
-    if (taps != 1 && taps != 9) return MU_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MU_F16) {
-        if (taps == 9) conv_fwd_launch<h16, 9>((const h16*)x, (const h16*)w, bias, (h16*)y, B, H, W, Cin, Cout, x_ld, y_ld, st);
-        else conv_fwd_launch<h16, 1>((const h16*)x, (const h16*)w, bias, (h16*)y, B, H, W, Cin, Cout, x_ld, y_ld, st);
-    } else if (dtype == MU_F32) {
-        if (taps == 9) conv_fwd_launch<float, 9>((const float*)x, (const float*)w, bias, (float*)y, B, H, W, Cin, Cout, x_ld, y_ld, st);
-        else conv_fwd_launch<float, 1>((const float*)x, (const float*)w, bias, (float*)y, B, H, W, Cin, Cout, x_ld, y_ld, st);
-    } else if (dtype == MU_F32X) {
-        if (taps == 9) conv_fwd_launch<xh32, 9>((const xh32*)x, (const xh32*)w, bias, (xh32*)y, B, H, W, Cin, Cout, x_ld, y_ld, st);
-        else conv_fwd_launch<xf32, 1>((const xf32*)x, (const xf32*)w, bias, (xf32*)y, B, H, W, Cin, Cout, x_ld, y_ld, st);
-    } else return MU_ERR_ARG;
+    return mu_conv_fwd_stats(x, w, bias, y, B, H, W, Cin, Cout, taps, x_ld, y_ld, dtype, nullptr, stream);
+}
+
+extern "C" int mu_conv_fwd_fused(const void* x, const void* w, const float* scale, const float* bias, const void* res, int act, void* y, int B,
+                                 int H, int W, int Cin, int Cout, int taps, long x_ld, long y_ld, int dtype, void* stream) {
+    if (const int rc = conv_io_check(x && w && y && B > 0 && H > 0 && W > 0, Cin, Cout, x_ld, y_ld)) return rc;
+    if (act < MU_ACT_NONE || act > MU_ACT_RELU) return MU_ERR_ARG;
+    const int rc = with_conv_type(dtype, taps, [&](auto t, auto tc) -> int {
+        using T = decltype(t);
+        conv_fwd_fused_launch<T, decltype(tc)::value>((const T*)x, (const T*)w, scale, bias, (const T*)res, act, (T*)y, conv_geom(B, H, W), Cin, Cout, x_ld,
+                                                      y_ld, (hipStream_t)stream);
+        return MU_OK;
+    });
+    if (rc) return rc;
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
@@ -2064,10 +2088,9 @@ extern "C" int mu_conv_fwd(const void* x, const void* w, const float* bias, void
 // Weight terms: both halves (HL = 2).  With the hi halves only -- one MFMA per product -- the step was 1.5 ms shorter same-box, but the
 // small-module goldens' parameter gradients landed at 1.06e-3 .. 1.17e-3 against their 1e-3 gate: 9 * Cout = 72 .. 288 terms average too little.
 enum ConvDgradHKernel { DH_NONE, DH_NT4HL, DH_NT3HL_128, DH_NT3HL_64, DH_GEN128, DH_GEN64, DH_GEN32, DH_COUNT };
-static ConvDgradHKernel conv_dgrad_h_pick(int B, int H, int W, int Cin, int Cout) {
-    (void)B;
-    if (Cin % 64 == 0 && W % 16 == 0 && H % 8 == 0 && Cout % 64 == 0) {
-        if (Cout % 128 == 0 && H % 16 == 0) return DH_NT4HL;
+static ConvDgradHKernel conv_dgrad_h_pick(const ConvGeom& g, int Cin, int Cout) {
+    if (Cin % 64 == 0 && g.W % 16 == 0 && g.H % 8 == 0 && Cout % 64 == 0) {
+        if (Cout % 128 == 0 && g.H % 16 == 0) return DH_NT4HL;
         return Cout % 128 == 0 ? DH_NT3HL_128 : DH_NT3HL_64;
     }
     return Cout % 128 == 0 ? DH_GEN128 : Cout % 64 == 0 ? DH_GEN64 : DH_GEN32;
@@ -2075,28 +2098,27 @@ static ConvDgradHKernel conv_dgrad_h_pick(int B, int H, int W, int Cin, int Cout
 // (Cin = channels of dy, Cout = channels of dx, as in mu_conv_dgrad_h)
 extern "C" int mu_conv_dgrad_h_plan(int B, int H, int W, int Cin, int Cout) {
     if (!conv_plan_args_ok(B, H, W, Cin, Cout, 9, MU_F32X)) return 0;
-    return conv_dgrad_h_pick(B, H, W, Cin, Cout);
+    return conv_dgrad_h_pick(conv_geom(B, H, W), Cin, Cout);
 }
 extern "C" int mu_conv_dgrad_h(const void* dy_h, const void* w_hl, const float* dy_scale, void* dx, int B, int H, int W, int Cin, int Cout,
                                long dy_ld, long dx_ld, void* stream) {
-    if (!dy_h || !w_hl || !dy_scale || !dx || B <= 0 || H <= 0 || W <= 0) return MU_ERR_ARG;
-    if (Cin <= 0 || Cout <= 0 || Cin % 32 || Cout % 32 || dy_ld < Cin || dx_ld < Cout || dy_ld % 8 || dx_ld % 4) return MU_ERR_SHAPE;
+    if (const int rc = conv_io_check(dy_h && w_hl && dy_scale && dx && B > 0 && H > 0 && W > 0, Cin, Cout, dy_ld, dx_ld, 32, 4)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const h16* x = (const h16*)dy_h;
     const h16* w = (const h16*)w_hl;
     float* y = (float*)dx;
-    const long M = (long)B * H * W;
-    const int npb = (int)((M + 127) / 128);
+    const ConvGeom g = conv_geom(B, H, W);
+    const int npb = g.pb128, t16 = (int)g.t16, t8 = (int)g.t8;
     constexpr int HL = 2;
-    switch (conv_dgrad_h_pick(B, H, W, Cin, Cout)) {
+    switch (conv_dgrad_h_pick(g, Cin, Cout)) {
     case DH_NT4HL:
-        conv_nt4hl_kernel<HL><<<B * (H / 16) * (W / 16) * (Cout / 128), 512, 0, st>>>(x, w, y, B, H, W, Cin, Cout, dy_ld, dx_ld, dy_scale);
+        conv_nt4hl_kernel<HL><<<t16 * (Cout / 128), 512, 0, st>>>(x, w, y, B, H, W, Cin, Cout, dy_ld, dx_ld, dy_scale);
         break;
     case DH_NT3HL_128:
-        conv_nt3hl_kernel<4, 4, 2, false, HL><<<B * (H / 8) * (W / 16) * (Cout / 128), 256, 0, st>>>(x, w, y, B, H, W, Cin, Cout, dy_ld, dx_ld, dy_scale);
+        conv_nt3hl_kernel<4, 4, 2, false, HL><<<t8 * (Cout / 128), 256, 0, st>>>(x, w, y, B, H, W, Cin, Cout, dy_ld, dx_ld, dy_scale);
         break;
     case DH_NT3HL_64:
-        conv_nt3hl_kernel<4, 2, 1, true, HL><<<B * (H / 8) * (W / 16) * (Cout / 64), 256, 0, st>>>(x, w, y, B, H, W, Cin, Cout, dy_ld, dx_ld, dy_scale);
+        conv_nt3hl_kernel<4, 2, 1, true, HL><<<t8 * (Cout / 64), 256, 0, st>>>(x, w, y, B, H, W, Cin, Cout, dy_ld, dx_ld, dy_scale);
         break;
     case DH_GEN128:
         conv_nt_kernel<h16, 4, 4, 2, 9, false, HL><<<npb * (Cout / 128), 256, 0, st>>>(x, w, nullptr, nullptr, B, H, W, Cin, Cout, dy_ld, dx_ld, nullptr, nullptr, 0, y, dy_scale);
@@ -2123,41 +2145,39 @@ extern "C" int mu_conv1x1_add_supported(int Cin, int Cout, int dtype) {
     return (dtype == MU_F16 || dtype == MU_F32 || dtype == MU_F32X) && Cin > 0 && Cout > 0 && (Cin * es) % 128 == 0 && Cout % 64 == 0 ? 1 : 0;
 }
 
-template <typename T>
-static void conv1x1_add_launch(const T* x, const T* w, const T* addend, T* y, long M, int Cin, int Cout, long x_ld, long y_ld, hipStream_t st) {
-    const int npb = (int)((M + 127) / 128);
+// The two 1x1 entries over M rows run the LDS-DMA kernel on one image row of M pixels: 128 output channels per tile where Cout allows.
+// `tail...`: what follows y_ld in the kernel's argument list (the addend, or nothing, nothing and MU_NT2_ENC_H).
+template <typename T, bool FEPI, typename... Tail>
+static void conv1x1_launch(const T* x, const T* w, const float* bias, T* y, long M, int Cin, int Cout, long x_ld, long y_ld, hipStream_t st,
+                           Tail... tail) {
+    const ConvGeom g = conv_geom_rows(M);
     if (Cout % 128 == 0)
-        conv_nt2_kernel<T, 4, 4, 2, 1, false, true><<<npb * (Cout / 128), 256, 0, st>>>(x, w, nullptr, y, 1, 1, (int)M, Cin, Cout, x_ld, y_ld, addend);
+        conv_nt2_kernel<T, 4, 4, 2, 1, false, FEPI><<<g.pb128 * (Cout / 128), 256, 0, st>>>(x, w, bias, y, 1, 1, (int)M, Cin, Cout, x_ld, y_ld, tail...);
     else
-        conv_nt2_kernel<T, 4, 4, 1, 1, false, true><<<(int)((M + 255) / 256) * (Cout / 64), 256, 0, st>>>(x, w, nullptr, y, 1, 1, (int)M, Cin, Cout, x_ld, y_ld, addend);
+        conv_nt2_kernel<T, 4, 4, 1, 1, false, FEPI><<<g.pb256 * (Cout / 64), 256, 0, st>>>(x, w, bias, y, 1, 1, (int)M, Cin, Cout, x_ld, y_ld, tail...);
 }
 
 // The q/k/v projection of the fp32x attention block with its output written DIRECTLY in the attention operand encoding ([8 fp16 hi |
 // 8 fp16 lo] per eight channels, mu_split_encode_h form): saves the read + write pass over qkv [B, N, 3C] behind the projection.
 extern "C" int mu_conv1x1_fwd_enc_h(const void* x, const void* w, const float* bias, void* y, long M, int Cin, int Cout, long x_ld, long y_ld,
                                     void* stream) {
-    if (!x || !w || !y || M <= 0 || M > 0x7fffffffL) return MU_ERR_ARG;
-    if (Cin <= 0 || Cout <= 0 || Cin % 32 || Cout % 64 || x_ld < Cin || y_ld < Cout || x_ld % 8 || y_ld % 8) return MU_ERR_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    const xf32* xs = (const xf32*)x;
-    const xf32* ws = (const xf32*)w;
-    const int npb = (int)((M + 127) / 128);
-    if (Cout % 128 == 0)
-        conv_nt2_kernel<xf32, 4, 4, 2, 1><<<npb * (Cout / 128), 256, 0, st>>>(xs, ws, bias, (xf32*)y, 1, 1, (int)M, Cin, Cout, x_ld, y_ld, nullptr, nullptr, MU_NT2_ENC_H);
-    else
-        conv_nt2_kernel<xf32, 4, 4, 1, 1><<<(int)((M + 255) / 256) * (Cout / 64), 256, 0, st>>>(xs, ws, bias, (xf32*)y, 1, 1, (int)M, Cin, Cout, x_ld, y_ld, nullptr, nullptr, MU_NT2_ENC_H);
+    if (const int rc = conv_io_check(x && w && y && M > 0 && M <= 0x7fffffffL, Cin, Cout, x_ld, y_ld, 64)) return rc;
+    conv1x1_launch<xf32, false>((const xf32*)x, (const xf32*)w, bias, (xf32*)y, M, Cin, Cout, x_ld, y_ld, (hipStream_t)stream, (const xf32*)nullptr,
+                                (const float*)nullptr, MU_NT2_ENC_H);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
 
 extern "C" int mu_conv1x1_fwd_add(const void* x, const void* w, const void* addend, void* y, long M, int Cin, int Cout, long x_ld, long y_ld,
                                   int dtype, void* stream) {
-    if (!x || !w || !addend || !y || M <= 0 || M > 0x7fffffffL) return MU_ERR_ARG;
-    if (!mu_conv1x1_add_supported(Cin, Cout, dtype) || x_ld < Cin || y_ld < Cout || x_ld % 8 || y_ld % 8) return MU_ERR_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MU_F16) conv1x1_add_launch<h16>((const h16*)x, (const h16*)w, (const h16*)addend, (h16*)y, M, Cin, Cout, x_ld, y_ld, st);
-    else if (dtype == MU_F32X) conv1x1_add_launch<xf32>((const xf32*)x, (const xf32*)w, (const xf32*)addend, (xf32*)y, M, Cin, Cout, x_ld, y_ld, st);
-    else conv1x1_add_launch<float>((const float*)x, (const float*)w, (const float*)addend, (float*)y, M, Cin, Cout, x_ld, y_ld, st);
+    if (const int rc = conv_io_check(x && w && addend && y && M > 0 && M <= 0x7fffffffL, Cin, Cout, x_ld, y_ld, 64)) return rc;
+    if (!mu_conv1x1_add_supported(Cin, Cout, dtype)) return MU_ERR_SHAPE;      // (also: the dtype, and input rows of whole 128-byte lines)
+    const int rc = with_conv_storage<1>(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        conv1x1_launch<T, true>((const T*)x, (const T*)w, nullptr, (T*)y, M, Cin, Cout, x_ld, y_ld, (hipStream_t)stream, (const T*)addend);
+        return MU_OK;
+    });
+    if (rc) return rc;
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
@@ -2827,33 +2847,35 @@ __global__ __launch_bounds__(256) void wgrad_reduce_pair_kernel(const float* __r
 
 static inline bool wgrad_is_wide(int bco) { return bco == 192 || bco == 160; }
 
-static inline void wgrad_plan(long M, int Cin, int Cout, int taps, int bco, int bci, int* nsplit, long* pps) {
-    long tiles = (long)taps * ((Cout + bco - 1) / bco) * ((Cin + bci - 1) / bci);
+// bytes of `slabs` fp32 partial slabs [taps][Cout][Cin]: the one place the weight-gradient workspace is sized
+static inline long slab_bytes(long slabs, int taps, int Cout, int Cin) { return slabs * taps * Cout * Cin * (long)sizeof(float); }
+
+struct WgradTile { int bco, bci; };                // output x input channels of a tile
+struct WgradSplit { int nsplit; long pps; };       // pixel ranges (= slabs) and pixels per range
+
+static inline WgradSplit wgrad_plan(long M, int Cin, int Cout, int taps, WgradTile t) {
+    long tiles = (long)taps * ((Cout + t.bco - 1) / t.bco) * ((Cin + t.bci - 1) / t.bci);
     long want = 2048 / tiles;
     if (want < 1) want = 1;
     long max_split = (M + 255) / 256;           // at least 256 pixels per split
     if (want > max_split) want = max_split;
     // wide tiles: 512 pixel ranges per tile -- these launches are HBM streams and want ~2 blocks per CU in flight
-    const long cap = wgrad_is_wide(bco) ? 512 / tiles > 64 ? 512 / tiles : 64 : 256;
+    const long cap = wgrad_is_wide(t.bco) ? 512 / tiles > 64 ? 512 / tiles : 64 : 256;
     if (want > cap) want = cap;
     long p = (M + want - 1) / want;
     p = (p + 31) / 32 * 32;                    // multiple of both stage depths (32 / 16)
-    *pps = p;
-    *nsplit = (int)((M + p - 1) / p);
+    return {(int)((M + p - 1) / p), p};
 }
 
-static inline void wgrad_tile(int Cin, int Cout, int* bco, int* bci, int taps = 9, bool fp16 = false) {
-    *bco = (Cout % 128 == 0) ? 128 : (Cout % 64 == 0 ? 64 : 32);
-    *bci = (Cin % 128 == 0) ? 128 : (Cin % 64 == 0 ? 64 : 32);
-    if (fp16 && taps == 1 && *bci >= 64 && (Cout % 192 == 0 || Cout == 160)) {
-        // fp16 1x1 layers: tiles that span all (or 192) output channels, both operands read once.  q/k/v projection (Cout = 3C) and the 150 -> 160 class head: with square tiles the narrow operand was re-read per
-        // output-channel tile (64 -> 192: 804 MB instead of 537; 64 -> 160 with 32x32 tiles: 1.34 GB instead of 470 MB)
-        *bco = Cout == 160 ? 160 : 192;
-        return;
-    }
+static inline WgradTile wgrad_tile(int Cin, int Cout, int taps = 9, bool fp16 = false) {
+    const int bco = (Cout % 128 == 0) ? 128 : (Cout % 64 == 0 ? 64 : 32);
+    const int bci = (Cin % 128 == 0) ? 128 : (Cin % 64 == 0 ? 64 : 32);
+    // fp16 1x1 layers: tiles that span all (or 192) output channels, both operands read once.  q/k/v projection (Cout = 3C) and the 150 -> 160 class head: with square tiles the narrow operand was re-read per
+    // output-channel tile (64 -> 192: 804 MB instead of 537; 64 -> 160 with 32x32 tiles: 1.34 GB instead of 470 MB)
+    if (fp16 && taps == 1 && bci >= 64 && (Cout % 192 == 0 || Cout == 160)) return {Cout == 160 ? 160 : 192, bci};
     // supported tile pairs: 128x128, 64x64, 32x32 (+ mixed via the smaller square)
-    int m = *bco < *bci ? *bco : *bci;
-    *bco = m; *bci = m;
+    const int m = bco < bci ? bco : bci;
+    return {m, m};
 }
 
 // v2 (3 taps per block) applies to fp16 3x3 layers with W % 32 == 0 (or W == 16) and 64/128-wide channel tiles.
@@ -2864,24 +2886,23 @@ static inline void wgrad_tile(int Cin, int Cout, int* bco, int* bci, int taps = 
 // same work, so one whole round has no tail, and the fp32 slab traffic (write + reduce: 2.4 GB/step at 512 / 1536 blocks, the reduce
 // kernel at HBM rate) shrinks with the split count.  In-process A/B: 128->128 @128^2 341 -> 324 us, 512->512 @16^2 123 -> 105 us,
 // 64->64 @128^2 147 -> 125 us; 768 blocks (1.5 rounds) for the 4-wave tiles is 10 % WORSE than 512.
-static inline bool wgrad3_choose(int H, int W, int Cin, int Cout, int taps, int dtype, int* tco, int* tci) {
-    if (dtype != MU_F16 || taps != 9 || !(W % 32 == 0 || (W == 16 && H % 2 == 0))) return false;
+// (returns the square tile, 128 or 64; 0: the layer is not served)
+static inline int wgrad3_choose(int H, int W, int Cin, int Cout, int taps, int dtype) {
+    if (dtype != MU_F16 || taps != 9 || !(W % 32 == 0 || (W == 16 && H % 2 == 0))) return 0;
     const int a = Cout % 128 == 0 ? 128 : (Cout % 64 == 0 ? 64 : 0), b = Cin % 128 == 0 ? 128 : (Cin % 64 == 0 ? 64 : 0);
-    if (!a || !b) return false;
-    *tco = *tci = a == b ? a : 64;
-    return true;
+    if (!a || !b) return 0;
+    return a == b ? a : 64;
 }
-static inline void wgrad3_plan(long M, int Cin, int Cout, int tco, int tci, int* nsplit, long* pps) {
-    long tiles = 3L * (Cout / tco) * (Cin / tci);
-    long want = (tco == 128 ? 256 : 512) / tiles;
+static inline WgradSplit wgrad3_plan(long M, int Cin, int Cout, int tile) {
+    long tiles = 3L * (Cout / tile) * (Cin / tile);
+    long want = (tile == 128 ? 256 : 512) / tiles;
     if (want < 1) want = 1;
     long max_split = (M + 511) / 512;
     if (want > max_split) want = max_split;
     if (want > 256) want = 256;
     long p = (M + want - 1) / want;
     p = (p + 63) / 64 * 64;                     // whole 64-pixel stages (the two-k-step kernel); M is a multiple of 32
-    *pps = p;
-    *nsplit = (int)((M + p - 1) / p);
+    return {(int)((M + p - 1) / p), p};
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3376,58 +3397,54 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad9_w16_kernel(const h16* __re
 // `pair` (mu_conv_wgrad_h, round 6): Cin counts the 16-bit COLUMNS of a chunk-encoded fp32x input -- two per channel -- and the layer-size
 // limits below, which were measured on real channel counts, apply to Cin / 2
 static inline int wg9_pair_div(bool pair) { return pair ? 2 : 1; }
-static inline bool wgrad9_w16_choose(int B, int H, int W, int Cin, int Cout, int taps, int dtype, int* nb, int* rpb, bool pair = false) {
-    if (dtype != MU_F16 || taps != 9 || W != 16 || H % 2 || Cin % 64 || Cout % 64 || Cin / wg9_pair_div(pair) > 512 || Cout > 512) return false;
+struct WgradBands { int nb, rpb; };                // row bands (= slabs; 0: the layer is not served) and image rows per band
+static inline WgradBands wgrad9_w16_choose(int B, int H, int W, int Cin, int Cout, int taps, int dtype, bool pair = false) {
+    if (dtype != MU_F16 || taps != 9 || W != 16 || H % 2 || Cin % 64 || Cout % 64 || Cin / wg9_pair_div(pair) > 512 || Cout > 512) return {0, 0};
     const long rows = (long)B * H;
     long want = 256 / ((Cin / 64) * (Cout / 64));
     if (want < 1) want = 1;
     long r = (rows + want - 1) / want;
     r = (r + 1) / 2 * 2;                                       // whole row pairs
-    *rpb = (int)r;
-    *nb = (int)((rows + r - 1) / r);
-    return true;
+    return {(int)((rows + r - 1) / r), (int)r};
 }
 
-static inline bool wgrad9_choose(int B, int H, int W, int Cin, int Cout, int taps, int dtype, int* nb, int* rpb, bool pair = false) {
+static inline WgradBands wgrad9_choose(int B, int H, int W, int Cin, int Cout, int taps, int dtype, bool pair = false) {
     // which layers: one of the two channel counts 64 (the ring kernel's 64-wide tiles), or both <= 128 at W = 32 -- in-process A/B, B = 64:
     // 32^2 128->128 40.9 -> 36.1 us; the 128-wide layers at 64^2 / 128^2 are 5-7 % SLOWER here than on the ring kernel's 128 x 128 tiles
     const bool need64 = W > 32;
     const int creal = Cin / wg9_pair_div(pair);
     if (dtype != MU_F16 || taps != 9 || W % 32 || W > 128 || Cin % 64 || Cout % 64 || (need64 && !(creal == 64 || Cout == 64)) ||
-        creal > 128 || Cout > 128) return false;
+        creal > 128 || Cout > 128) return {0, 0};
     const long rows = (long)B * H;
     long want = 256 / ((Cin / 64) * (Cout / 64));          // one block per CU (W <= 64: 66 KB of LDS, two would fit)
     if (want > rows) want = rows;
     if (want < 1) want = 1;
-    *rpb = (int)((rows + want - 1) / want);
-    *nb = (int)((rows + *rpb - 1) / *rpb);
-    return true;
+    const int rpb = (int)((rows + want - 1) / want);
+    return {(int)((rows + rpb - 1) / rpb), rpb};
 }
 
+// One workspace size per layer shape, whatever dtype, cin_valid and bias the calls then come with: the most slabs any family's plan
+// helper asks for on these dimensions -- the helpers conv_wgrad_pick reads, whether or not it would pick that family -- plus two terms
+// that are reserved rather than derived.
 static long wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cout, int taps, bool pair) {
-    int bco, bci, nsplit; long pps;
-    wgrad_tile(Cin, Cout, &bco, &bci);
-    wgrad_plan((long)B * H * W, Cin, Cout, taps, bco, bci, &nsplit, &pps);
-    long a = (long)nsplit * taps * Cout * Cin * sizeof(float);
-    wgrad_tile(Cin, Cout, &bco, &bci, taps, true);          // the fp16 plan of a 1x1 layer may use more pixel ranges
-    wgrad_plan((long)B * H * W, Cin, Cout, taps, bco, bci, &nsplit, &pps);
-    if ((long)nsplit * taps * Cout * Cin * (long)sizeof(float) > a) a = (long)nsplit * taps * Cout * Cin * sizeof(float);
-    if (taps == 1) a += (long)nsplit * Cout * (long)sizeof(float);          // bias partials of mu_conv_wgrad_bias
-    int tco, tci;
-    if (wgrad3_choose(H, W, Cin, Cout, taps, MU_F16, &tco, &tci)) {
-        wgrad3_plan((long)B * H * W, Cin, Cout, tco, tci, &nsplit, &pps);
-        long b = (long)nsplit * taps * Cout * Cin * sizeof(float);
-        if (b > a) a = b;
+    const long M = (long)B * H * W;
+    long slabs = wgrad_plan(M, Cin, Cout, taps, wgrad_tile(Cin, Cout)).nsplit;
+    const int nsplit16 = wgrad_plan(M, Cin, Cout, taps, wgrad_tile(Cin, Cout, taps, true)).nsplit;      // the fp16 plan of a 1x1 layer may use more pixel ranges
+    if (nsplit16 > slabs) slabs = nsplit16;
+    if (const int tile = wgrad3_choose(H, W, Cin, Cout, taps, MU_F16)) {
+        const int n3 = wgrad3_plan(M, Cin, Cout, tile).nsplit;
+        if (n3 > slabs) slabs = n3;
     }
-    int nb9, rpb9;
-    if (wgrad9_choose(B, H, W, Cin, Cout, taps, MU_F16, &nb9, &rpb9, pair) || wgrad9_w16_choose(B, H, W, Cin, Cout, taps, MU_F16, &nb9, &rpb9, pair)) {
-        long b = (long)nb9 * taps * Cout * Cin * sizeof(float);
-        if (b > a) a = b;
-    }
-    if (taps == 9 && Cin == 32) {                       // first-layer kernel (<= 4 valid input channels): [blocks][9][Cout][4]
-        long c = (long)MU_RGB_MAXBLK * 9 * Cout * 4 * sizeof(float);
-        if (c > a) a = c;
-    }
+    WgradBands b9 = wgrad9_choose(B, H, W, Cin, Cout, taps, MU_F16, pair);
+    if (!b9.nb) b9 = wgrad9_w16_choose(B, H, W, Cin, Cout, taps, MU_F16, pair);
+    if (b9.nb > slabs) slabs = b9.nb;
+    long a = slab_bytes(slabs, taps, Cout, Cin);
+    // reserved: the bias partials of mu_conv_wgrad_bias -- one row of Cout per pixel range of the fp16 plan -- behind the slabs of every
+    // 1x1 layer, whether or not that layer has the wide tiles that write them
+    if (taps == 1) a += (long)nsplit16 * Cout * (long)sizeof(float);
+    // reserved: the first-layer kernels' [MU_RGB_MAXBLK][9][Cout][4] for every 3x3 layer of 32 padded input channels, whether or not
+    // cin_valid <= 3 will pick them (they size their grid from what they are given, see ConvWgradPlan)
+    if (taps == 9 && Cin == 32 && slab_bytes(MU_RGB_MAXBLK, 9, Cout, 4) > a) a = slab_bytes(MU_RGB_MAXBLK, 9, Cout, 4);
     return a;
 }
 
@@ -3435,41 +3452,11 @@ extern "C" long mu_conv_wgrad_workspace_bytes(int B, int H, int W, int Cin, int 
     return wgrad_workspace_bytes(B, H, W, Cin, Cout, taps, false);
 }
 
-template <typename T, int TAPS>
-static int wgrad_launch(const T* x, const T* dy, float* part, int B, int H, int W, int Cin, int Cout, long x_ld, long dy_ld, int bt,
-                        int nsplit, long pps, hipStream_t st, int bci = 0, float* bias_part = nullptr) {
-    if constexpr (TAPS == 1 && (sizeof(T) == 2 || std::is_same<T, xf32>::value)) {
-        if (wgrad_is_wide(bt)) {                            // bt x bci tiles (bci = 64 or 128)
-            const int grid = ((Cout + bt - 1) / bt) * ((Cin + bci - 1) / bci) * nsplit;
-#define WG1(TM_, TN_)                                                                                                                  \
-    do {                                                                                                                               \
-        if (bias_part) conv_wgrad_kernel<T, TM_, TN_, 2, 1, true><<<grid, 256, 0, st>>>(x, dy, part, B, H, W, Cin, Cout, x_ld, dy_ld, nsplit, pps, bias_part); \
-        else conv_wgrad_kernel<T, TM_, TN_, 2, 1><<<grid, 256, 0, st>>>(x, dy, part, B, H, W, Cin, Cout, x_ld, dy_ld, nsplit, pps);    \
-    } while (0)
-            if (bt == 192 && bci == 64) WG1(6, 2);
-            else if (bt == 192) WG1(6, 4);
-            else if (bci == 64) WG1(5, 2);
-            else WG1(5, 4);
-#undef WG1
-            return MU_OK;
-        }
-    }
-    if (bias_part) return MU_ERR_SHAPE;
-    const int nt = ((Cout + bt - 1) / bt) * ((Cin + bt - 1) / bt);
-    const int grid = TAPS * nt * nsplit;
-    if (bt == 128) conv_wgrad_kernel<T, 4, 4, 2, TAPS><<<grid, 256, 0, st>>>(x, dy, part, B, H, W, Cin, Cout, x_ld, dy_ld, nsplit, pps);
-    else if (bt == 64) conv_wgrad_kernel<T, 2, 2, 2, TAPS><<<grid, 256, 0, st>>>(x, dy, part, B, H, W, Cin, Cout, x_ld, dy_ld, nsplit, pps);
-    else conv_wgrad_kernel<T, 1, 1, 2, TAPS><<<grid, 256, 0, st>>>(x, dy, part, B, H, W, Cin, Cout, x_ld, dy_ld, nsplit, pps);
-    return MU_OK;
-}
-
 extern "C" int mu_conv_wgrad_bias_supported(int Cin, int Cout, int taps, int dtype) {
-    int bco, bci;
-    wgrad_tile(Cin, Cout, &bco, &bci, taps, dtype == MU_F16);
-    return dtype == MU_F16 && taps == 1 && Cin % 32 == 0 && Cout % 32 == 0 && wgrad_is_wide(bco) ? 1 : 0;
+    return dtype == MU_F16 && taps == 1 && Cin % 32 == 0 && Cout % 32 == 0 && wgrad_is_wide(wgrad_tile(Cin, Cout, taps, dtype == MU_F16).bco) ? 1 : 0;
 }
 
-// The weight-gradient plan: which kernel family and variant conv_wgrad_impl launches, with the split plan it launches it with.
+// The weight-gradient plan: which kernel conv_wgrad_impl launches, with the split it launches it with and the workspace it writes.
 // Ids (mu_conv_wgrad_plan / mu_conv_wgrad_bias_plan): the first-layer kernels, the nine-tap band kernels, the three-tap ring kernel by
 // tile and row staging, the wide 1x1 tiles (with bias partials: + WG_WIDE_BIAS), the generic square tiles.
 enum ConvWgradKernel {
@@ -3489,178 +3476,189 @@ static const int WG_WIDE_BIAS = WG_WIDE192_CI64_BIAS - WG_WIDE192_CI64;
 struct ConvWgradPlan {
     int id;
     int err;                // id == WG_NONE: the status conv_wgrad_impl returns
-    int bco, bci, nsplit;   // generic / wide tiles (wgrad_tile, wgrad_plan) -- nsplit: the three-tap kernel's count when that one is picked
-    long pps;
-    int tco, tci;           // three-tap kernel
-    int nb9, rpb9;          // nine-tap band kernels
+    int nsplit;             // pixel ranges (tile kernels) or row bands (nine-tap kernels) of the launch
+    long pps;               // pixels per range (tile kernels)
+    int rpb;                // image rows per band (nine-tap kernels)
+    // What the kernel writes: `slabs` fp32 slabs [taps][Cout][slab_cin], then `bias_rows` rows of Cout bias partials.  The first-layer
+    // family is the special case: its slabs are [9][Cout][4] and it runs with as many blocks as slabs fit into ws_bytes (up to
+    // MU_RGB_MAXBLK and the image rows), so its plan states the one slab it needs at least.
+    int slabs, slab_cin, bias_rows;
+    long bytes(int taps, int Cout) const { return slab_bytes(slabs, taps, Cout, slab_cin) + (long)bias_rows * Cout * (long)sizeof(float); }
 };
 static ConvWgradPlan conv_wgrad_pick(int B, int H, int W, int Cin, int Cout, int taps, int cin_valid, int dtype, bool pair, bool with_bias) {
-    ConvWgradPlan p = {WG_NONE, MU_ERR_ARG, 0, 0, 0, 0, 0, 0, 0, 0};
+    ConvWgradPlan p = {WG_NONE, MU_ERR_ARG, 0, 0, 0, 0, Cin, 0};
+    const long M = (long)B * H * W;
     // (fp32x: the wide 160-channel tile of the class head as well -- 32 x 32 tiles otherwise; the 192-wide q/k/v tiles stay fp16-only:
     //  64 x 64 tiles serve those layers)
-    wgrad_tile(Cin, Cout, &p.bco, &p.bci, taps, dtype == MU_F16 || (dtype == MU_F32X && Cout == 160));
-    wgrad_plan((long)B * H * W, Cin, Cout, taps, p.bco, p.bci, &p.nsplit, &p.pps);
+    const WgradTile tile = wgrad_tile(Cin, Cout, taps, dtype == MU_F16 || (dtype == MU_F32X && Cout == 160));
+    const WgradSplit split = wgrad_plan(M, Cin, Cout, taps, tile);
+    auto picked = [&p](int id, int nsplit, long pps = 0, int rpb = 0) {
+        p.id = id, p.nsplit = p.slabs = nsplit, p.pps = pps, p.rpb = rpb;
+        return p;
+    };
     if (taps == 9 && cin_valid <= 3 && Cout % 64 == 0 && W <= MU_RGB_MAXW && (dtype == MU_F16 || dtype == MU_F32 || dtype == MU_F32X)) {
-        if (dtype == MU_F16 && W % 32 == 0) p.id = WG_RGB2_NPT1 + (W / 32 > 8 ? 8 : W / 32) - 1;
-        else p.id = WG_RGB_FMA;
-        return p;
+        p.slab_cin = 4;
+        return picked(dtype == MU_F16 && W % 32 == 0 ? WG_RGB2_NPT1 + (W / 32 > 8 ? 8 : W / 32) - 1 : WG_RGB_FMA, 1);
     }
-    if (wgrad9_choose(B, H, W, Cin, Cout, taps, dtype, &p.nb9, &p.rpb9, pair)) {
-        p.id = WG_WG9_NPT1 + (W / 32 > 4 ? 4 : W / 32) - 1;
-        p.nsplit = p.nb9;
-        return p;
-    }
-    if (wgrad9_w16_choose(B, H, W, Cin, Cout, taps, dtype, &p.nb9, &p.rpb9, pair)) {
-        p.id = WG_WG9_W16;
-        p.nsplit = p.nb9;
-        return p;
-    }
-    if (wgrad3_choose(H, W, Cin, Cout, taps, dtype, &p.tco, &p.tci)) {
-        wgrad3_plan((long)B * H * W, Cin, Cout, p.tco, p.tci, &p.nsplit, &p.pps);
+    if (const WgradBands b = wgrad9_choose(B, H, W, Cin, Cout, taps, dtype, pair); b.nb) return picked(WG_WG9_NPT1 + (W / 32 > 4 ? 4 : W / 32) - 1, b.nb, 0, b.rpb);
+    if (const WgradBands b = wgrad9_w16_choose(B, H, W, Cin, Cout, taps, dtype, pair); b.nb) return picked(WG_WG9_W16, b.nb, 0, b.rpb);
+    if (const int t3 = wgrad3_choose(H, W, Cin, Cout, taps, dtype)) {
+        const WgradSplit s3 = wgrad3_plan(M, Cin, Cout, t3);
         const bool two_row32 = W == 32 && H % 2 == 0, flat64 = W % 64 == 0;
-        if (p.tco == 128)
-            p.id = W == 16 ? WG_WG3_128_W16 : two_row32 ? WG_WG3_128_ROWS2 : flat64 ? WG_WG3_128_FLAT64 : WG_WG3_128;
-        else p.id = W == 16 ? WG_WG3_64_W16 : two_row32 ? WG_WG3_64_ROWS2 : flat64 ? WG_WG3_64_FLAT64 : WG_WG3_64;
-        return p;
+        if (t3 == 128) return picked(W == 16 ? WG_WG3_128_W16 : two_row32 ? WG_WG3_128_ROWS2 : flat64 ? WG_WG3_128_FLAT64 : WG_WG3_128, s3.nsplit, s3.pps);
+        return picked(W == 16 ? WG_WG3_64_W16 : two_row32 ? WG_WG3_64_ROWS2 : flat64 ? WG_WG3_64_FLAT64 : WG_WG3_64, s3.nsplit, s3.pps);
     }
     if (dtype != MU_F16 && dtype != MU_F32 && dtype != MU_F32X) return p;
     // (3x3 layers of the fp32x mode: mu_conv_wgrad_h -- fp16-pair input, one scaled fp16 dy; only the <= 3-channel first layer, served above on
     //  plain operands, comes through here with taps = 9)
     if (dtype == MU_F32X && taps == 9) return p;
-    const bool wide_ok = taps == 1 && (dtype == MU_F16 || dtype == MU_F32X);      // (the types wgrad_launch has wide tiles for)
-    if (wide_ok && wgrad_is_wide(p.bco)) {
-        p.id = (p.bco == 192 ? (p.bci == 64 ? WG_WIDE192_CI64 : WG_WIDE192_CI128) : (p.bci == 64 ? WG_WIDE160_CI64 : WG_WIDE160_CI128)) +
-               (with_bias ? WG_WIDE_BIAS : 0);
-        return p;
+    const bool wide_ok = taps == 1 && (dtype == MU_F16 || dtype == MU_F32X);      // (the types wgrad_tiles_launch has wide tiles for)
+    if (wide_ok && wgrad_is_wide(tile.bco)) {
+        if (with_bias) p.bias_rows = split.nsplit;
+        return picked((tile.bco == 192 ? (tile.bci == 64 ? WG_WIDE192_CI64 : WG_WIDE192_CI128) : (tile.bci == 64 ? WG_WIDE160_CI64 : WG_WIDE160_CI128)) +
+                          (with_bias ? WG_WIDE_BIAS : 0), split.nsplit, split.pps);
     }
     if (with_bias) { p.err = MU_ERR_SHAPE; return p; }
-    p.id = p.bco == 128 ? WG_GEN128 : p.bco == 64 ? WG_GEN64 : WG_GEN32;
-    return p;
+    return picked(tile.bco == 128 ? WG_GEN128 : tile.bco == 64 ? WG_GEN64 : WG_GEN32, split.nsplit, split.pps);
 }
 
-// pair_I > 0 (mu_conv_wgrad_h): x is the 16-bit view of a chunk-encoded fp32x input (Cin = 2 x its channels), dy the scaled fp16 gradient;
-// the slabs are reduced pairwise into dw_oihw[cout_valid][pair_I][taps] and multiplied by oscale[1]
-static int conv_wgrad_impl(const void* x, const void* dy, float* dw_oihw, float* db, int B, int H, int W, int Cin, int Cout, int taps,
-                           int cin_valid, int cout_valid, long x_ld, long dy_ld, void* workspace, long ws_bytes, int dtype,
-                           void* stream, int pair_I = 0, const float* oscale = nullptr) {
-    if (!x || !dy || !dw_oihw || !workspace || B <= 0 || H <= 0 || W <= 0) return MU_ERR_ARG;
-    if (db && !mu_conv_wgrad_bias_supported(Cin, Cout, taps, dtype)) return MU_ERR_SHAPE;
-    if (Cin % 32 || Cout % 32 || x_ld < Cin || dy_ld < Cout || x_ld % 8 || dy_ld % 8) return MU_ERR_SHAPE;
-    if (cin_valid <= 0 || cin_valid > Cin || cout_valid <= 0 || cout_valid > Cout) return MU_ERR_ARG;
-    if (taps != 1 && taps != 9) return MU_ERR_ARG;
-    const ConvWgradPlan plan = conv_wgrad_pick(B, H, W, Cin, Cout, taps, cin_valid, dtype, pair_I > 0, db != nullptr);
-    const int bco = plan.bco, bci = plan.bci, tco = plan.tco, tci = plan.tci, nb9 = plan.nb9, rpb9 = plan.rpb9, nsplit = plan.nsplit;
-    const long pps = plan.pps;
-    hipStream_t st = (hipStream_t)stream;
-    float* part = (float*)workspace;
-    const h16 *xh = (const h16*)x, *dyh = (const h16*)dy;
-    switch (plan.id) {
-    case WG_NONE:
-        return plan.err;
-    case WG_RGB_FMA:
-    case WG_RGB2_NPT1: case WG_RGB2_NPT2: case WG_RGB2_NPT3: case WG_RGB2_NPT4:
-    case WG_RGB2_NPT5: case WG_RGB2_NPT6: case WG_RGB2_NPT7: case WG_RGB2_NPT8: {
-        // (plain-FMA kernel: the fp32x mode runs it as fp32)
-        long nb = ws_bytes / ((long)9 * Cout * 4 * (long)sizeof(float));
-        if (nb > MU_RGB_MAXBLK) nb = MU_RGB_MAXBLK;
-        if (nb > (long)B * H) nb = (long)B * H;
-        if (nb < 1) return MU_ERR_WORKSPACE;
-        dim3 grid((int)nb, Cout / 64);
-        if (plan.id != WG_RGB_FMA) {
-            // matrix-core form: a band of consecutive image rows per block (the grid covers the rows exactly: an idle block writes a zero slab)
-            if (nb > 768) nb = 768;                            // three 45 KB blocks per CU: one round
-            const int rpb = (int)(((long)B * H + nb - 1) / nb);
-            nb = ((long)B * H + rpb - 1) / rpb;
-            grid.x = (int)nb;
-            const size_t lds = ((size_t)2 * W * MU_RGB2_DYS + 5 * (size_t)(W + 2) * 4) * sizeof(h16);
-            const size_t lds_red = (size_t)4 * 64 * 16 * sizeof(float);
-#define RGB2(NPT) wgrad_rgb2_kernel<NPT><<<grid, 256, lds > lds_red ? lds : lds_red, st>>>(xh, dyh, part, B, H, W, Cout, x_ld, dy_ld, rpb)
-            switch (plan.id) {
-                case WG_RGB2_NPT1: RGB2(1); break; case WG_RGB2_NPT2: RGB2(2); break; case WG_RGB2_NPT3: RGB2(3); break;
-                case WG_RGB2_NPT4: RGB2(4); break; case WG_RGB2_NPT5: RGB2(5); break; case WG_RGB2_NPT6: RGB2(6); break;
-                case WG_RGB2_NPT7: RGB2(7); break; default: RGB2(8); break;
-            }
-#undef RGB2
-        }
-        else if (dtype == MU_F16) wgrad_rgb_kernel<h16><<<grid, 256, 0, st>>>(xh, dyh, part, B, H, W, Cout, cin_valid, x_ld, dy_ld);
-        else wgrad_rgb_kernel<float><<<grid, 256, 0, st>>>((const float*)x, (const float*)dy, part, B, H, W, Cout, cin_valid, x_ld, dy_ld);
-        const long n = (long)cout_valid * cin_valid * 9;
-        const long nblk = (n + 63) / 64;
-        wgrad_reduce_kernel<4><<<(int)(nblk > 4096 ? 4096 : nblk), 256, 0, st>>>(part, dw_oihw, (int)nb, 9, Cout, 4, cout_valid, cin_valid);
-        MU_CHECK_LAUNCH();
-        return MU_OK;
-    }
-    case WG_WG9_NPT1: case WG_WG9_NPT2: case WG_WG9_NPT3: case WG_WG9_NPT4: {
-        if (ws_bytes < (long)nb9 * taps * Cout * Cin * (long)sizeof(float)) return MU_ERR_WORKSPACE;
-        const dim3 grid9(nb9, Cout / 64, Cin / 64);
-#define WG9(NPT) conv_wgrad9_kernel<NPT><<<grid9, 256, 0, st>>>(xh, dyh, part, B, H, W, Cin, Cout, x_ld, dy_ld, rpb9)
-        switch (plan.id) { case WG_WG9_NPT1: WG9(1); break; case WG_WG9_NPT2: WG9(2); break; case WG_WG9_NPT3: WG9(3); break; default: WG9(4); break; }
-#undef WG9
-        break;
-    }
-    case WG_WG9_W16:
-        if (ws_bytes < (long)nb9 * taps * Cout * Cin * (long)sizeof(float)) return MU_ERR_WORKSPACE;
-        conv_wgrad9_w16_kernel<<<dim3(nb9, Cout / 64, Cin / 64), 256, 0, st>>>(xh, dyh, part, B, H, Cin, Cout, x_ld, dy_ld, rpb9);
-        break;
-    case WG_WG3_128_W16: case WG_WG3_128_ROWS2: case WG_WG3_128_FLAT64: case WG_WG3_128:
-    case WG_WG3_64_W16: case WG_WG3_64_ROWS2: case WG_WG3_64_FLAT64: case WG_WG3_64: {
-        if (ws_bytes < (long)nsplit * taps * Cout * Cin * (long)sizeof(float)) return MU_ERR_WORKSPACE;
-        const int grid = 3 * (Cout / tco) * (Cin / tci) * nsplit;
-#define WG3(...) conv_wgrad3_kernel<h16, __VA_ARGS__><<<grid, tco == 128 ? 512 : 256, 0, st>>>(xh, dyh, part, B, H, W, Cin, Cout, x_ld, dy_ld, nsplit, pps)
-        switch (plan.id) {
-        // 128 x 128: 8 waves, 64x32 tile x 3 taps per wave (96 accumulators): 2 waves/SIMD
-        case WG_WG3_128_W16: WG3(4, 2, 2, 8, true); break;
-        case WG_WG3_128_ROWS2: WG3(4, 2, 2, 8, true, 2); break;             // (the ping-pong schedule at W = 32: +2.6 % slower)
-        case WG_WG3_128_FLAT64: WG3(4, 2, 2, 8, false, 2, true); break;
-        case WG_WG3_128: WG3(4, 2, 2, 8); break;
-        case WG_WG3_64_W16: WG3(2, 2, 2, 4, true); break;
-        case WG_WG3_64_ROWS2: WG3(2, 2, 2, 4, true, 2); break;
-        case WG_WG3_64_FLAT64: WG3(2, 2, 2, 4, false, 2); break;
-        default: WG3(2, 2, 2); break;
-        }
-#undef WG3
-        break;
-    }
-    default: {          // wide 1x1 tiles and the generic square tiles (wgrad_launch reads the tile from bco / bci)
-        if (ws_bytes < (long)nsplit * taps * Cout * Cin * (long)sizeof(float)) return MU_ERR_WORKSPACE;
-        if (dtype == MU_F16) {
-            if (taps == 9) wgrad_launch<h16, 9>(xh, dyh, part, B, H, W, Cin, Cout, x_ld, dy_ld, bco, nsplit, pps, st);
-            else {
-                float* bias_part = db ? part + (long)nsplit * Cout * Cin : nullptr;
-                if (db && ws_bytes < ((long)nsplit * Cout * Cin + (long)nsplit * Cout) * (long)sizeof(float)) return MU_ERR_WORKSPACE;
-                int rc = wgrad_launch<h16, 1>(xh, dyh, part, B, H, W, Cin, Cout, x_ld, dy_ld, bco, nsplit, pps, st, bci, bias_part);
-                if (rc) return rc;
-                if (db) wgrad_bias_reduce_kernel<<<mu_cdiv(cout_valid, 16), 256, 0, st>>>(bias_part, nsplit, Cout, cout_valid, db);
-            }
-        } else if (dtype == MU_F32) {
-            if (taps == 9) wgrad_launch<float, 9>((const float*)x, (const float*)dy, part, B, H, W, Cin, Cout, x_ld, dy_ld, bco, nsplit, pps, st);
-            else wgrad_launch<float, 1>((const float*)x, (const float*)dy, part, B, H, W, Cin, Cout, x_ld, dy_ld, bco, nsplit, pps, st);
-        } else {
-            wgrad_launch<xf32, 1>((const xf32*)x, (const xf32*)dy, part, B, H, W, Cin, Cout, x_ld, dy_ld, bco, nsplit, pps, st, bci);
-        }
-        break;
-    }
-    }
-    if (pair_I > 0) {
-        const long n2 = (long)cout_valid * pair_I * taps;
-        if (nsplit >= 16) {
-            const long nb = (n2 + 63) / 64;
-            wgrad_reduce_pair_kernel<4><<<(int)(nb > 4096 ? 4096 : nb), 256, 0, st>>>(part, dw_oihw, nsplit, taps, Cout, Cin, cout_valid, pair_I, oscale);
-        } else {
-            const long nb = (n2 + 255) / 256;
-            wgrad_reduce_pair_kernel<1><<<(int)(nb > 2048 ? 2048 : nb), 256, 0, st>>>(part, dw_oihw, nsplit, taps, Cout, Cin, cout_valid, pair_I, oscale);
-        }
-        MU_CHECK_LAUNCH();
-        return MU_OK;
-    }
-    const long n = (long)cout_valid * cin_valid * taps;
-    if (nsplit >= 16) {
-        const long nb = (n + 63) / 64;
-        wgrad_reduce_kernel<4><<<(int)(nb > 4096 ? 4096 : nb), 256, 0, st>>>(part, dw_oihw, nsplit, taps, Cout, Cin, cout_valid, cin_valid, oscale);
+// One call of the weight gradient.  pair_I > 0 (mu_conv_wgrad_h): x is the 16-bit view of a chunk-encoded fp32x input (Cin = 2 x its
+// channels), dy the scaled fp16 gradient; the slabs are reduced pairwise into dw_oihw[cout_valid][pair_I][taps] and multiplied by oscale[1]
+struct ConvWgrad {
+    const void *x, *dy;
+    float *dw_oihw, *db;
+    int B, H, W, Cin, Cout, taps, cin_valid, cout_valid;
+    long x_ld, dy_ld;
+    void* workspace;
+    long ws_bytes;
+    int dtype;
+    void* stream;
+    int pair_I = 0;
+    const float* oscale = nullptr;
+};
+
+// The launchers of conv_wgrad_impl: `part` = the workspace, the plan as picked.  The template arguments are the kernel's.
+// First-layer family: NPT = 0 the plain-FMA kernel (the fp32x mode runs it as fp32), else the matrix-core form at W = 32 NPT -- a band
+// of consecutive image rows per block (the grid covers the rows exactly: an idle block writes a zero slab).  Returns the slabs written.
+template <int NPT>
+static int wgrad_rgb_launch(const ConvWgrad& a, float* part) {
+    const int B = a.B, H = a.H, W = a.W, Cout = a.Cout;
+    hipStream_t st = (hipStream_t)a.stream;
+    long nb = a.ws_bytes / slab_bytes(1, 9, Cout, 4);
+    if (nb > MU_RGB_MAXBLK) nb = MU_RGB_MAXBLK;
+    if (nb > (long)B * H) nb = (long)B * H;
+    if constexpr (NPT > 0) {
+        if (nb > 768) nb = 768;                            // three 45 KB blocks per CU: one round
+        const int rpb = (int)(((long)B * H + nb - 1) / nb);
+        nb = ((long)B * H + rpb - 1) / rpb;
+        const size_t lds = ((size_t)2 * W * MU_RGB2_DYS + 5 * (size_t)(W + 2) * 4) * sizeof(h16);
+        const size_t lds_red = (size_t)4 * 64 * 16 * sizeof(float);
+        wgrad_rgb2_kernel<NPT><<<dim3((int)nb, Cout / 64), 256, lds > lds_red ? lds : lds_red, st>>>((const h16*)a.x, (const h16*)a.dy, part, B, H, W, Cout,
+                                                                                                   a.x_ld, a.dy_ld, rpb);
+    } else if (a.dtype == MU_F16) {
+        wgrad_rgb_kernel<h16><<<dim3((int)nb, Cout / 64), 256, 0, st>>>((const h16*)a.x, (const h16*)a.dy, part, B, H, W, Cout, a.cin_valid, a.x_ld, a.dy_ld);
     } else {
-        const long nb = (n + 255) / 256;
-        wgrad_reduce_kernel<1><<<(int)(nb > 2048 ? 2048 : nb), 256, 0, st>>>(part, dw_oihw, nsplit, taps, Cout, Cin, cout_valid, cin_valid, oscale);
+        wgrad_rgb_kernel<float><<<dim3((int)nb, Cout / 64), 256, 0, st>>>((const float*)a.x, (const float*)a.dy, part, B, H, W, Cout, a.cin_valid, a.x_ld, a.dy_ld);
     }
+    return (int)nb;
+}
+template <int NPT>
+static void wgrad9_launch(const ConvWgrad& a, const ConvWgradPlan& p, float* part) {
+    conv_wgrad9_kernel<NPT><<<dim3(p.nsplit, a.Cout / 64, a.Cin / 64), 256, 0, (hipStream_t)a.stream>>>((const h16*)a.x, (const h16*)a.dy, part, a.B, a.H, a.W,
+                                                                                                       a.Cin, a.Cout, a.x_ld, a.dy_ld, p.rpb);
+}
+// (8 waves: the 128 x 128 tile, 64x32 x 3 taps per wave (96 accumulators), 2 waves/SIMD; 4 waves: 64 x 64)
+template <int TM, int TN, int WR, int NWV = 4, bool W16 = false, int SPS = 1, bool PP = false>
+static void wgrad3_launch(const ConvWgrad& a, const ConvWgradPlan& p, float* part) {
+    constexpr int TILE = NWV == 8 ? 128 : 64;
+    conv_wgrad3_kernel<h16, TM, TN, WR, NWV, W16, SPS, PP><<<3 * (a.Cout / TILE) * (a.Cin / TILE) * p.nsplit, NWV * 64, 0, (hipStream_t)a.stream>>>(
+        (const h16*)a.x, (const h16*)a.dy, part, a.B, a.H, a.W, a.Cin, a.Cout, a.x_ld, a.dy_ld, p.nsplit, p.pps);
+}
+// Tiles of TM x TN 32-channel blocks, one tap per block: the square tiles for every type, the wide ones (1x1 layers) for fp16 and the
+// bf16 pairs; BIAS: bias partials behind the slabs.  (The fp16-pair type has no instantiation: its 3x3 layers are mu_conv_wgrad_h.)
+template <int TM, int TN, bool BIAS = false>
+static void wgrad_tiles_launch(const ConvWgrad& a, const ConvWgradPlan& p, float* part) {
+    with_conv_type(a.dtype, a.taps, [&](auto t, auto tc) -> int {
+        using T = decltype(t);
+        constexpr int TAPS = decltype(tc)::value;
+        if constexpr (!std::is_same<T, xh32>::value && (TM == TN || (TAPS == 1 && !std::is_same<T, float>::value))) {
+            const int grid = TAPS * mu_cdiv(a.Cout, 32 * TM) * mu_cdiv(a.Cin, 32 * TN) * p.nsplit;
+            float* bias_part = BIAS ? part + slab_bytes(p.slabs, TAPS, a.Cout, a.Cin) / sizeof(float) : nullptr;
+            conv_wgrad_kernel<T, TM, TN, 2, TAPS, BIAS><<<grid, 256, 0, (hipStream_t)a.stream>>>((const T*)a.x, (const T*)a.dy, part, a.B, a.H, a.W, a.Cin, a.Cout,
+                                                                                                a.x_ld, a.dy_ld, p.nsplit, p.pps, bias_part);
+            if constexpr (BIAS) wgrad_bias_reduce_kernel<<<mu_cdiv(a.cout_valid, 16), 256, 0, (hipStream_t)a.stream>>>(bias_part, p.nsplit, a.Cout, a.cout_valid, a.db);
+        }
+        return MU_OK;
+    });
+}
+// dst[O][I][taps] = the sum of `nsplit` slabs [taps][Cout][Cin] (times oscale[1] where given).  lanes4: four k-lanes per element
+// (worth it from 16 slabs on); pair: the column pairs of mu_conv_wgrad_h (wgrad_reduce_pair_kernel).
+static void wgrad_reduce_launch(const float* part, float* dst, int nsplit, int taps, int Cout, int Cin, int O, int I, bool lanes4, bool pair,
+                                const float* oscale, hipStream_t st) {
+    const long n = (long)O * I * taps;
+    const int grid = lanes4 ? mu_grid(n, 64, 4096) : mu_grid(n, 256, 2048);
+    if (pair && lanes4) wgrad_reduce_pair_kernel<4><<<grid, 256, 0, st>>>(part, dst, nsplit, taps, Cout, Cin, O, I, oscale);
+    else if (pair) wgrad_reduce_pair_kernel<1><<<grid, 256, 0, st>>>(part, dst, nsplit, taps, Cout, Cin, O, I, oscale);
+    else if (lanes4) wgrad_reduce_kernel<4><<<grid, 256, 0, st>>>(part, dst, nsplit, taps, Cout, Cin, O, I, oscale);
+    else wgrad_reduce_kernel<1><<<grid, 256, 0, st>>>(part, dst, nsplit, taps, Cout, Cin, O, I, oscale);
+}
+
+// Refusal order: null pointers and non-positive sizes (MU_ERR_ARG), db on a shape without bias partials (MU_ERR_SHAPE, before taps is
+// looked at), channel counts and row strides (MU_ERR_SHAPE), the valid counts and taps (MU_ERR_ARG), what no kernel serves (the plan's
+// status), a workspace smaller than the plan writes (MU_ERR_WORKSPACE).  Then the plan's kernel, named by its id, and the slab reduce.
+static int conv_wgrad_impl(const ConvWgrad& a) {
+    const int Cin = a.Cin, Cout = a.Cout, taps = a.taps;
+    if (!a.x || !a.dy || !a.dw_oihw || !a.workspace || a.B <= 0 || a.H <= 0 || a.W <= 0) return MU_ERR_ARG;
+    if (a.db && !mu_conv_wgrad_bias_supported(Cin, Cout, taps, a.dtype)) return MU_ERR_SHAPE;
+    if (Cin % 32 || Cout % 32 || a.x_ld < Cin || a.dy_ld < Cout || a.x_ld % 8 || a.dy_ld % 8) return MU_ERR_SHAPE;
+    if (a.cin_valid <= 0 || a.cin_valid > Cin || a.cout_valid <= 0 || a.cout_valid > Cout) return MU_ERR_ARG;
+    if (taps != 1 && taps != 9) return MU_ERR_ARG;
+    const ConvWgradPlan p = conv_wgrad_pick(a.B, a.H, a.W, Cin, Cout, taps, a.cin_valid, a.dtype, a.pair_I > 0, a.db != nullptr);
+    if (p.id == WG_NONE) return p.err;
+    if (a.ws_bytes < p.bytes(taps, Cout)) return MU_ERR_WORKSPACE;
+    float* part = (float*)a.workspace;
+    int slabs = p.slabs;
+    switch (p.id) {
+    case WG_RGB_FMA: slabs = wgrad_rgb_launch<0>(a, part); break;
+    case WG_RGB2_NPT1: slabs = wgrad_rgb_launch<1>(a, part); break;
+    case WG_RGB2_NPT2: slabs = wgrad_rgb_launch<2>(a, part); break;
+    case WG_RGB2_NPT3: slabs = wgrad_rgb_launch<3>(a, part); break;
+    case WG_RGB2_NPT4: slabs = wgrad_rgb_launch<4>(a, part); break;
+    case WG_RGB2_NPT5: slabs = wgrad_rgb_launch<5>(a, part); break;
+    case WG_RGB2_NPT6: slabs = wgrad_rgb_launch<6>(a, part); break;
+    case WG_RGB2_NPT7: slabs = wgrad_rgb_launch<7>(a, part); break;
+    case WG_RGB2_NPT8: slabs = wgrad_rgb_launch<8>(a, part); break;
+    case WG_WG9_NPT1: wgrad9_launch<1>(a, p, part); break;
+    case WG_WG9_NPT2: wgrad9_launch<2>(a, p, part); break;
+    case WG_WG9_NPT3: wgrad9_launch<3>(a, p, part); break;
+    case WG_WG9_NPT4: wgrad9_launch<4>(a, p, part); break;
+    case WG_WG9_W16:
+        conv_wgrad9_w16_kernel<<<dim3(p.nsplit, Cout / 64, Cin / 64), 256, 0, (hipStream_t)a.stream>>>((const h16*)a.x, (const h16*)a.dy, part, a.B, a.H, Cin, Cout,
+                                                                                                      a.x_ld, a.dy_ld, p.rpb);
+        break;
+    case WG_WG3_128_W16: wgrad3_launch<4, 2, 2, 8, true>(a, p, part); break;
+    case WG_WG3_128_ROWS2: wgrad3_launch<4, 2, 2, 8, true, 2>(a, p, part); break;          // (the ping-pong schedule at W = 32: +2.6 % slower)
+    case WG_WG3_128_FLAT64: wgrad3_launch<4, 2, 2, 8, false, 2, true>(a, p, part); break;
+    case WG_WG3_128: wgrad3_launch<4, 2, 2, 8>(a, p, part); break;
+    case WG_WG3_64_W16: wgrad3_launch<2, 2, 2, 4, true>(a, p, part); break;
+    case WG_WG3_64_ROWS2: wgrad3_launch<2, 2, 2, 4, true, 2>(a, p, part); break;
+    case WG_WG3_64_FLAT64: wgrad3_launch<2, 2, 2, 4, false, 2>(a, p, part); break;
+    case WG_WG3_64: wgrad3_launch<2, 2, 2>(a, p, part); break;
+    case WG_WIDE192_CI64: wgrad_tiles_launch<6, 2>(a, p, part); break;
+    case WG_WIDE192_CI128: wgrad_tiles_launch<6, 4>(a, p, part); break;
+    case WG_WIDE160_CI64: wgrad_tiles_launch<5, 2>(a, p, part); break;
+    case WG_WIDE160_CI128: wgrad_tiles_launch<5, 4>(a, p, part); break;
+    case WG_WIDE192_CI64_BIAS: wgrad_tiles_launch<6, 2, true>(a, p, part); break;
+    case WG_WIDE192_CI128_BIAS: wgrad_tiles_launch<6, 4, true>(a, p, part); break;
+    case WG_WIDE160_CI64_BIAS: wgrad_tiles_launch<5, 2, true>(a, p, part); break;
+    case WG_WIDE160_CI128_BIAS: wgrad_tiles_launch<5, 4, true>(a, p, part); break;
+    case WG_GEN128: wgrad_tiles_launch<4, 4>(a, p, part); break;
+    case WG_GEN64: wgrad_tiles_launch<2, 2>(a, p, part); break;
+    case WG_GEN32: wgrad_tiles_launch<1, 1>(a, p, part); break;
+    }
+    // (the first-layer slabs always take the four-lane reduce)
+    wgrad_reduce_launch(part, a.dw_oihw, slabs, taps, Cout, p.slab_cin, a.cout_valid, a.pair_I > 0 ? a.pair_I : a.cin_valid, slabs >= 16 || p.id <= WG_RGB2_NPT8,
+                        a.pair_I > 0, a.oscale, (hipStream_t)a.stream);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
@@ -3711,8 +3709,7 @@ extern "C" const char* mu_conv_plan_name(int op, int id) {
 extern "C" int mu_conv_wgrad(const void* x, const void* dy, float* dw_oihw, int B, int H, int W, int Cin, int Cout, int taps,
                              int cin_valid, int cout_valid, long x_ld, long dy_ld, void* workspace, long ws_bytes, int dtype,
                              void* stream) {
-    return conv_wgrad_impl(x, dy, dw_oihw, nullptr, B, H, W, Cin, Cout, taps, cin_valid, cout_valid, x_ld, dy_ld, workspace, ws_bytes, dtype,
-                           stream);
+    return conv_wgrad_impl({x, dy, dw_oihw, nullptr, B, H, W, Cin, Cout, taps, cin_valid, cout_valid, x_ld, dy_ld, workspace, ws_bytes, dtype, stream});
 }
 
 // fp32x, 3x3 layers: the TWO-TERM weight gradient (round 6).  x: the layer's saved input, chunk-encoded fp16 pairs (mu_split_encode_h4 /
@@ -3726,8 +3723,8 @@ extern "C" int mu_conv_wgrad_h(const void* x, const void* dy_h, const float* dy_
                                int cin_valid, int cout_valid, long x_ld, long dy_ld, void* workspace, long ws_bytes, void* stream) {
     if (!dy_scale || cin_valid <= 3) return MU_ERR_ARG;      // (the <= 3-channel first layer is a plain-FMA kernel on plain operands: mu_conv_wgrad)
     if (Cin % 32 || cin_valid > Cin) return MU_ERR_SHAPE;
-    return conv_wgrad_impl(x, dy_h, dw_oihw, nullptr, B, H, W, 2 * Cin, Cout, 9, 2 * Cin, cout_valid, 2 * x_ld, dy_ld, workspace, ws_bytes, MU_F16,
-                           stream, cin_valid, dy_scale);
+    return conv_wgrad_impl({x, dy_h, dw_oihw, nullptr, B, H, W, 2 * Cin, Cout, 9, 2 * Cin, cout_valid, 2 * x_ld, dy_ld, workspace, ws_bytes, MU_F16, stream,
+                            cin_valid, dy_scale});
 }
 
 // The ONE-term form: x_h = the fp16 ROUNDING of the layer's input (rows of Cin halves, stride x_ld halves: the second output of
@@ -3738,13 +3735,13 @@ extern "C" int mu_conv_wgrad_h(const void* x, const void* dy_h, const float* dy_
 extern "C" int mu_conv_wgrad_h1(const void* x_h, const void* dy_h, const float* dy_scale, float* dw_oihw, int B, int H, int W, int Cin, int Cout,
                                 int cin_valid, int cout_valid, long x_ld, long dy_ld, void* workspace, long ws_bytes, void* stream) {
     if (!dy_scale || cin_valid <= 3) return MU_ERR_ARG;
-    return conv_wgrad_impl(x_h, dy_h, dw_oihw, nullptr, B, H, W, Cin, Cout, 9, cin_valid, cout_valid, x_ld, dy_ld, workspace, ws_bytes, MU_F16,
-                           stream, 0, dy_scale);
+    return conv_wgrad_impl({x_h, dy_h, dw_oihw, nullptr, B, H, W, Cin, Cout, 9, cin_valid, cout_valid, x_ld, dy_ld, workspace, ws_bytes, MU_F16, stream, 0,
+                            dy_scale});
 }
 
 extern "C" int mu_conv_wgrad_bias(const void* x, const void* dy, float* dw_oihw, float* db, int B, int H, int W, int Cin, int Cout,
                                   int taps, int cin_valid, int cout_valid, long x_ld, long dy_ld, void* workspace, long ws_bytes,
                                   int dtype, void* stream) {
     if (!db) return MU_ERR_ARG;
-    return conv_wgrad_impl(x, dy, dw_oihw, db, B, H, W, Cin, Cout, taps, cin_valid, cout_valid, x_ld, dy_ld, workspace, ws_bytes, dtype, stream);
+    return conv_wgrad_impl({x, dy, dw_oihw, db, B, H, W, Cin, Cout, taps, cin_valid, cout_valid, x_ld, dy_ld, workspace, ws_bytes, dtype, stream});
 }

@@ -14,6 +14,10 @@ Cases: tests/_conv_cases.LAYERS, one pytest id per (entry, dtype, kernel, shape)
 queries.  Memory discipline in every case: outputs pre-filled with NaN, row padding (ld - C columns) and 4 KiB guard bands before and
 after every output and the workspace hold a sentinel that must survive, workspaces have exactly the queried size and start as NaN.
 
+Behind the cases: the refusals of every mu_conv_* entry point (the documented status for each fault, one at a time, with every output
+and guard band bit-unchanged) and the workspace boundary of every weight-gradient family (the smallest ws_bytes each accepts, found
+by bisection inside a real buffer of the queried size and pinned in WS_FAMILIES, with the exact dW at exactly that size).
+
 The module mark is per test (not `pytestmark`): the comparator self-tests at the end are CPU tests."""
 import functools
 import math
@@ -372,6 +376,258 @@ def test_exact(entry, dn, name, kernel):
         run_wgrad_h(k, kernel, entry == "wgrad_h1")
     else:
         raise AssertionError(entry)
+
+
+# ------------------------------------------------------------------------------------------------
+# refusals: the documented status, and nothing written.  Every buffer is real and sized for the valid call.
+# ------------------------------------------------------------------------------------------------
+ARG, SHAPE, WORKSPACE = -1, -2, -4
+ENTRY_ARGS = {
+    "mu_conv_fwd": "x w bias y B H W Cin Cout taps x_ld y_ld dtype st",
+    "mu_conv_fwd_stats": "x w bias y B H W Cin Cout taps x_ld y_ld dtype stat st",
+    "mu_conv_fwd_fused": "x w scale bias res act y B H W Cin Cout taps x_ld y_ld dtype st",
+    "mu_conv_dgrad_h": "x w dys y B H W Cin Cout x_ld y_ld st",
+    "mu_conv1x1_fwd_add": "x w res y M Cin Cout x_ld y_ld dtype st",
+    "mu_conv1x1_fwd_enc_h": "x w bias y M Cin Cout x_ld y_ld st",
+    "mu_conv_wgrad": "x dy dw B H W Cin Cout taps cin_valid cout_valid x_ld y_ld ws ws_bytes dtype st",
+    "mu_conv_wgrad_bias": "x dy dw db B H W Cin Cout taps cin_valid cout_valid x_ld y_ld ws ws_bytes dtype st",
+    "mu_conv_wgrad_h": "x dy dys dw B H W Cin Cout cin_valid cout_valid x_ld y_ld ws ws_bytes st",
+    "mu_conv_wgrad_h1": "x dy dys dw B H W Cin Cout cin_valid cout_valid x_ld y_ld ws ws_bytes st",
+}
+
+
+class EntryCall:
+    """An entry point on one row: .a = its valid arguments by name, .outs = its Guarded outputs, .status(**changes) = the code it
+    returns with those arguments replaced.  Inputs are zeros (fp32-sized, so large enough in every dtype)."""
+
+    def __init__(self, fn, name, dn, out_dtype, ws_bytes=0, stat_rows=0):
+        k = self.k = _case(name, dn, False)
+        c = k.c
+        self.fn, M = fn, k.M
+        zeros = lambda n: torch.zeros(n, device="cuda")
+        self.outs = {"y": Guarded(M, k.Cout, k.y_ld, out_dtype), "dw": Guarded(1, c["cout"] * c["cin"] * k.taps, c["cout"] * c["cin"] * k.taps, torch.float32),
+                     "db": Guarded(1, c["cout"], c["cout"], torch.float32), "ws": _workspace(max(ws_bytes, 4)),
+                     "stat": Guarded(max(stat_rows, 1), 2 * k.Cout, 2 * k.Cout, torch.float32)}
+        self.keep = [zeros(M * k.x_ld), zeros(2 * k.taps * k.Cin * k.Cout), zeros(k.Cout), zeros(k.Cout), zeros(M * k.y_ld), zeros(M * k.y_ld),
+                     torch.ones(2, device="cuda")]
+        x, w, bias, scale, res, dy, dys = (t.data_ptr() for t in self.keep)
+        self.a = dict(x=x, w=w, bias=bias, scale=scale, res=res, dy=dy, dys=dys, act=k.L.ACT_RELU, B=k.B, H=k.H, W=k.W, M=M, Cin=k.Cin, Cout=k.Cout,
+                      taps=k.taps, cin_valid=c["cin"], cout_valid=c["cout"], x_ld=k.x_ld, y_ld=k.y_ld, dtype=k.code, st=k.st, ws_bytes=ws_bytes,
+                      **{n: g.ptr() for n, g in self.outs.items()})
+
+    def status(self, **changes):
+        a = dict(self.a, **changes)
+        return getattr(self.k.lib, self.fn)(*[a[n] for n in ENTRY_ARGS[self.fn].split()])
+
+    def refuses(self, expected, **changes):
+        """The call with `changes` returns `expected` and leaves every output, its row padding and its guard bands bit-unchanged."""
+        for g in self.outs.values():
+            g.body[:] = SENT
+        before = {n: g.buf.clone() for n, g in self.outs.items()}
+        rc = self.status(**changes)
+        torch.cuda.synchronize()
+        assert rc == expected, f"{self.fn} with {changes}: status {rc}, documented {expected}"
+        for n, g in self.outs.items():
+            assert torch.equal(g.buf.view(torch.uint8), before[n].view(torch.uint8)), f"{self.fn} with {changes}: refused, but wrote `{n}`"
+
+
+def _common_faults(e, nulls, sizes, taps_code=ARG, dtype_code=ARG, cin0_code=SHAPE, yld_step=4):
+    """The faults every entry shares, one at a time: null pointers and non-positive sizes (MU_ERR_ARG), then channel counts and row
+    strides (MU_ERR_SHAPE)."""
+    a = e.a
+    for n in nulls:
+        e.refuses(ARG, **{n: None})
+    for n, bad in sizes:
+        e.refuses(ARG, **{n: bad})
+    e.refuses(cin0_code, Cin=0)
+    e.refuses(SHAPE, Cin=a["Cin"] + 16)
+    e.refuses(SHAPE, Cout=a["Cout"] + 16)
+    e.refuses(SHAPE, x_ld=a["Cin"] - 8)
+    e.refuses(SHAPE, x_ld=a["x_ld"] + (2 if e.fn == "mu_conv_wgrad_h" else 4))      # (that entry doubles x_ld: the 16-bit view)
+    e.refuses(SHAPE, y_ld=a["Cout"] - 8)
+    e.refuses(SHAPE, y_ld=a["y_ld"] + yld_step)
+    if "taps" in ENTRY_ARGS[e.fn].split():
+        e.refuses(taps_code, taps=3)
+    if "dtype" in ENTRY_ARGS[e.fn].split():
+        e.refuses(dtype_code, dtype=7)
+
+
+BHW = [("B", 0), ("H", -1), ("W", 0)]
+ROWS_M = [("M", 0), ("M", 2 ** 31)]
+
+
+@gpu
+def test_forward_entries_refuse_with_the_documented_status_and_write_nothing():
+    from maskunet_amd import _lib
+    lib = _lib.load()
+    row, f16 = "2x8x16_64to64_k3", torch.float16
+    e = EntryCall("mu_conv_fwd", row, "fp16", f16)
+    assert e.status() == 0
+    _common_faults(e, ["x", "w", "y"], BHW)
+    rows = lib.mu_conv_stats_rows(2, 8, 16, 64, 64, 9, 1)
+    assert rows > 0
+    e = EntryCall("mu_conv_fwd_stats", row, "fp16", f16, stat_rows=rows)
+    assert e.status() == 0
+    # (a tap count or a dtype without statistics rows is "no statistics rows for this shape": MU_ERR_SHAPE, before taps is looked at)
+    _common_faults(e, ["x", "w", "y"], BHW, taps_code=SHAPE, dtype_code=SHAPE)
+    e.refuses(SHAPE, dtype=0)
+    e.refuses(ARG, stat=None, taps=3)
+    e = EntryCall("mu_conv_fwd_stats", "2x9x7_64to64_k3", "fp16", f16)          # a shape without statistics rows
+    assert lib.mu_conv_stats_rows(2, 9, 7, 64, 64, 9, 1) == 0 and e.status(stat=None) == 0
+    e.refuses(SHAPE)
+    e.refuses(SHAPE, taps=3)
+    e.refuses(ARG, taps=3, x=None)
+    e = EntryCall("mu_conv_fwd_fused", row, "fp16", f16)
+    assert e.status() == 0
+    _common_faults(e, ["x", "w", "y"], BHW)
+    e.refuses(ARG, act=e.k.L.ACT_RELU + 1)
+    e.refuses(ARG, act=e.k.L.ACT_NONE - 1)
+    e.refuses(SHAPE, act=99, Cout=80)                       # the shape is looked at before the activation
+    e = EntryCall("mu_conv_dgrad_h", row, "fp32x", torch.float32)
+    assert e.status() == 0
+    _common_faults(e, ["x", "w", "dys", "y"], BHW, yld_step=2)
+    row1 = "1x16x16_64to64_k1"
+    e = EntryCall("mu_conv1x1_fwd_add", row1, "fp16", f16)
+    assert e.status() == 0
+    _common_faults(e, ["x", "w", "res", "y"], ROWS_M, dtype_code=SHAPE)
+    e.refuses(SHAPE, Cout=96, y_ld=96)                      # a multiple of 32, not of 64
+    e = EntryCall("mu_conv1x1_fwd_enc_h", row1, "fp32x", torch.float32)
+    assert e.status() == 0
+    _common_faults(e, ["x", "w", "y"], ROWS_M)
+    e.refuses(SHAPE, Cout=96, y_ld=96)
+
+
+@gpu
+def test_weight_gradient_entries_refuse_with_the_documented_status_and_write_nothing():
+    from maskunet_amd import _lib
+    lib = _lib.load()
+    # (Cin = 0 passes the multiple-of-32 check and fails 0 < cin_valid <= Cin: MU_ERR_ARG)
+    row = "1x16x16_64to64_k1"
+    nws = lib.mu_conv_wgrad_workspace_bytes(1, 16, 16, 64, 64, 1)
+    e = EntryCall("mu_conv_wgrad", row, "fp16", torch.float32, ws_bytes=nws)
+    assert e.status() == 0
+    valid = [("cin_valid", 0), ("cin_valid", 65), ("cout_valid", 0), ("cout_valid", 65)]
+    _common_faults(e, ["x", "dy", "dw", "ws"], BHW + valid, cin0_code=ARG)
+    e.refuses(WORKSPACE, ws_bytes=0)
+    e.refuses(WORKSPACE, ws_bytes=WS_SMALLEST[("wgrad", row)] - 1)
+    e.refuses(SHAPE, Cin=80, taps=3)                        # the shape is looked at before taps
+    # db on a shape without bias partials: MU_ERR_SHAPE, even when taps is bad
+    e = EntryCall("mu_conv_wgrad_bias", row, "fp16", torch.float32, ws_bytes=nws)
+    assert lib.mu_conv_wgrad_bias_supported(64, 64, 1, 1) == 0
+    e.refuses(SHAPE)
+    e.refuses(SHAPE, taps=3)
+    e.refuses(ARG, db=None)
+    e.refuses(ARG, taps=3, x=None)
+    rowb = "2x9x7_64to192_k1"
+    nws = lib.mu_conv_wgrad_workspace_bytes(2, 9, 7, 64, 192, 1)
+    e = EntryCall("mu_conv_wgrad_bias", rowb, "fp16", torch.float32, ws_bytes=nws)
+    assert e.status() == 0
+    valid = [("cin_valid", 0), ("cin_valid", 65), ("cout_valid", 0), ("cout_valid", 193)]
+    _common_faults(e, ["x", "dy", "dw", "db", "ws"], BHW + valid, taps_code=SHAPE, dtype_code=SHAPE, cin0_code=ARG)
+    e.refuses(SHAPE, dtype=0)
+    e.refuses(WORKSPACE, ws_bytes=0)
+    e.refuses(WORKSPACE, ws_bytes=WS_SMALLEST[("wgrad", rowb)])               # the slabs fit, the bias partials do not
+    e.refuses(WORKSPACE, ws_bytes=WS_SMALLEST[("wgrad_bias", rowb)] - 1)
+    rowh = "1x10x6_19to32_k3"
+    for fn, entry, q in (("mu_conv_wgrad_h", "wgrad_h", lib.mu_conv_wgrad_h_workspace_bytes(1, 10, 6, 32, 32)),
+                         ("mu_conv_wgrad_h1", "wgrad_h1", lib.mu_conv_wgrad_workspace_bytes(1, 10, 6, 32, 32, 9))):
+        e = EntryCall(fn, rowh, "fp32x", torch.float32, ws_bytes=q)
+        assert e.status() == 0
+        two_term = entry == "wgrad_h"
+        valid = [("cin_valid", 0), ("cin_valid", 3), ("cout_valid", 0), ("cout_valid", 33), ("dys", None)]
+        _common_faults(e, ["x", "dy", "dw", "ws"], BHW + valid, cin0_code=SHAPE if two_term else ARG)
+        e.refuses(SHAPE if two_term else ARG, cin_valid=33)
+        e.refuses(ARG, dys=None, Cin=48)                    # the scale pair and the first-layer bound come first
+        e.refuses(WORKSPACE, ws_bytes=0)
+        e.refuses(WORKSPACE, ws_bytes=WS_SMALLEST[(entry, rowh)] - 1)
+
+
+# ------------------------------------------------------------------------------------------------
+# the workspace boundary of every weight-gradient family
+# ------------------------------------------------------------------------------------------------
+# (plan, entry, row, smallest ws_bytes the entry accepts): the sizes written down from the library of the commit before the host-layer
+# refactor of conv.hip, the way MODEL_PLANS was.  The first-layer kernels run from one [9][Cout][4] slab on; the others need every slab
+# of their plan (and the wide tiles with db their bias partials behind them), which may be less than the one size the query reserves.
+WS_FAMILIES = [
+    ("rgb_fma", "wgrad", "1x8x8_1to64_k3", 9216),
+    ("rgb2_npt5", "wgrad", "1x3x160_3to64_k3", 9216),
+    ("wgrad9_npt4", "wgrad", "1x6x128_64to64_k3", 884736),
+    ("wgrad9_w16", "wgrad", "1x8x16_128to64_k3", 1179648),
+    ("wgrad3_128", "wgrad", "1x5x96_128to128_k3", 589824),
+    ("wgrad3_64", "wgrad", "1x6x160_64to64_k3", 294912),
+    ("wide192_ci64", "wgrad", "2x9x7_64to192_k1", 49152),
+    ("wide192_ci64_bias", "wgrad_bias", "2x9x7_64to192_k1", 49920),
+    ("gen64", "wgrad", "1x16x16_64to64_k1", 16384),
+    ("gen32", "wgrad_h", "1x10x6_19to32_k3", 73728),
+    ("gen32", "wgrad_h1", "1x10x6_19to32_k3", 36864),
+]
+WS_SMALLEST = {(entry, row): n for _, entry, row, n in WS_FAMILIES}
+
+
+def _wgrad_entry(k, entry):
+    """(queried workspace bytes, call(dw, db, ws, ws_bytes) -> status) of a weight-gradient entry on the integer operands of the case k."""
+    L, lib, c = k.L, k.lib, k.c
+    if entry in ("wgrad", "wgrad_bias"):
+        x, dy = k.rows(k.ref["x"], k.Cin, k.x_ld), k.rows(k.ref["dy"], k.Cout, k.y_ld)
+        nws = lib.mu_conv_wgrad_workspace_bytes(k.B, k.H, k.W, k.Cin, k.Cout, k.taps)
+        tail = (k.B, k.H, k.W, k.Cin, k.Cout, k.taps, c["cin"], c["cout"], k.x_ld, k.y_ld)
+        if entry == "wgrad":
+            return nws, lambda dw, db, ws, n: lib.mu_conv_wgrad(x.data_ptr(), dy.data_ptr(), dw.ptr(), *tail, ws.ptr(), n, k.code, k.st)
+        return nws, lambda dw, db, ws, n: lib.mu_conv_wgrad_bias(x.data_ptr(), dy.data_ptr(), dw.ptr(), db.ptr(), *tail, ws.ptr(), n, k.code, k.st)
+    dyh, sc = _dy_h(k)
+    xd = k.rows(k.ref["x"], k.Cin, k.Cin, dtype=torch.float32)
+    xe, x16 = torch.empty_like(xd), torch.empty(xd.shape, dtype=torch.float16, device="cuda")
+    L.call("mu_split_encode_h4x", xd.data_ptr(), xe.data_ptr(), x16.data_ptr(), xd.numel(), k.st)
+    tail = (k.B, k.H, k.W, k.Cin, k.Cout, c["cin"], c["cout"], k.Cin, k.Cout)
+    if entry == "wgrad_h":
+        return (lib.mu_conv_wgrad_h_workspace_bytes(k.B, k.H, k.W, k.Cin, k.Cout),
+                lambda dw, db, ws, n: lib.mu_conv_wgrad_h(xe.data_ptr(), dyh.data_ptr(), sc.data_ptr(), dw.ptr(), *tail, ws.ptr(), n, k.st))
+    return (lib.mu_conv_wgrad_workspace_bytes(k.B, k.H, k.W, k.Cin, k.Cout, 9),
+            lambda dw, db, ws, n: lib.mu_conv_wgrad_h1(x16.data_ptr(), dyh.data_ptr(), sc.data_ptr(), dw.ptr(), *tail, ws.ptr(), n, k.st))
+
+
+@gpu
+@pytest.mark.parametrize("plan,entry,name,smallest", WS_FAMILIES, ids=[f"{e}-{p}-{r}" for p, e, r, _ in WS_FAMILIES])
+def test_workspace_boundary(plan, entry, name, smallest):
+    k = _case(name, "fp32x" if entry in ("wgrad_h", "wgrad_h1") else "fp16", True)
+    c = k.c
+    pid = {"wgrad": lambda: k.lib.mu_conv_wgrad_plan(k.B, k.H, k.W, k.Cin, k.Cout, k.taps, c["cin"], 1, 0),
+           "wgrad_bias": lambda: k.lib.mu_conv_wgrad_bias_plan(k.B, k.H, k.W, k.Cin, k.Cout, k.taps, c["cin"], 1),
+           "wgrad_h": lambda: k.lib.mu_conv_wgrad_plan(k.B, k.H, k.W, k.Cin, k.Cout, 9, c["cin"], 1, 1),
+           "wgrad_h1": lambda: k.lib.mu_conv_wgrad_plan(k.B, k.H, k.W, k.Cin, k.Cout, 9, c["cin"], 1, 0)}[entry]()
+    assert C.plan_name("wgrad", pid) == plan
+    query, call = _wgrad_entry(k, entry)
+    n_dw = c["cout"] * c["cin"] * k.taps
+    fresh = lambda: (Guarded(1, n_dw, n_dw, torch.float32), Guarded(1, c["cout"], c["cout"], torch.float32), _workspace(query))
+    # bisection between 0 (refused) and the query (accepted): every probe is a refusal or a complete valid call inside the real buffer
+    dw, db, ws = fresh()
+    probes = {0: call(dw, db, ws, 0), query: call(dw, db, ws, query)}
+    assert probes[0] == WORKSPACE and probes[query] == 0, probes
+    lo, hi = 0, query
+    while lo + 1 < hi:
+        mid = (lo + hi) // 2
+        probes[mid] = call(dw, db, ws, mid)
+        assert probes[mid] in (0, WORKSPACE), (mid, probes[mid])
+        lo, hi = (lo, mid) if probes[mid] == 0 else (mid, hi)
+    for n in (min(hi + 4, query), (hi + query) // 2):      # accepted sizes the bisection may not have visited
+        probes[n] = call(dw, db, ws, n)
+    torch.cuda.synchronize()
+    print(f"{entry} {plan} {name}: smallest accepted workspace {hi} of {query} queried, {len(probes)} probes")
+    refused, accepted = [n for n, rc in probes.items() if rc], [n for n, rc in probes.items() if rc == 0]
+    assert max(refused) < min(accepted), f"refusal is not monotone in ws_bytes: refused {sorted(refused)}, accepted {sorted(accepted)}"
+    assert hi <= query and hi == smallest, (hi, smallest, query)
+    for g, what in ((ws, "workspace"), (dw, "dW"), (db, "db")):
+        g.check(what)
+    # the call at exactly that size: exact results, intact guards, and nothing written behind the bytes it was given
+    dw, db, ws = fresh()
+    assert call(dw, db, ws, hi) == 0
+    torch.cuda.synchronize()
+    for g, what in ((ws, "workspace"), (dw, "dW"), (db, "db")):
+        g.check(what)
+    assert bool(torch.isnan(ws.body[0, hi // 4:]).all()), f"[{plan}] wrote behind the {hi} bytes of workspace it was given"
+    assert_exact(dw.valid().view(c["cout"], c["cin"], k.taps), _dw_ref(k), "oit", plan)
+    if entry == "wgrad_bias":
+        assert_exact(db.valid().view(-1), k.ref["db"], "c", plan + " db")
 
 
 # ------------------------------------------------------------------------------------------------
