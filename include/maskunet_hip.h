@@ -539,6 +539,32 @@ int mu_instance_match(const int* pairs, const int* n_pairs, const int* pred_tabl
                       int max_inst_gt, int num_classes, int K, int max_dets, const double* thr, int T, int* det_valid, int* det_class,
                       float* det_score, int* det_gt, double* det_iou, int* gt_per_class, int* pq_gt, double* pq_iou, int* pq_fp,
                       int* overflow, void* workspace, long ws_bytes, void* stream);
+/* mu_coco_match: COCOeval.evaluateImg in full and panopticapi's crowd rules over the pair table of mu_instance_pairs: what
+ * `coco_eval.evaluate()` does per image before accumulate() / summarize() (coco_instance.py:361-367, ade_instance.py:441-447).  Inputs,
+ * rows that take part, K and max_dets as mu_instance_match (max_dets = the largest of the maxDets ladder), and
+ *   gt_crowd int32 [B,max_inst_gt] or NULL (all 0): row g-1 != 0 = ground truth g is iscrowd;
+ *   gt_area fp64 [B,max_inst_gt] or NULL (the pixel area of the table): the area of the RANGE test only, never of an IoU;
+ *   area_rng fp64 [A][2] on the HOST, lo <= hi, both ends inclusive; thr as mu_instance_match.
+ * Per (image, class, range a, threshold t): gtIg[g] = crowd || area < lo || area > hi; the ground truths are visited non-ignored first,
+ * ascending id in each group; for each detection in order: iou = min(t, 1 - 1e-10), m = none; for each g: skip if matched at (a, t) and
+ * not crowd; stop if m is non-ignored and g ignored; skip if iou(d, g) < iou; else iou = iou(d, g), m = g (of equal IoUs the later
+ * wins).  iou = double(i) / double(a_p + a_g - i), against a crowd ground truth double(i) / double(a_p).
+ *   det_valid, det_class, det_rank int32 [B,K] (rank among the evaluated rows of the class in the image, from 0), det_score fp32 [B,K];
+ *   det_gt int32, det_iou fp64, det_ignore uint8 [B,A,T,K]: det_ignore = gtIg[m], or for an unmatched detection a_p < lo || a_p > hi;
+ *   gt_counted int32 [B,A,num_classes]: the non-ignored ground truths (npig);
+ *   pq_gt_per_class int32 [B,num_classes], pq_gt, pq_iou, pq_fp [B,K]: as mu_instance_match, but a crowd ground truth is neither a
+ *     candidate nor counted, and pq_fp = 0 if (v_p + i_crowd) / a_p > 0.5, i_crowd = the overlap with the crowd ground truth of the
+ *     detection's class that has the highest id;  overflow int32 [B].
+ * Rows that are not evaluated are zero; every output byte is written.  Limits of mu_instance_match and 1 <= A <= 4, else MU_ERR_SHAPE;
+ * a threshold outside (0, 1], lo > hi or a NaN in thr / area_rng: MU_ERR_ARG, before any launch. */
+int mu_coco_match_supported(int H, int W, int max_inst_pred, int max_inst_gt, int num_classes, int K, int max_dets, int T, int A);
+long mu_coco_match_workspace_bytes(int B, int K);
+int mu_coco_match(const int* pairs, const int* n_pairs, const int* pred_table, const float* pred_score, const int* pred_order,
+                  const int* pred_count, const int* gt_table, const int* gt_count, const int* gt_crowd_or_null,
+                  const double* gt_area_or_null, int B, int H, int W, int max_inst_pred, int max_inst_gt, int num_classes, int K,
+                  int max_dets, const double* thr, int T, const double* area_rng, int A, int* det_valid, int* det_class, int* det_rank,
+                  float* det_score, int* det_gt, double* det_iou, unsigned char* det_ignore, int* gt_counted, int* pq_gt_per_class,
+                  int* pq_gt, double* pq_iou, int* pq_fp, int* overflow, void* workspace, long ws_bytes, void* stream);
 /* COCO run-length masks: what mask_to_rle / maskUtils.encode make of every prediction (city_instance.py:399-403, coco_instance.py:351,397)
  * and annToMask (coco_instance.py:63) reads, restated from the published maskApi.c (rleEncode, rleDecode, rleToString, rleArea).
  * Format.  A mask [H,W] is read COLUMN-major: position j = x * H + y, N = H * W.  counts = the lengths of alternating runs, starting with

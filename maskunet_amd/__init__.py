@@ -10,7 +10,7 @@ from .dp import DataParallel, shard_batch
 from .losses import CrossEntropyLoss, InstanceContrastiveLoss, cross_entropy, mean_iou, pixel_cross_entropy_nhwc
 from .instances import (Instances, generate_instance_mask, instances_from_embeddings, instances_from_id_map, instances_from_labels,
                         predict_instances)
-from .matching import InstanceAP, Matches, PanopticQuality, match_instances
+from .matching import CocoEval, CocoMatches, InstanceAP, Matches, PanopticQuality, coco_match, match_instances
 from .metrics import SemanticBatch, SemanticMetrics, metrics_from_counts, semantic_eval
 from .rle import RLEs, decode_rle, encode_rle, rle_counts_from_string, rle_string_from_counts
 from .coco import CocoMasks, coco_masks
@@ -27,5 +27,5 @@ __all__ = ["ConvBlock", "DownSample", "UpSample", "Mask2FormerAttention", "UNet"
            "instances_from_labels", "generate_instance_mask", "Instances", "instances_from_embeddings", "match_instances", "Matches",
            "InstanceAP", "PanopticQuality", "RLEs", "encode_rle", "decode_rle", "rle_counts_from_string", "rle_string_from_counts",
            "coco_masks", "CocoMasks", "instances_from_id_map", "semantic_eval", "SemanticBatch", "SemanticMetrics",
-           "metrics_from_counts", "resize_pil_to_nhwc", "pack_images", "PackedImages"]
+           "metrics_from_counts", "resize_pil_to_nhwc", "pack_images", "PackedImages", "coco_match", "CocoMatches", "CocoEval"]
 __version__ = "0.1.0"

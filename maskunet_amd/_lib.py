@@ -116,6 +116,9 @@ SIGNATURES = {
     "mu_instance_match_supported": (I, [I, I, I, I, I, I, I, I]),
     "mu_instance_match_workspace_bytes": (L, [I, I]),
     "mu_instance_match": (I, [P] * 8 + [I] * 8 + [P, I] + [P] * 10 + [P, L, P]),
+    "mu_coco_match_supported": (I, [I, I, I, I, I, I, I, I, I]),
+    "mu_coco_match_workspace_bytes": (L, [I, I]),
+    "mu_coco_match": (I, [P] * 10 + [I] * 8 + [P, I, P, I] + [P] * 13 + [P, L, P]),
     "mu_rle_encode_supported": (I, [I, I, I, I]),
     "mu_rle_encode_workspace_bytes": (L, [I, I, I, I, I]),
     "mu_rle_encode": (I, [P, P, I, I, I, I, I, P, P, P, P, P, P, L, P]),

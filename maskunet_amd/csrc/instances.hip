@@ -1149,6 +1149,308 @@ extern "C" int mu_instance_match(const int* pairs, const int* n_pairs, const int
 }
 
 // ------------------------------------------------------------------------------------------
+// mu_coco_match: COCOeval.evaluateImg in full (iscrowd, area ranges, the ignore flags) and panopticapi's crowd rules over the same pair
+// table; inst_match_kernel above is untouched.  The same shape: one workgroup per image, rows, ranks and lists as there, then the A
+// area ranges one after the other -- matched[] and the per-class counters are reused, only two bitmaps over the ground truths are new:
+//   crowd[]  bit g - 1: ground truth g takes part and is iscrowd (built once);
+//   ig[]     bit g - 1: gtIg of the current range = crowd || area < lo || area > hi (area: gt_area if given, else the pixel area).
+// COCO's visiting order (the stable argsort of gtIg: non-ignored first, ascending id inside each group) is two walks over the
+// detection's rows of the pair table, which are in ascending gt id: first the non-ignored ground truths, then -- only if nothing
+// matched, that is evaluateImg's break -- the ignored ones.  Against a crowd ground truth iou = double(i) / double(a_p), and its
+// matched bit never excludes it.
+// Panoptic: a crowd ground truth is no candidate and is not counted; an unmatched detection is no false positive if
+// double(v + i_crowd) / double(a_p) > 0.5 with i_crowd its overlap with the highest crowd id of its class (ccnt[] holds that id
+// between the scan and the first range).
+// Dynamic LDS: the layout above plus 2 * 2 * ceil(max_inst_gt / 64) words: 58 372 bytes at the limits.
+// ------------------------------------------------------------------------------------------
+#define COCO_MAX_A 4
+
+struct CocoParams {
+    const int *pairs, *n_pairs, *ptable, *porder, *pcount, *gtable, *gcount, *gcrowd;
+    const float* pscore;
+    const double* garea;
+    int N, mp, mg, nc, K, max_dets, T, A;
+    int *det_valid, *det_class, *det_rank, *det_gt, *gt_counted, *pq_gt_per_class, *pq_gt, *pq_fp, *overflow, *dstart;
+    float* det_score;
+    double *det_iou, *pq_iou;
+    unsigned char* det_ignore;
+    double thr[MATCH_MAX_T];
+    double rng[COCO_MAX_A][2];
+};
+
+static int coco_bit_words(int max_inst_gt) { return ((max_inst_gt + 63) >> 6) << 1; }      // whole 64-lane ballots
+
+__device__ __forceinline__ bool coco_bit(const unsigned* bits, int g) { return (bits[(g - 1) >> 5] >> ((g - 1) & 31)) & 1u; }
+
+__global__ __launch_bounds__(INST_THREADS) void coco_match_kernel(const CocoParams P) {
+    extern __shared__ unsigned inst_lds[];
+    const int K = P.K, nc = P.nc, T = P.T, A = P.A;
+    const int GB = ((P.mg + 63) >> 6) << 1;
+    unsigned* info = inst_lds;
+    int* list = (int*)(info + K);
+    unsigned* matched = (unsigned*)(list + K);
+    int* ccnt = (int*)(matched + P.mg);
+    int* cstart = ccnt + nc;
+    unsigned* crowd = (unsigned*)(cstart + nc + 1);
+    unsigned* ig = crowd + GB;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int* pairs = P.pairs + (long)b * P.N * 3;
+    const int n = min(max(P.n_pairs[b], 0), P.N);
+    const int* ptable = P.ptable + (long)b * P.mp * 8;
+    const int* gtable = P.gtable + (long)b * P.mg * 8;
+    const int* porder = P.porder + (long)b * P.mp;
+    const int* gcrowd = P.gcrowd ? P.gcrowd + (long)b * P.mg : nullptr;
+    const double* garea = P.garea ? P.garea + (long)b * P.mg : nullptr;
+    const int Kp = min(max(P.pcount[b], 0), P.mp), Kg = min(max(P.gcount[b], 0), P.mg);
+    int* dstart = P.dstart + (long)b * K;
+
+    if (tid == 0) P.overflow[b] = (P.pcount[b] > P.mp || P.gcount[b] > P.mg) ? 1 : 0;
+    for (int c = tid; c < nc; c += INST_THREADS) ccnt[c] = 0;
+    __syncthreads();
+    // the ground truths that take part: crowd bits, and the non-crowd ones per class (what panoptic counts)
+    for (int g0 = wave * 64; g0 < GB * 32; g0 += INST_THREADS) {
+        const int g = g0 + lane;                       // id g + 1
+        const int c = g < Kg ? gtable[(long)g * 8] : 0;
+        const bool part = c >= 1 && c < nc;
+        const bool cr = part && gcrowd && gcrowd[g] != 0;
+        if (part && !cr) atomicAdd(&ccnt[c], 1);
+        const unsigned long long m = __ballot(cr);
+        if (lane == 0) {
+            crowd[g0 >> 5] = (unsigned)m;
+            crowd[(g0 >> 5) + 1] = (unsigned)(m >> 32);
+        }
+    }
+    for (int k = tid; k < K; k += INST_THREADS) {
+        const int p = porder[k];
+        int c = (p >= 1 && p <= Kp) ? ptable[(long)(p - 1) * 8] : 0;
+        if (c < 1 || c >= nc) c = 0;
+        info[k] = (unsigned)c;
+    }
+    __syncthreads();
+    for (int c = tid; c < nc; c += INST_THREADS) {
+        P.pq_gt_per_class[(long)b * nc + c] = ccnt[c];
+        ccnt[c] = 0;
+    }
+    __syncthreads();
+
+    // rank of every row among the rows of its class, as in inst_match_kernel
+    for (int k = tid; k < K; k += INST_THREADS) {
+        const unsigned c = info[k] & 0xffffu;
+        unsigned rank = 0xffffu;
+        if (c) {
+            rank = 0;
+            for (int j = 0; j < k; ++j) rank += ((info[j] & 0xffffu) == c);
+            if (rank < (unsigned)P.max_dets) atomicAdd(&ccnt[c], 1);
+            else rank = 0xffffu;
+        }
+        info[k] = c | (rank << 16);
+    }
+    __syncthreads();
+    if (wave == 0) {
+        const int evaluated = wave_scan_excl_array(ccnt, cstart, nc, lane);
+        if (lane == 0) cstart[nc] = evaluated;
+    }
+    __syncthreads();
+
+    // ccnt[c] = the highest crowd id of class c, 0 = none
+    for (int c = tid; c < nc; c += INST_THREADS) ccnt[c] = 0;
+    __syncthreads();
+    for (int g = 1 + tid; g <= Kg; g += INST_THREADS)
+        if (coco_bit(crowd, g)) atomicMax(&ccnt[gtable[(long)(g - 1) * 8]], g);
+    __syncthreads();
+
+    // per row: the [B,K] outputs, the row's place in its class's list, its first row in the pair table, the panoptic match
+    for (int k = tid; k < K; k += INST_THREADS) {
+        const unsigned c = info[k] & 0xffffu, rank = info[k] >> 16;
+        const bool valid = c != 0u && rank != 0xffffu;
+        const long o = (long)b * K + k;
+        int m_gt = 0, m_fp = 0;
+        double m_iou = 0.0;
+        if (valid) {
+            const int p = porder[k];
+            list[cstart[c] + (int)rank] = k;
+            int lo = 0, hi = n;                        // lower bound of p in the pair table
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (pairs[(long)mid * 3] < p) lo = mid + 1;
+                else hi = mid;
+            }
+            dstart[k] = lo;
+            const int a_p = ptable[(long)(p - 1) * 8 + 1];
+            const int last_crowd = ccnt[c];
+            int v = 0, i_crowd = 0;
+            for (int r = lo; r < n && pairs[(long)r * 3] == p; ++r) {
+                const int g = pairs[(long)r * 3 + 1];
+                const int gc = (g >= 1 && g <= Kg) ? gtable[(long)(g - 1) * 8] : 0;
+                if (gc < 1 || gc >= nc) v += pairs[(long)r * 3 + 2];
+                else if (g == last_crowd) i_crowd = pairs[(long)r * 3 + 2];
+            }
+            for (int r = lo; r < n && pairs[(long)r * 3] == p; ++r) {
+                const int g = pairs[(long)r * 3 + 1];
+                if (g < 1 || g > Kg || gtable[(long)(g - 1) * 8] != (int)c || coco_bit(crowd, g)) continue;
+                const int i = pairs[(long)r * 3 + 2];
+                const int u = a_p + gtable[(long)(g - 1) * 8 + 1] - i - v;
+                if (u <= 0) continue;
+                const double iou = (double)i / (double)u;
+                if (iou > 0.5) {
+                    m_gt = g;
+                    m_iou = iou;
+                }
+            }
+            if (!m_gt) m_fp = (a_p > 0 && (double)(v + i_crowd) / (double)a_p > 0.5) ? 0 : 1;
+            P.det_score[o] = P.pscore[(long)b * P.mp + p - 1];
+        } else {
+            dstart[k] = 0;
+            P.det_score[o] = 0.f;
+            for (int at = 0; at < A * T; ++at) {
+                P.det_gt[((long)b * A * T + at) * K + k] = 0;
+                P.det_iou[((long)b * A * T + at) * K + k] = 0.0;
+                P.det_ignore[((long)b * A * T + at) * K + k] = 0;
+            }
+        }
+        P.det_valid[o] = valid ? 1 : 0;
+        P.det_class[o] = valid ? (int)c : 0;
+        P.det_rank[o] = valid ? (int)rank : 0;
+        P.pq_gt[o] = m_gt;
+        P.pq_iou[o] = m_iou;
+        P.pq_fp[o] = m_fp;
+    }
+
+    for (int a = 0; a < A; ++a) {
+        const double lo_a = P.rng[a][0], hi_a = P.rng[a][1];
+        __syncthreads();                               // the rows above / the chains of the range before are done with ccnt, matched, ig
+        for (int c = tid; c < nc; c += INST_THREADS) ccnt[c] = 0;
+        for (int g = tid; g < P.mg; g += INST_THREADS) matched[g] = 0u;
+        __syncthreads();
+        for (int g0 = wave * 64; g0 < GB * 32; g0 += INST_THREADS) {
+            const int g = g0 + lane;
+            const int c = g < Kg ? gtable[(long)g * 8] : 0;
+            const bool part = c >= 1 && c < nc;
+            bool ignored = false;
+            if (part) {
+                const double area = garea ? garea[g] : (double)gtable[(long)g * 8 + 1];
+                ignored = ((crowd[g >> 5] >> (g & 31)) & 1u) || area < lo_a || area > hi_a;
+                if (!ignored) atomicAdd(&ccnt[c], 1);
+            }
+            const unsigned long long m = __ballot(ignored);
+            if (lane == 0) {
+                ig[g0 >> 5] = (unsigned)m;
+                ig[(g0 >> 5) + 1] = (unsigned)(m >> 32);
+            }
+        }
+        __syncthreads();
+        for (int c = tid; c < nc; c += INST_THREADS) P.gt_counted[((long)b * A + a) * nc + c] = ccnt[c];
+
+        // chain q = (class, threshold), as in inst_match_kernel
+        for (int q = tid; q < (nc - 1) * T; q += INST_THREADS) {
+            const int c = 1 + q / T, t = q % T;
+            const double floor_iou = fmin(P.thr[t], 1.0 - 1e-10);
+            const long at = ((long)b * A + a) * T + t;
+            for (int s = cstart[c]; s < cstart[c + 1]; ++s) {
+                const int k = list[s];
+                const int p = porder[k];
+                const int a_p = ptable[(long)(p - 1) * 8 + 1];
+                double best = floor_iou;
+                int best_g = 0;
+                for (int pass = 0; pass < 2 && !best_g; ++pass) {      // the non-ignored ground truths, then the ignored ones
+                    for (int r = dstart[k]; r < n && pairs[(long)r * 3] == p; ++r) {
+                        const int g = pairs[(long)r * 3 + 1];
+                        if (g < 1 || g > Kg || gtable[(long)(g - 1) * 8] != c) continue;
+                        if ((int)coco_bit(ig, g) != pass) continue;
+                        const bool cr = coco_bit(crowd, g);
+                        if (!cr && ((*(volatile unsigned*)&matched[g - 1] >> t) & 1u)) continue;
+                        const int i = pairs[(long)r * 3 + 2];
+                        const int u = cr ? a_p : a_p + gtable[(long)(g - 1) * 8 + 1] - i;
+                        if (u <= 0) continue;
+                        const double iou = (double)i / (double)u;
+                        if (iou < best) continue;
+                        best = iou;
+                        best_g = g;
+                    }
+                }
+                if (best_g) atomicOr(&matched[best_g - 1], 1u << t);
+                P.det_gt[at * K + k] = best_g;
+                P.det_iou[at * K + k] = best_g ? best : 0.0;
+                P.det_ignore[at * K + k] = best_g ? (unsigned char)coco_bit(ig, best_g)
+                                                  : (unsigned char)((double)a_p < lo_a || (double)a_p > hi_a);
+            }
+        }
+    }
+}
+
+extern "C" int mu_coco_match_supported(int H, int W, int max_inst_pred, int max_inst_gt, int num_classes, int K, int max_dets, int T,
+                                       int A) {
+    if (mu_instance_match_supported(H, W, max_inst_pred, max_inst_gt, num_classes, K, max_dets, T) != MU_OK) return MU_ERR_SHAPE;
+    if (A < 1 || A > COCO_MAX_A) return MU_ERR_SHAPE;
+    return MU_OK;
+}
+
+// int first_row[B][K], as mu_instance_match
+extern "C" long mu_coco_match_workspace_bytes(int B, int K) { return mu_instance_match_workspace_bytes(B, K); }
+
+extern "C" int mu_coco_match(const int* pairs, const int* n_pairs, const int* pred_table, const float* pred_score, const int* pred_order,
+                             const int* pred_count, const int* gt_table, const int* gt_count, const int* gt_crowd_or_null,
+                             const double* gt_area_or_null, int B, int H, int W, int max_inst_pred, int max_inst_gt, int num_classes,
+                             int K, int max_dets, const double* thr, int T, const double* area_rng, int A, int* det_valid,
+                             int* det_class, int* det_rank, float* det_score, int* det_gt, double* det_iou, unsigned char* det_ignore,
+                             int* gt_counted, int* pq_gt_per_class, int* pq_gt, double* pq_iou, int* pq_fp, int* overflow,
+                             void* workspace, long ws_bytes, void* stream) {
+    if (!pairs || !n_pairs || !pred_table || !pred_score || !pred_order || !pred_count || !gt_table || !gt_count || !thr || !area_rng ||
+        !det_valid || !det_class || !det_rank || !det_score || !det_gt || !det_iou || !det_ignore || !gt_counted || !pq_gt_per_class ||
+        !pq_gt || !pq_iou || !pq_fp || !overflow || !workspace || B <= 0 || H <= 0 || W <= 0)
+        return MU_ERR_ARG;
+    if (mu_coco_match_supported(H, W, max_inst_pred, max_inst_gt, num_classes, K, max_dets, T, A) != MU_OK) return MU_ERR_SHAPE;
+    for (int t = 0; t < T; ++t)
+        if (!(thr[t] > 0.0 && thr[t] <= 1.0)) return MU_ERR_ARG;      // NaN included
+    for (int a = 0; a < A; ++a)
+        if (!(area_rng[2 * a] <= area_rng[2 * a + 1])) return MU_ERR_ARG;
+    if (ws_bytes < mu_coco_match_workspace_bytes(B, K)) return MU_ERR_WORKSPACE;
+    CocoParams P;
+    P.pairs = pairs;
+    P.n_pairs = n_pairs;
+    P.ptable = pred_table;
+    P.pscore = pred_score;
+    P.porder = pred_order;
+    P.pcount = pred_count;
+    P.gtable = gt_table;
+    P.gcount = gt_count;
+    P.gcrowd = gt_crowd_or_null;
+    P.garea = gt_area_or_null;
+    P.N = H * W;
+    P.mp = max_inst_pred;
+    P.mg = max_inst_gt;
+    P.nc = num_classes;
+    P.K = K;
+    P.max_dets = max_dets;
+    P.T = T;
+    P.A = A;
+    P.det_valid = det_valid;
+    P.det_class = det_class;
+    P.det_rank = det_rank;
+    P.det_score = det_score;
+    P.det_gt = det_gt;
+    P.det_iou = det_iou;
+    P.det_ignore = det_ignore;
+    P.gt_counted = gt_counted;
+    P.pq_gt_per_class = pq_gt_per_class;
+    P.pq_gt = pq_gt;
+    P.pq_iou = pq_iou;
+    P.pq_fp = pq_fp;
+    P.overflow = overflow;
+    P.dstart = (int*)workspace;
+    for (int t = 0; t < MATCH_MAX_T; ++t) P.thr[t] = t < T ? thr[t] : 1.0;
+    for (int a = 0; a < COCO_MAX_A; ++a) {
+        P.rng[a][0] = a < A ? area_rng[2 * a] : 0.0;
+        P.rng[a][1] = a < A ? area_rng[2 * a + 1] : 0.0;
+    }
+    // 58372 bytes at the limits: no grant needed
+    const size_t lds = (size_t)(2 * K + max_inst_gt + 2 * num_classes + 1 + 2 * coco_bit_words(max_inst_gt)) * sizeof(int);
+    coco_match_kernel<<<B, INST_THREADS, lds, (hipStream_t)stream>>>(P);
+    MU_CHECK_LAUNCH();
+    return MU_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // mu_id_instances: ground-truth instances from an id map the dataset supplies -- get_instance_annotations
 // (city_instance.py:431-449) on Cityscapes instanceIds, panopticapi's rgb2id of a COCO panoptic PNG, or coco_masks(...).ids.  Instance
 // k is the set of pixels that hold the k-th distinct non-zero value in ascending signed order (np.unique); its class is the median of
