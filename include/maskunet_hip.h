@@ -357,7 +357,8 @@ int mu_attn_bwd_phases_padded(const void* qkv, const void* x, const void* oattn,
  *                    *cnt == 0: all dst_rows rows NaN (the reference's dK / dV of an image without a visible key)
  *   mu_softmax_rows: S[r][j] <- softmax_j(scale * S[r][j]) over j < *cnt, 0 for *cnt <= j < ld (:174-184; no visible key: NaN rows,
  *                    as the reference's softmax of an all -inf row)
- *   mu_attn_wide_ds: dP[r][j] <- P[r][j] * (dP[r][j] - sum_k P[r][k] dP[r][k]) * scale for j < *cnt, 0 behind (softmax backward)
+ *   mu_attn_wide_ds: dP[r][j] <- P[r][j] * (dP[r][j] - sum_k P[r][k] dP[r][k] / sum_k P[r][k]) * scale for j < *cnt, 0 behind (softmax
+ *                    backward; the division by the stored row's own sum, 1 to rounding, keeps dS right where one key dominates)
  *   mu_ln_rows_fwd : out = LayerNorm over the first c_valid of C stored channels of (o + x), * gamma + beta (:187-188); mean / rstd
  *                    [rows] saved for the backward; pad channels 0
  *   mu_ln_rows_bwd : dY = d(o + x) of the above; g_xhat = grad_out * xhat (its column sums are dgamma, those of grad_out dbeta:

@@ -6,6 +6,7 @@
 // here -- this path trades the flash kernels' memory footprint and speed for generality.  This file holds the row kernels in between:
 // gather / scatter of the kept rows, the masked row softmax, dS = P o (dP - rowsum(P o dP)) / sqrt(C), and LayerNorm([C]) forward /
 // backward over any C.  T = fp16 or fp32 storage, fp32 arithmetic; no atomics (results are run-to-run identical).
+// The RAW scores q.k are stored in T before the softmax scales them: fp16 storage limits this path to |q.k| < 65504.
 #include "common.h"
 #include "../../include/maskunet_hip.h"
 
@@ -73,7 +74,11 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(T* __restrict__ S, in
     }
 }
 
-// dP[r][j] <- P[r][j] * (dP[r][j] - sum_k P[r][k] dP[r][k]) * scale  (j < cnt), 0 behind (NaN rows when cnt == 0)
+// dP[r][j] <- P[r][j] * (dP[r][j] - a) * scale  (j < cnt), 0 behind (NaN rows when cnt == 0), a = sum_k P[r][k] dP[r][k] / sum_k P[r][k].
+// The division by the row's own sum is the identity for an exact softmax row; P as STORED (rounded to T) sums to 1 only to half an
+// ulp of its largest entry.  With one dominant key, 1 - P_max is of that size itself, and dP_max - sum_k P_k dP_k -- all that is left
+// of dS for that key -- would be off by its own magnitude (fp16: dQ / dK wrong by 50 %).  Normalised, dP_j - a =
+// sum_k P_k (dP_j - dP_k) / sum_k P_k depends on the small entries only, and every row of dS sums to zero whatever the rounding of P.
 template <typename T>
 __global__ __launch_bounds__(256) void attn_wide_ds_kernel(const T* __restrict__ P, T* __restrict__ dP, int N, int ld, const int* __restrict__ cnt,
                                                            float scale) {
@@ -82,9 +87,11 @@ __global__ __launch_bounds__(256) void attn_wide_ds_kernel(const T* __restrict__
     for (int r = blockIdx.x; r < N; r += gridDim.x) {
         const T* p = P + (long)r * ld;
         T* d = dP + (long)r * ld;
-        float a = 0.f;
-        for (int j = threadIdx.x; j < n; j += 256) a = fmaf((float)p[j], (float)d[j], a);
+        float a = 0.f, z = 0.f;
+        for (int j = threadIdx.x; j < n; j += 256) { a = fmaf((float)p[j], (float)d[j], a); z += (float)p[j]; }
         a = blk_sum(a, sh);
+        z = blk_sum(z, sh);
+        a = a / z;
         // (no visible key: P is NaN throughout and so is dS -- the reference's dQ of such an image is NaN)
         for (int j = threadIdx.x; j < ld; j += 256) d[j] = j < n ? (T)((float)p[j] * ((float)d[j] - a) * scale) : (n ? (T)0.f : (T)NAN);
     }
