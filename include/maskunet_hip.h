@@ -329,11 +329,29 @@ int mu_attn_fwd(const void* qkv, const void* x, const int* kidx, const int* kcnt
                 void* oattn, float* lse2, float* ln_mean, float* ln_rstd, int B, int N, int C, int nkmax, float eps, int dtype,
                 void* stream);
 /* backward: grad_out [B,N,C] (wrt `out`) -> dY (grad wrt the pre-LayerNorm sum, i.e. the residual branch),
- * dqkv [B,N,3C] (masked keys get exact zeros), dgamma, dbeta.  delta [B,N] is scratch output. */
+ * dqkv [B,N,3C] (masked keys get exact zeros), dgamma, dbeta.  delta [B,N] is scratch output.  workspace: 16-byte aligned,
+ * mu_attn_bwd_workspace_bytes(B, N, C) bytes (the same size for every dtype).
+ * Refusal order of the attention entry points: a null pointer, a non-positive B / N / nkmax or c_valid outside 1..C is MU_ERR_ARG; then
+ * (backward) ws_bytes below the query is MU_ERR_WORKSPACE; then an unknown dtype is MU_ERR_ARG; then (backward) N % 4 != 0, or a C
+ * outside {32,64,128,256}, is MU_ERR_SHAPE.  A refused call enqueues nothing: no kernel and no memset, every buffer is left as it was. */
 long mu_attn_bwd_workspace_bytes(int B, int N, int C);
 int mu_attn_bwd(const void* qkv, const void* x, const void* oattn, const void* grad_out, const int* kidx, const int* kcnt,
                 const float* lse2, const float* ln_mean, const float* ln_rstd, const float* gamma, void* dY, float* delta, void* dqkv,
                 float* dgamma, float* dbeta, int B, int N, int C, int nkmax, void* workspace, long ws_bytes, int dtype, void* stream);
+/* the same, one phase group at a time (bit mask): 1 = zero dqkv + LayerNorm backward / delta / dgamma,dbeta,
+ * 2 = dQ sweep, 4 = dK/dV sweep.  Phases 2 and 4 need phase 1's dY, delta and workspace contents.
+ * 8 (MU_ATTN_KIDX_PERMUTATION, OR-ed into every call of one backward) = a promise about kidx: nkmax == N and every row is a whole
+ * permutation of 0..N-1 with the masked keys listed after the kept ones (what a stable descending argsort of the keep mask
+ * gives).  The dK/dV sweep then writes the masked keys' zero rows itself and phase 1 skips the memset of the whole dqkv buffer. */
+#define MU_ATTN_KIDX_PERMUTATION 8
+/* 16 (MU_ATTN_DQKV_ENCODED, OR-ed into every call of one backward; MU_F32X only, ignored otherwise): dqkv is written CHUNK-ENCODED
+ * ([4 bf16 hi | 4 bf16 lo] per 16 bytes, the mu_split_encode form) -- the operand form mu_conv_fwd / mu_conv1x1_fwd_add / mu_conv_wgrad
+ * take for the q/k/v projection's data- and weight-gradient, and mu_colsum(MU_F32X) for its bias gradient. */
+#define MU_ATTN_DQKV_ENCODED 16
+int mu_attn_bwd_phases(const void* qkv, const void* x, const void* oattn, const void* grad_out, const int* kidx, const int* kcnt,
+                       const float* lse2, const float* ln_mean, const float* ln_rstd, const float* gamma, void* dY, float* delta,
+                       void* dqkv, float* dgamma, float* dbeta, int B, int N, int C, int nkmax, void* workspace, long ws_bytes,
+                       int dtype, int phases, void* stream);
 /* Channel counts that are not one of the kernels' widths (32, 64, 128, 256) -- `Mask2FormerAttention(channels, size)` accepts any
  * (ade_semantic.py:153-161) -- run zero-padded: C = the padded width every tensor here is stored with (qkv, x, out, ... and gamma /
  * beta, all zero in the pad channels: zero-padded projection weights give zero Q/K/V pads), c_valid = the true channel count.  The
@@ -371,20 +389,6 @@ int mu_ln_rows_fwd(const void* o, const void* x, const float* gamma, const float
                    int C, int c_valid, float eps, int dtype, void* stream);
 int mu_ln_rows_bwd(const void* grad_out, const void* o, const void* x, const float* mean, const float* rstd, const float* gamma, void* dY,
                    void* g_xhat, long rows, int C, int c_valid, int dtype, void* stream);
-/* the same, one phase group at a time (bit mask): 1 = zero dqkv + LayerNorm backward / delta / dgamma,dbeta,
- * 2 = dQ sweep, 4 = dK/dV sweep.  Phases 2 and 4 need phase 1's dY, delta and workspace contents.
- * 8 (MU_ATTN_KIDX_PERMUTATION, OR-ed into every call of one backward) = a promise about kidx: nkmax == N and every row is a whole
- * permutation of 0..N-1 with the masked keys listed after the kept ones (what a stable descending argsort of the keep mask
- * gives).  The dK/dV sweep then writes the masked keys' zero rows itself and phase 1 skips the memset of the whole dqkv buffer. */
-#define MU_ATTN_KIDX_PERMUTATION 8
-/* 16 (MU_ATTN_DQKV_ENCODED, OR-ed into every call of one backward; MU_F32X only, ignored otherwise): dqkv is written CHUNK-ENCODED
- * ([4 bf16 hi | 4 bf16 lo] per 16 bytes, the mu_split_encode form) -- the operand form mu_conv_fwd / mu_conv1x1_fwd_add / mu_conv_wgrad
- * take for the q/k/v projection's data- and weight-gradient, and mu_colsum(MU_F32X) for its bias gradient. */
-#define MU_ATTN_DQKV_ENCODED 16
-int mu_attn_bwd_phases(const void* qkv, const void* x, const void* oattn, const void* grad_out, const int* kidx, const int* kcnt,
-                       const float* lse2, const float* ln_mean, const float* ln_rstd, const float* gamma, void* dY, float* delta,
-                       void* dqkv, float* dgamma, float* dbeta, int B, int N, int C, int nkmax, void* workspace, long ws_bytes,
-                       int dtype, int phases, void* stream);
 
 /* ---- "next" rows: the steps either side of the path ------------------------------ */
 /* f1: nn.CrossEntropyLoss (ade_semantic.py:377,399; ignore_index: city_semantic.py:341) on NHWC logits [M, Cp] (C valid

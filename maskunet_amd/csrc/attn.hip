@@ -187,7 +187,7 @@ template <> struct AT<float> {
 // 32 ks + 8 g ..), three v_mfma_f32_16x16x32_f16 per row product (lo hi + hi lo + hi hi); the transposed operands of the
 // accumulator-operand products come from ds_read_b64_tr_b16 on the hi and on the lo chunks, and P / dS enter as ONE packed fp16
 // operand straight from the accumulators (two MFMAs per product, no register split).  The resident, pre-scaled operands are decoded,
-// scaled and re-split once outside the sweep.  Range management (the backward's power-of-two scales): see attn_bwd_t.
+// scaled and re-split once outside the sweep.  Range management (the backward's power-of-two scales): see attn_bwd_launch.
 template <> struct AT<xf32> {
     static constexpr int VN = 4, KR = 32, GS = 8;
     static constexpr bool PK = true;
@@ -964,9 +964,7 @@ __global__ __launch_bounds__(256) void split_encode_h_kernel(const f32x4* src, u
 extern "C" int mu_split_encode_h(const void* src, void* dst, long n_elems, void* stream) {
     if (!src || !dst || n_elems <= 0 || n_elems % 8) return MU_ERR_ARG;
     const long ng = n_elems / 8;
-    long g = (ng + 511) / 512;
-    g = g < 1 ? 1 : (g > 8192 ? 8192 : g);
-    split_encode_h_kernel<<<(int)g, 256, 0, (hipStream_t)stream>>>((const f32x4*)src, (uint4*)dst, ng);
+    split_encode_h_kernel<<<mu_grid(ng, 512, 8192), 256, 0, (hipStream_t)stream>>>((const f32x4*)src, (uint4*)dst, ng);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
@@ -996,7 +994,7 @@ __global__ __launch_bounds__(NW * 64, (OCCQ ? OCCQ : attn_dq_occ<T, D>())) void 
     constexpr bool XF = std::is_same<T, xf32>::value;
     constexpr int TEK = Z::TE(KT);
     __shared__ __attribute__((aligned(16))) T lds[2 * 2 * TEK];
-    // fp32x: dY arrives scaled by the power of two gs (attn_bwd_t), the probabilities are computed as 2^pshift P: dS -- ONE fp16 operand --
+    // fp32x: dY arrives scaled by the power of two gs (attn_bwd_launch), the probabilities are computed as 2^pshift P: dS -- ONE fp16 operand --
     // then sits inside fp16's exponent range; the accumulators are un-scaled once, in the epilogue (exact: powers of two)
     float gs = 1.0f, un = 1.0f;
     if constexpr (XF) {
@@ -1142,7 +1140,7 @@ __global__ __launch_bounds__(NW * 64, (OCCQ ? OCCQ : attn_dq_occ<T, D>())) void 
 // C = 128 with 4 waves of 16 keys every launch moved 4.2 GB in 0.7 ms (6 TB/s, the L2 -> LDS ceiling) -- 8 waves halve that.
 // Waves per SIMD the sweep is bounded to (4-wave blocks; measured in-process, B = 64, N = 16384, C = 64 fp16): 3 waves/SIMD (168 VGPRs, 4 spilled)
 // 4.70 ms vs 2 waves/SIMD 5.24 ms; 1 wave/SIMD with 64 keys/wave 9 ms.  fp32x at C <= 64: 2.  C = 256 does not fit under any bound, and the
-// 8- and 12-wave blocks of C = 128 (attn_bwd_t) are alone on their CU.
+// 8- and 12-wave blocks of C = 128 (AttnTiles) are alone on their CU.
 template <typename T, int D, int NW> constexpr int attn_dkv_occ() {
     if (NW >= 8 || D > 64) return 1;
     return std::is_same<T, xf32>::value ? 2 : (sizeof(T) == 2 ? 3 : 1);
@@ -1323,7 +1321,7 @@ __global__ __launch_bounds__(NW * 64, (attn_dkv_occ<T, D, NW>())) void attn_bwd_
         // fp16 storage: P and dP' are rounded to fp16 first -- both are fp16 MFMA operands' worth of precision anyway --
         // and dS = P * dP' is FOUR packed fp16 multiplies per 8 scores instead of 8 fp32 ones: 24 instead of 32 VALU instructions per
         // 32-query x 32-key tile behind the 16 exponentials (the sweep runs at MFMA + VALU issue time)
-        // fp32x takes the same path (the row constants carry the power-of-two scales that keep P and dP' inside fp16's range: attn_bwd_t)
+        // fp32x takes the same path (the row constants carry the power-of-two scales that keep P and dP' inside fp16's range: attn_bwd_launch)
         if constexpr (A::PK) {
             typename A::Packed pb[NKT], db[NKT];
 #pragma unroll
@@ -1414,53 +1412,86 @@ __global__ __launch_bounds__(NW * 64, (attn_dkv_occ<T, D, NW>())) void attn_bwd_
 // ------------------------------------------------------------------------------------------
 // host entry points
 // ------------------------------------------------------------------------------------------
-template <typename T>
-static int attn_fwd_t(const T* qkv, const T* x, const int* kidx, const int* kcnt, const float* gamma, const float* beta, T* out,
-                      T* oattn, float* lse2, float* mean, float* rstd, int B, int N, int C, int cv, int nkmax, float eps, hipStream_t st) {
-    const float sl2 = (float)(1.4426950408889634 / sqrt((double)cv));      // 1/sqrt(channels) of the TRUE channel count (ade_semantic.py:174)
-    // (measured and removed: 8-wave blocks sharing each K/V tile among 256 queries, -8 %; 64 queries per wave against 32-key tiles,
-    //  -4 %; 128- / 32-key tiles and other occupancy bounds, +-0: the sweep is bound by MFMA + VALU issue time, DESIGN.md section 8a)
-#define LAUNCH_FWD(DD, KT) \
-    attn_fwd2_kernel<T, DD, KT, 4><<<dim3(mu_cdiv(N, 128), B), 256, 0, st>>>(qkv, x, kidx, kcnt, gamma, beta, out, oattn, lse2, mean, rstd, N, nkmax, sl2, eps)
+// The dtype and width dispatch of the entry points: f(T{}) with T the operand type of the sweeps (MU_F32X: xf32, fp32 storage read as
+// fp16 pairs), any other dtype MU_ERR_ARG; f(attn_width_c<D>{}) with D one of the widths the sweeps have a register tiling for, any
+// other C MU_ERR_SHAPE.
+template <typename F>
+static inline int with_attn_type(int dtype, F&& f) {
+    if (dtype == MU_F16) return f(h16{});
+    if (dtype == MU_F32) return f(float{});
+    if (dtype == MU_F32X) return f(xf32{});
+    return MU_ERR_ARG;
+}
+template <int D> using attn_width_c = std::integral_constant<int, D>;
+template <typename F>
+static inline int with_attn_width(int C, F&& f) {
     switch (C) {
-        case 32: LAUNCH_FWD(32, 64); break;
-        case 64:
-            if constexpr (std::is_same<T, xf32>::value)       // 32-key tiles: 32 KB of LDS and <= 168 registers -> three waves per SIMD
-                attn_fwd2_kernel<T, 64, 32, 4, 3><<<dim3(mu_cdiv(N, 128), B), 256, 0, st>>>(qkv, x, kidx, kcnt, gamma, beta, out, oattn, lse2, mean, rstd, N, nkmax, sl2, eps);
-            else LAUNCH_FWD(64, 64);
-            break;
-        case 128: LAUNCH_FWD(128, 32); break;
-        case 256: LAUNCH_FWD(256, 32); break;
+        case 32: return f(attn_width_c<32>{});
+        case 64: return f(attn_width_c<64>{});
+        case 128: return f(attn_width_c<128>{});
+        case 256: return f(attn_width_c<256>{});
         default: return MU_ERR_SHAPE;
     }
-#undef LAUNCH_FWD
-    if (cv != C) {           // zero-padded channels: LayerNorm over the first cv channels only (re-does the fused epilogue's out / mean / rstd)
-        using TS = typename std::conditional<std::is_same<T, xf32>::value, float, T>::type;      // storage type (no matrix product here)
-        const TS *oa = (const TS*)oattn, *xs = (const TS*)x;
-        TS* os = (TS*)out;
-        const long rows = (long)B * N;
-        const int nb = (int)(rows / 64 < 1 ? 1 : (rows / 64 > 4096 ? 4096 : rows / 64));
-        switch (C) {
-            case 32: attn_ln_fwd_kernel<TS, 32><<<nb, 256, 0, st>>>(oa, xs, gamma, beta, os, mean, rstd, rows, cv, eps); break;
-            case 64: attn_ln_fwd_kernel<TS, 64><<<nb, 256, 0, st>>>(oa, xs, gamma, beta, os, mean, rstd, rows, cv, eps); break;
-            case 128: attn_ln_fwd_kernel<TS, 128><<<nb, 256, 0, st>>>(oa, xs, gamma, beta, os, mean, rstd, rows, cv, eps); break;
-            default: attn_ln_fwd_kernel<TS, 256><<<nb, 256, 0, st>>>(oa, xs, gamma, beta, os, mean, rstd, rows, cv, eps); break;
-        }
+}
+
+// The tile choice of every sweep, per operand type and width: the one place that says which instantiation a launch takes.
+template <typename T, int D>
+struct AttnTiles {
+    static constexpr bool XF = std::is_same<T, xf32>::value;
+    // forward: keys per tile, and the waves-per-SIMD bound where it is not attn_fwd_occ<T, D>() (0).  fp32x at D = 64 takes 32-key
+    // tiles: 32 KB of LDS and <= 168 registers -> three waves per SIMD.
+    // (measured and removed: 8-wave blocks sharing each K/V tile among 256 queries, -8 %; 64 queries per wave against 32-key tiles,
+    //  -4 %; 128- / 32-key tiles and other occupancy bounds, +-0: the sweep is bound by MFMA + VALU issue time, DESIGN.md section 8a)
+    static constexpr int FWD_KT = (D >= 128 || (XF && D == 64)) ? 32 : 64;
+    static constexpr int FWD_OCC = (XF && D == 64) ? 3 : 0;
+    // dQ sweep: keys per tile (the measurements stand at attn_dq_occ)
+    static constexpr int DQ_KT = D == 32 ? 64 : 32;
+    // dK/dV sweep: 16-key tiles per wave and waves per block (16 * NKT keys each).  D = 128, fp16: 12-wave blocks = 3 waves/SIMD at 168
+    // VGPRs (in-process, N = 4096: 4 waves x 2 blocks 0.68, 8 waves 0.67, 12 waves 0.58 ms) with 16 keys per wave (NKT = 1, 150 VGPRs:
+    // 1.174 -> 0.959 ms; the 32-key version spills).  D = 128, fp32x: the 4-deep Q / dO ring takes 128 KB, so a 4-wave block is alone
+    // on its CU (one wave per SIMD: matrix pipe busy 25 %); 8 waves share the ring (two per SIMD, 16 keys each).  Everything else: 4 waves.
+    static constexpr int NKT = D <= 64 ? 2 : 1;
+    static constexpr int NWK = D != 128 ? 4 : (sizeof(T) == 2 ? 12 : (XF ? 8 : 4));
+};
+// storage type of T: what the LayerNorm passes, which hold no matrix product, are instantiated for
+template <typename T> using attn_storage_t = typename std::conditional<std::is_same<T, xf32>::value, float, T>::type;
+
+// blocks of the LayerNorm row passes: one per 64 WHOLE rows (rounded down: the passes stride over the rows), at least 1, at most `cap`
+static inline int attn_row_blocks(long rows, int cap) { const long g = rows / 64; return (int)(g < 1 ? 1 : (g > cap ? cap : g)); }
+
+// the arguments of one forward call (pointers untyped as they cross the C ABI: attn_fwd_launch gives them their type)
+struct AttnFwd {
+    const void *qkv, *x; const int *kidx, *kcnt; const float *gamma, *beta;
+    void *out, *oattn; float *lse2, *mean, *rstd;
+    int B, N, C, cv, nkmax; float eps; hipStream_t st;
+};
+
+template <typename T, int D>
+static int attn_fwd_launch(const AttnFwd& a) {
+    using TL = AttnTiles<T, D>;
+    const T* x = (const T*)a.x;
+    T *out = (T*)a.out, *oattn = (T*)a.oattn;
+    const float sl2 = (float)(1.4426950408889634 / sqrt((double)a.cv));      // 1/sqrt(channels) of the TRUE channel count (ade_semantic.py:174)
+    attn_fwd2_kernel<T, D, TL::FWD_KT, 4, TL::FWD_OCC><<<dim3(mu_cdiv(a.N, 128), a.B), 256, 0, a.st>>>((const T*)a.qkv, x, a.kidx, a.kcnt, a.gamma, a.beta, out, oattn, a.lse2, a.mean, a.rstd, a.N, a.nkmax, sl2, a.eps);
+    if (a.cv != a.C) {       // zero-padded channels: LayerNorm over the first cv channels only (re-does the fused epilogue's out / mean / rstd)
+        using TS = attn_storage_t<T>;
+        const long rows = (long)a.B * a.N;
+        attn_ln_fwd_kernel<TS, D><<<attn_row_blocks(rows, 4096), 256, 0, a.st>>>((const TS*)oattn, (const TS*)x, a.gamma, a.beta, (TS*)out, a.mean, a.rstd, rows, a.cv, a.eps);
     }
     return MU_OK;
 }
 
+// Refusal order: a null pointer, a non-positive dimension or c_valid outside 1..C is MU_ERR_ARG; then an unknown dtype is MU_ERR_ARG;
+// then a C the sweeps have no width for is MU_ERR_SHAPE.  Nothing is enqueued before the last check has passed.
 extern "C" int mu_attn_fwd_padded(const void* qkv, const void* x, const int* kidx, const int* kcnt, const float* gamma, const float* beta,
                                   void* out, void* oattn, float* lse2, float* ln_mean, float* ln_rstd, int B, int N, int C, int c_valid,
                                   int nkmax, float eps, int dtype, void* stream) {
     if (!qkv || !x || !kidx || !kcnt || !gamma || !beta || !out || !oattn || !lse2 || !ln_mean || !ln_rstd) return MU_ERR_ARG;
     if (B <= 0 || N <= 0 || nkmax <= 0 || c_valid <= 0 || c_valid > C) return MU_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (dtype == MU_F16) rc = attn_fwd_t<h16>((const h16*)qkv, (const h16*)x, kidx, kcnt, gamma, beta, (h16*)out, (h16*)oattn, lse2, ln_mean, ln_rstd, B, N, C, c_valid, nkmax, eps, st);
-    else if (dtype == MU_F32) rc = attn_fwd_t<float>((const float*)qkv, (const float*)x, kidx, kcnt, gamma, beta, (float*)out, (float*)oattn, lse2, ln_mean, ln_rstd, B, N, C, c_valid, nkmax, eps, st);
-    else if (dtype == MU_F32X) rc = attn_fwd_t<xf32>((const xf32*)qkv, (const xf32*)x, kidx, kcnt, gamma, beta, (xf32*)out, (xf32*)oattn, lse2, ln_mean, ln_rstd, B, N, C, c_valid, nkmax, eps, st);
-    else return MU_ERR_ARG;
+    const AttnFwd a = {qkv, x, kidx, kcnt, gamma, beta, out, oattn, lse2, ln_mean, ln_rstd, B, N, C, c_valid, nkmax, eps, (hipStream_t)stream};
+    const int rc = with_attn_type(dtype, [&](auto t) -> int {
+        return with_attn_width(C, [&](auto d) -> int { return attn_fwd_launch<decltype(t), decltype(d)::value>(a); });
+    });
     if (rc) return rc;
     MU_CHECK_LAUNCH();
     return MU_OK;
@@ -1472,10 +1503,31 @@ extern "C" int mu_attn_fwd(const void* qkv, const void* x, const int* kidx, cons
     return mu_attn_fwd_padded(qkv, x, kidx, kcnt, gamma, beta, out, oattn, lse2, ln_mean, ln_rstd, B, N, C, C, nkmax, eps, dtype, stream);
 }
 
+// The backward workspace: the one description of its layout (mu_attn_bwd_workspace_bytes is bytes(); nothing else offsets into it).
+// Every region size, hence every offset, is a multiple of 16 bytes for every (B, N, C) -- 16 KiB * C, 4352, 256 * B * ceil(N / 32) --
+// which is what the double2 reads of `part` and the uint4 stores of `dYe` need of a 16-byte-aligned workspace.
 #define ATT_LN_MAXBLK 1024
-static inline long attn_ln_part_bytes(int C) { return (long)ATT_LN_MAXBLK * C * 2 * sizeof(double); }
-static inline long attn_rowc_bytes(int B, int N) { return (long)B * ((N + 31) / 32) * 64 * sizeof(float); }
-static inline long attn_amax_bytes() { return (long)(ATT_LN_MAXBLK + 64) * sizeof(float); }      // per-block max|dY| + the scale (fp32x)
+struct AttnBwdWs {
+    double* part;   // [ATT_LN_MAXBLK][C][2] fp64 partial sums of the LayerNorm prepass: (block, channel, (dgamma, dbeta))
+    float* amax;    // [ATT_LN_MAXBLK] fp32x: per-block max|dY| of the prepass
+    float* gsc;     // [64] fp32x: the power-of-two scale of the encoded dY (one value; amax + ATT_LN_MAXBLK)
+    float* rowc;    // [B][ceil(N / 32)][2][32] row constants of the dK/dV sweep
+    void* dYe;      // [B][N][C] fp32x: the fp16-pair-encoded copy of dY the two sweeps read
+    static constexpr long amax_off(int C) { return (long)ATT_LN_MAXBLK * C * 2 * sizeof(double); }
+    static constexpr long rowc_off(int C) { return amax_off(C) + (ATT_LN_MAXBLK + 64) * sizeof(float); }
+    static constexpr long dye_off(int B, int N, int C) { return rowc_off(C) + (long)B * ((N + 31) / 32) * 64 * sizeof(float); }
+    static constexpr long bytes(int B, int N, int C) { return (long)ATT_LN_MAXBLK * C * 2 * sizeof(double) + (long)(ATT_LN_MAXBLK + 64) * sizeof(float) + (long)B * ((N + 31) / 32) * 64 * sizeof(float) + (long)B * N * C * (long)sizeof(float); }
+    AttnBwdWs(void* ws, int B, int N, int C) : part((double*)ws), amax((float*)((char*)ws + amax_off(C))), gsc(amax + ATT_LN_MAXBLK),
+                                               rowc((float*)((char*)ws + rowc_off(C))), dYe((char*)ws + dye_off(B, N, C)) {}
+};
+// the last region ends at bytes(), the size external callers allocate by; the offsets keep 16-byte alignment
+static_assert(AttnBwdWs::dye_off(2, 64, 32) + 2L * 64 * 32 * sizeof(float) == AttnBwdWs::bytes(2, 64, 32) &&
+              AttnBwdWs::dye_off(3, 36, 128) + 3L * 36 * 128 * sizeof(float) == AttnBwdWs::bytes(3, 36, 128), "attention backward workspace layout");
+static_assert(AttnBwdWs::amax_off(32) % 16 == 0 && AttnBwdWs::rowc_off(32) % 16 == 0 && AttnBwdWs::dye_off(3, 36, 128) % 16 == 0 &&
+              AttnBwdWs::dye_off(1, 1, 256) % 16 == 0, "attention backward workspace alignment");
+
+extern "C" long mu_attn_bwd_workspace_bytes(int B, int N, int C) { return AttnBwdWs::bytes(B, N, C); }
+
 // the sweeps compute 2^pshift P (fp32x): typical probabilities ~1/N land near 1, P <= 1 stays below 2^12
 static inline float attn_pshift(int N) {
     int j = 0;
@@ -1483,69 +1535,56 @@ static inline float attn_pshift(int N) {
     j -= 2;
     return (float)(j < 0 ? 0 : (j > 12 ? 12 : j));
 }
-// LayerNorm partials | max|dY| partials + scale | row constants of the dK/dV sweep | (MU_F32X) the fp16-pair-encoded copy of dY the two sweeps read
-extern "C" long mu_attn_bwd_workspace_bytes(int B, int N, int C) {
-    return attn_ln_part_bytes(C) + attn_amax_bytes() + attn_rowc_bytes(B, N) + (long)B * N * C * (long)sizeof(float);
-}
 
-template <typename T>
-static int attn_bwd_t(const T* qkv, const T* x, const T* oattn, const T* gout, const int* kidx, const int* kcnt, const float* lse2,
-                      const float* mean, const float* rstd, const float* gamma, T* dY, float* delta, T* dqkv, float* dgamma,
-                      float* dbeta, int B, int N, int C, int cv, int nkmax, void* ws, hipStream_t st, int phases) {
-    using TS = typename std::conditional<std::is_same<T, xf32>::value, float, T>::type;      // storage type for the LayerNorm prepass
-    const long rows = (long)B * N;
-    float* amaxp = (float*)((char*)ws + attn_ln_part_bytes(C));
-    float* gsc = amaxp + ATT_LN_MAXBLK;
-    float* rowc = (float*)((char*)ws + attn_ln_part_bytes(C) + attn_amax_bytes());
-    constexpr bool XF = std::is_same<T, xf32>::value;
+// the arguments of one backward call (see AttnFwd)
+struct AttnBwd {
+    const void *qkv, *x, *oattn, *gout; const int *kidx, *kcnt; const float *lse2, *mean, *rstd, *gamma;
+    void* dY; float* delta; void* dqkv; float *dgamma, *dbeta;
+    int B, N, C, cv, nkmax; void* ws; int phases; hipStream_t st;
+};
+
+template <typename T, int D>
+static int attn_bwd_launch(const AttnBwd& a) {
+    using TL = AttnTiles<T, D>;
+    using TS = attn_storage_t<T>;                            // the LayerNorm prepass
+    constexpr bool XF = TL::XF;
+    const AttnBwdWs w(a.ws, a.B, a.N, D);
+    const int N = a.N, nkmax = a.nkmax;
+    const long rows = (long)a.B * N;
     const float pshift = XF ? attn_pshift(N) : 0.f;
-    int nblk = (int)(rows / 64 < 1 ? 1 : (rows / 64 > ATT_LN_MAXBLK ? ATT_LN_MAXBLK : rows / 64));
-    const float scale = (float)(1.0 / sqrt((double)cv));
-    const float sl2 = (float)(1.4426950408889634 / sqrt((double)cv));
-    dim3 gq(mu_cdiv(N, 128), B);
+    const float scale = (float)(1.0 / sqrt((double)a.cv));
+    const float sl2 = (float)(1.4426950408889634 / sqrt((double)a.cv));
     // phases & 8 (MU_ATTN_KIDX_PERMUTATION): every kidx row is a whole permutation of 0..N-1 with the masked keys after the kept
     // ones, so the dK/dV sweep writes the masked keys' zero rows itself (dQ parts are written for every row by the dQ sweep)
     // phases & 16 (MU_ATTN_DQKV_ENCODED, MU_F32X only): dqkv is written in the chunk encoding the projection's data- and weight-gradient
     // kernels read (mu_split_encode form) instead of plain fp32 -- saves the separate encoding pass over the largest tensor of the block
-    const int enc_out = (XF && (phases & 16)) ? 1 : 0;
-    const int zero_masked = (((phases & 8) && nkmax == N) ? 1 : 0) | (enc_out << 1);
-    if ((phases & 1) && !(zero_masked & 1) && hipMemsetAsync(dqkv, 0, (size_t)rows * 3 * C * sizeof(T), st) != hipSuccess) return MU_ERR_LAUNCH;
-    // fp32x: the sweeps take dY chunk-encoded like qkv (the caller encodes qkv; dY is produced here, by phase 1): its encoded copy
-    // lives in the workspace behind the row constants, and `dYs` is what the sweeps read
-    const T* dYs = dY;
-    if constexpr (XF) dYs = (const T*)((char*)ws + attn_ln_part_bytes(C) + attn_amax_bytes() + attn_rowc_bytes(B, N));
-    // dK/dV waves per block (16 * NKT keys each).  C = 128, fp16: 12-wave blocks = 3 waves/SIMD at 168 VGPRs (in-process, N = 4096: 4 waves
-    // x 2 blocks 0.68, 8 waves 0.67, 12 waves 0.58 ms) with 16 keys per wave (NKT = 1, 150 VGPRs: 1.174 -> 0.959 ms; the 32-key version spills).
-    // C = 128, fp32x: the 4-deep Q / dO ring takes 128 KB, so a 4-wave block is alone on its CU (one wave per SIMD: matrix pipe busy 25 %);
-    // 8 waves share the ring (two per SIMD, 16 keys each).  Everything else: 4 waves.
-#define LAUNCH_BWD(DD, NKT)                                                                                                     \
-    if (phases & 1) {                                                                                                           \
-        attn_ln_bwd_kernel<TS, DD><<<nblk, 256, 0, st>>>((const TS*)gout, (const TS*)oattn, (const TS*)x, mean, rstd, gamma, (TS*)dY, delta, (double*)ws, rows, lse2, rowc, N, scale, cv, pshift, XF ? amaxp : nullptr); \
-        attn_ln_bwd_final_kernel<<<mu_cdiv(DD, 4), 256, 0, st>>>((const double*)ws, nblk, DD, dgamma, dbeta, XF ? amaxp : nullptr, gsc); \
-        if constexpr (XF) {                                                                                                     \
-            const long ng = rows * DD / 8;                                                                                      \
-            const long gr = (ng + 511) / 512;                                                                                   \
-            attn_dy_encode_kernel<<<(int)(gr < 1 ? 1 : (gr > 8192 ? 8192 : gr)), 256, 0, st>>>((const f32x4*)dY, (uint4*)dYs, rowc, gsc, ng, DD / 8, N); \
-        }                                                                                                                       \
-    }                                                                                                                           \
-    if (phases & 2)                                                                                                             \
-        attn_bwd_dq2_kernel<T, DD, KTQ, 4><<<gq, 256, 0, st>>>(qkv, dYs, kidx, kcnt, lse2, delta, dqkv, N, nkmax, scale, sl2, gsc, pshift, enc_out); \
-    if (phases & 4) {                                                                                                           \
-        constexpr int NWK = DD != 128 ? 4 : (sizeof(T) == 2 ? 12 : (XF ? 8 : 4));                                               \
-        attn_bwd_dkv3_kernel<T, DD, NKT, NWK><<<dim3(mu_cdiv(nkmax, 16 * NWK * NKT), B), 64 * NWK, 0, st>>>(qkv, dYs, kidx, kcnt, rowc, dqkv, N, nkmax, scale, sl2, zero_masked, gsc, pshift); \
+    const int enc_out = (XF && (a.phases & 16)) ? 1 : 0;
+    const int zero_masked = (((a.phases & 8) && nkmax == N) ? 1 : 0) | (enc_out << 1);
+    const T* qkv = (const T*)a.qkv;
+    T* dqkv = (T*)a.dqkv;
+    // fp32x: the sweeps take dY encoded like qkv (the caller encodes qkv; dY is produced here, by phase 1): `dYs` is what they read
+    const T* dYs = (const T*)(XF ? w.dYe : a.dY);
+    if (a.phases & 1) {
+        if (!(zero_masked & 1) && hipMemsetAsync(dqkv, 0, (size_t)rows * 3 * D * sizeof(T), a.st) != hipSuccess) return MU_ERR_LAUNCH;
+        const int nblk = attn_row_blocks(rows, ATT_LN_MAXBLK);
+        TS* dY = (TS*)a.dY;
+        attn_ln_bwd_kernel<TS, D><<<nblk, 256, 0, a.st>>>((const TS*)a.gout, (const TS*)a.oattn, (const TS*)a.x, a.mean, a.rstd, a.gamma, dY, a.delta, w.part, rows, a.lse2, w.rowc, N, scale, a.cv, pshift, XF ? w.amax : nullptr);
+        attn_ln_bwd_final_kernel<<<mu_cdiv(D, 4), 256, 0, a.st>>>(w.part, nblk, D, a.dgamma, a.dbeta, XF ? w.amax : nullptr, w.gsc);
+        if constexpr (XF) {
+            const long ng = rows * D / 8;
+            attn_dy_encode_kernel<<<mu_grid(ng, 512, 8192), 256, 0, a.st>>>((const f32x4*)dY, (uint4*)w.dYe, w.rowc, w.gsc, ng, D / 8, N);
+        }
     }
-    if (N % 4) return MU_ERR_SHAPE;
-    switch (C) {
-        case 32: { constexpr int KTQ = 64; LAUNCH_BWD(32, 2); } break;
-        case 64: { constexpr int KTQ = 32; LAUNCH_BWD(64, 2); } break;
-        case 128: { constexpr int KTQ = 32; LAUNCH_BWD(128, 1); } break;
-        case 256: { constexpr int KTQ = 32; LAUNCH_BWD(256, 1); } break;
-        default: return MU_ERR_SHAPE;
-    }
-#undef LAUNCH_BWD
+    if (a.phases & 2)
+        attn_bwd_dq2_kernel<T, D, TL::DQ_KT, 4><<<dim3(mu_cdiv(N, 128), a.B), 256, 0, a.st>>>(qkv, dYs, a.kidx, a.kcnt, a.lse2, a.delta, dqkv, N, nkmax, scale, sl2, w.gsc, pshift, enc_out);
+    if (a.phases & 4)
+        attn_bwd_dkv3_kernel<T, D, TL::NKT, TL::NWK><<<dim3(mu_cdiv(nkmax, 16 * TL::NWK * TL::NKT), a.B), 64 * TL::NWK, 0, a.st>>>(qkv, dYs, a.kidx, a.kcnt, w.rowc, dqkv, N, nkmax, scale, sl2, zero_masked, w.gsc, pshift);
     return MU_OK;
 }
 
+// Refusal order: a null pointer, a non-positive dimension or c_valid outside 1..C is MU_ERR_ARG; then a workspace below
+// mu_attn_bwd_workspace_bytes is MU_ERR_WORKSPACE; then an unknown dtype is MU_ERR_ARG; then N % 4 or a C the sweeps have no width for
+// is MU_ERR_SHAPE.  Nothing is enqueued -- the memset of dqkv included -- before the last check has passed.  `phases` is not validated.
 extern "C" int mu_attn_bwd_phases_padded(const void* qkv, const void* x, const void* oattn, const void* grad_out, const int* kidx, const int* kcnt,
                            const float* lse2, const float* ln_mean, const float* ln_rstd, const float* gamma, void* dY, float* delta,
                            void* dqkv, float* dgamma, float* dbeta, int B, int N, int C, int c_valid, int nkmax, void* workspace, long ws_bytes,
@@ -1554,16 +1593,13 @@ extern "C" int mu_attn_bwd_phases_padded(const void* qkv, const void* x, const v
         !dgamma || !dbeta || !workspace)
         return MU_ERR_ARG;
     if (B <= 0 || N <= 0 || nkmax <= 0 || c_valid <= 0 || c_valid > C) return MU_ERR_ARG;
-    if (ws_bytes < mu_attn_bwd_workspace_bytes(B, N, C)) return MU_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (dtype == MU_F16)
-        rc = attn_bwd_t<h16>((const h16*)qkv, (const h16*)x, (const h16*)oattn, (const h16*)grad_out, kidx, kcnt, lse2, ln_mean, ln_rstd, gamma, (h16*)dY, delta, (h16*)dqkv, dgamma, dbeta, B, N, C, c_valid, nkmax, workspace, st, phases);
-    else if (dtype == MU_F32)
-        rc = attn_bwd_t<float>((const float*)qkv, (const float*)x, (const float*)oattn, (const float*)grad_out, kidx, kcnt, lse2, ln_mean, ln_rstd, gamma, (float*)dY, delta, (float*)dqkv, dgamma, dbeta, B, N, C, c_valid, nkmax, workspace, st, phases);
-    else if (dtype == MU_F32X)
-        rc = attn_bwd_t<xf32>((const xf32*)qkv, (const xf32*)x, (const xf32*)oattn, (const xf32*)grad_out, kidx, kcnt, lse2, ln_mean, ln_rstd, gamma, (xf32*)dY, delta, (xf32*)dqkv, dgamma, dbeta, B, N, C, c_valid, nkmax, workspace, st, phases);
-    else return MU_ERR_ARG;
+    if (ws_bytes < AttnBwdWs::bytes(B, N, C)) return MU_ERR_WORKSPACE;
+    const AttnBwd a = {qkv, x, oattn, grad_out, kidx, kcnt, lse2, ln_mean, ln_rstd, gamma, dY, delta, dqkv, dgamma, dbeta,
+                       B, N, C, c_valid, nkmax, workspace, phases, (hipStream_t)stream};
+    const int rc = with_attn_type(dtype, [&](auto t) -> int {
+        if (N % 4) return MU_ERR_SHAPE;
+        return with_attn_width(C, [&](auto d) -> int { return attn_bwd_launch<decltype(t), decltype(d)::value>(a); });
+    });
     if (rc) return rc;
     MU_CHECK_LAUNCH();
     return MU_OK;

@@ -148,68 +148,75 @@ __global__ __launch_bounds__(256) void ln_rows_bwd_kernel(const T* __restrict__ 
     }
 }
 
-static inline int wide_grid(long n) { return (int)(n < 1 ? 1 : (n > 4096 ? 4096 : n)); }
-#define WIDE_DISPATCH(dtype, CALL16, CALL32)                 \
-    if ((dtype) == MU_F16) { CALL16; }                       \
-    else if ((dtype) == MU_F32 || (dtype) == MU_F32X) { CALL32; } \
-    else return MU_ERR_ARG;
+// Host entry points: argument check (MU_ERR_ARG), then the storage dispatch (an unknown dtype is MU_ERR_ARG too), then one launch of at
+// most 4096 blocks.  No matrix product in this file: MU_F32X is plain fp32.
+template <typename F>
+static inline int with_wide_storage(int dtype, F&& f) {
+    return with_storage(dtype == MU_F32X ? MU_F32 : dtype, f);
+}
 
 extern "C" int mu_gather_rows(const void* src, long src_ld, const int* idx, const int* cnt, void* dst, int rows_out, int C, int dtype,
                               void* stream) {
     if (!src || !idx || !cnt || !dst || rows_out <= 0 || C <= 0 || src_ld < C) return MU_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    WIDE_DISPATCH(dtype, (gather_rows_kernel<h16><<<wide_grid(rows_out), 256, 0, st>>>((const h16*)src, src_ld, idx, cnt, (h16*)dst, rows_out, C)),
-                  (gather_rows_kernel<float><<<wide_grid(rows_out), 256, 0, st>>>((const float*)src, src_ld, idx, cnt, (float*)dst, rows_out, C)))
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    return with_wide_storage(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        gather_rows_kernel<T><<<mu_grid(rows_out, 1, 4096), 256, 0, (hipStream_t)stream>>>((const T*)src, src_ld, idx, cnt, (T*)dst, rows_out, C);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 extern "C" int mu_scatter_rows(const float* src, const int* idx, const int* cnt, void* dst, long dst_ld, int dst_rows, int C, int dtype,
                                void* stream) {
     if (!src || !idx || !cnt || !dst || dst_rows <= 0 || C <= 0 || dst_ld < C) return MU_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    WIDE_DISPATCH(dtype, (scatter_rows_kernel<h16><<<wide_grid(dst_rows), 256, 0, st>>>(src, idx, cnt, (h16*)dst, dst_ld, dst_rows, C)),
-                  (scatter_rows_kernel<float><<<wide_grid(dst_rows), 256, 0, st>>>(src, idx, cnt, (float*)dst, dst_ld, dst_rows, C)))
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    return with_wide_storage(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        scatter_rows_kernel<T><<<mu_grid(dst_rows, 1, 4096), 256, 0, (hipStream_t)stream>>>(src, idx, cnt, (T*)dst, dst_ld, dst_rows, C);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 extern "C" int mu_softmax_rows(void* S, int N, int ld, const int* cnt, float scale, int dtype, void* stream) {
     if (!S || !cnt || N <= 0 || ld <= 0) return MU_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    WIDE_DISPATCH(dtype, (softmax_rows_kernel<h16><<<wide_grid(N), 256, 0, st>>>((h16*)S, N, ld, cnt, scale)),
-                  (softmax_rows_kernel<float><<<wide_grid(N), 256, 0, st>>>((float*)S, N, ld, cnt, scale)))
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    return with_wide_storage(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        softmax_rows_kernel<T><<<mu_grid(N, 1, 4096), 256, 0, (hipStream_t)stream>>>((T*)S, N, ld, cnt, scale);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 extern "C" int mu_attn_wide_ds(const void* P, void* dP, int N, int ld, const int* cnt, float scale, int dtype, void* stream) {
     if (!P || !dP || !cnt || N <= 0 || ld <= 0) return MU_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    WIDE_DISPATCH(dtype, (attn_wide_ds_kernel<h16><<<wide_grid(N), 256, 0, st>>>((const h16*)P, (h16*)dP, N, ld, cnt, scale)),
-                  (attn_wide_ds_kernel<float><<<wide_grid(N), 256, 0, st>>>((const float*)P, (float*)dP, N, ld, cnt, scale)))
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    return with_wide_storage(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        attn_wide_ds_kernel<T><<<mu_grid(N, 1, 4096), 256, 0, (hipStream_t)stream>>>((const T*)P, (T*)dP, N, ld, cnt, scale);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
+// the LayerNorm passes: one wave per row, four rows per block
 extern "C" int mu_ln_rows_fwd(const void* o, const void* x, const float* gamma, const float* beta, void* out, float* mean, float* rstd,
                               long rows, int C, int c_valid, float eps, int dtype, void* stream) {
     if (!o || !x || !gamma || !beta || !out || !mean || !rstd || rows <= 0 || C <= 0 || c_valid <= 0 || c_valid > C) return MU_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    const int grid = wide_grid((rows + 3) / 4);
-    WIDE_DISPATCH(dtype, (ln_rows_fwd_kernel<h16><<<grid, 256, 0, st>>>((const h16*)o, (const h16*)x, gamma, beta, (h16*)out, mean, rstd, rows, C, c_valid, eps)),
-                  (ln_rows_fwd_kernel<float><<<grid, 256, 0, st>>>((const float*)o, (const float*)x, gamma, beta, (float*)out, mean, rstd, rows, C, c_valid, eps)))
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    return with_wide_storage(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        ln_rows_fwd_kernel<T><<<mu_grid(rows, 4, 4096), 256, 0, (hipStream_t)stream>>>((const T*)o, (const T*)x, gamma, beta, (T*)out, mean, rstd, rows, C, c_valid, eps);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
 
 extern "C" int mu_ln_rows_bwd(const void* grad_out, const void* o, const void* x, const float* mean, const float* rstd, const float* gamma,
                               void* dY, void* g_xhat, long rows, int C, int c_valid, int dtype, void* stream) {
     if (!grad_out || !o || !x || !mean || !rstd || !gamma || !dY || !g_xhat || rows <= 0 || C <= 0 || c_valid <= 0 || c_valid > C) return MU_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    const int grid = wide_grid((rows + 3) / 4);
-    WIDE_DISPATCH(dtype, (ln_rows_bwd_kernel<h16><<<grid, 256, 0, st>>>((const h16*)grad_out, (const h16*)o, (const h16*)x, mean, rstd, gamma, (h16*)dY, (h16*)g_xhat, rows, C, c_valid)),
-                  (ln_rows_bwd_kernel<float><<<grid, 256, 0, st>>>((const float*)grad_out, (const float*)o, (const float*)x, mean, rstd, gamma, (float*)dY, (float*)g_xhat, rows, C, c_valid)))
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    return with_wide_storage(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        ln_rows_bwd_kernel<T><<<mu_grid(rows, 4, 4096), 256, 0, (hipStream_t)stream>>>((const T*)grad_out, (const T*)o, (const T*)x, mean, rstd, gamma, (T*)dY, (T*)g_xhat, rows, C, c_valid);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
+

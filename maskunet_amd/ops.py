@@ -1124,6 +1124,30 @@ def _transpose_tokens(src, R, C):
     return dst
 
 
+def _pad_param(t, C):
+    """A [cv, cv] weight or [cv] vector of a block stored wider than its channel count: fp32, zero-padded to C in every dimension."""
+    return F.pad(t.detach().float(), [p for n in reversed(t.shape) for p in (0, C - n)])
+
+
+def _refuse_padded_scramble(scramble, cv, C):
+    if scramble and cv != C:
+        raise RuntimeError("mask_attention: the re-viewed (scrambled) output needs an unpadded channel count")
+
+
+def _attn_entry(name, cv, head, tail):
+    """`name(*head, *tail)` where the cv channels fill the stored width (the C that `head` ends with), else `name_padded(*head, cv, *tail)`."""
+    if cv == head[-1]:
+        call(name, *head, *tail)
+    else:
+        call(name + "_padded", *head, cv, *tail)
+
+
+def _attn_grads(gx, gw, gb, dg, db, C, cv, n_rest):
+    """Either backward's return: gx, q / k / v weight and bias gradients out of the fused [3C, C] / [3C] ones and LayerNorm's, cut to cv."""
+    return (gx, gw[:cv, :cv], gb[:cv], gw[C:C + cv, :cv], gb[C:C + cv], gw[2 * C:2 * C + cv, :cv], gb[2 * C:2 * C + cv],
+            dg[:cv], db[:cv]) + (None,) * n_rest
+
+
 class _MaskAttention(torch.autograd.Function):
     """Mask2FormerAttention.forward (ade_semantic.py:163-190) on an NHWC activation.
 
@@ -1142,11 +1166,8 @@ class _MaskAttention(torch.autograd.Function):
         if cv != C:
             # a channel count the kernels have no width for: every parameter zero-padded to C (slow path, torch pads; standalone
             # Mask2FormerAttention only -- the UNet's blocks are 64 / 128 / 256 wide)
-            if scramble:
-                raise RuntimeError("mask_attention: the re-viewed (scrambled) output needs an unpadded channel count")
-            pw = lambda w: F.pad(w.detach().float(), (0, C - cv, 0, C - cv))      # noqa: E731
-            pv = lambda v: F.pad(v.detach().float(), (0, C - cv))                # noqa: E731
-            wq, wk, wv, bq, bk, bv, lnw, lnb = pw(wq), pw(wk), pw(wv), pv(bq), pv(bk), pv(bv), pv(lnw), pv(lnb)
+            _refuse_padded_scramble(scramble, cv, C)
+            wq, wk, wv, bq, bk, bv, lnw, lnb = (_pad_param(t, C) for t in (wq, wk, wv, bq, bk, bv, lnw, lnb))
             cache_ok = False
 
         def make_qkv():          # the three Linear layers as one [3C, C] 1x1 layer: forward + data-gradient layouts and the bias, one launch
@@ -1179,12 +1200,8 @@ class _MaskAttention(torch.autograd.Function):
         lse2 = torch.empty((B, N), dtype=torch.float32, device=x.device)
         mean, rstd = torch.empty_like(lse2), torch.empty_like(lse2)
         g, b_ = lnw.detach().float().contiguous(), lnb.detach().float().contiguous()
-        if cv == C:
-            call("mu_attn_fwd", ptr(qkv), ptr(x), ptr(kidx), ptr(kcnt), ptr(g), ptr(b_), ptr(out), ptr(oattn), ptr(lse2), ptr(mean),
-                 ptr(rstd), B, N, C, kidx.shape[1], float(eps), mdt(x), stream())
-        else:
-            call("mu_attn_fwd_padded", ptr(qkv), ptr(x), ptr(kidx), ptr(kcnt), ptr(g), ptr(b_), ptr(out), ptr(oattn), ptr(lse2), ptr(mean),
-                 ptr(rstd), B, N, C, cv, kidx.shape[1], float(eps), mdt(x), stream())
+        _attn_entry("mu_attn_fwd", cv, (ptr(qkv), ptr(x), ptr(kidx), ptr(kcnt), ptr(g), ptr(b_), ptr(out), ptr(oattn), ptr(lse2), ptr(mean),
+                                        ptr(rstd), B, N, C), (kidx.shape[1], float(eps), mdt(x), stream()))
         ctx.save_for_backward(x, qkv, oattn, lse2, mean, rstd, g, kidx, kcnt, xe)
         ctx.is_x = _is_x(x)
         ctx.scramble, ctx.dims, ctx.kidx_perm = scramble, (B, H, W, C), bool(kidx_perm) and kidx.shape[1] == N
@@ -1217,16 +1234,10 @@ class _MaskAttention(torch.autograd.Function):
         enc_dqkv = ctx.is_x and DQKV_ENCODED
         if enc_dqkv:
             perm |= 16
-        cv = ctx.cv
         for phase in (1, 2, 4):      # LayerNorm-backward prepass, dQ sweep, dK/dV sweep (separate calls: each can be timed)
-            if cv == C:
-                call("mu_attn_bwd_phases", ptr(qkv), ptr(x), ptr(oattn), ptr(gout), ptr(kidx), ptr(kcnt), ptr(lse2), ptr(mean), ptr(rstd),
-                     ptr(g), ptr(dY), ptr(delta), ptr(dqkv), ptr(dg), ptr(db), B, N, C, kidx.shape[1], ptr(ws), ws.numel(), mdt(x),
-                     phase | perm, stream())
-            else:
-                call("mu_attn_bwd_phases_padded", ptr(qkv), ptr(x), ptr(oattn), ptr(gout), ptr(kidx), ptr(kcnt), ptr(lse2), ptr(mean),
-                     ptr(rstd), ptr(g), ptr(dY), ptr(delta), ptr(dqkv), ptr(dg), ptr(db), B, N, C, cv, kidx.shape[1], ptr(ws), ws.numel(),
-                     mdt(x), phase | perm, stream())
+            _attn_entry("mu_attn_bwd_phases", ctx.cv, (ptr(qkv), ptr(x), ptr(oattn), ptr(gout), ptr(kidx), ptr(kcnt), ptr(lse2), ptr(mean),
+                                                       ptr(rstd), ptr(g), ptr(dY), ptr(delta), ptr(dqkv), ptr(dg), ptr(db), B, N, C),
+                        (kidx.shape[1], ptr(ws), ws.numel(), mdt(x), phase | perm, stream()))
         dqkv4 = dqkv.view(B, H, W, 3 * C)
         dqkv_e = dqkv4 if enc_dqkv else _enc(dqkv4)      # fp32x: dqkv as a matrix operand (projection data- and weight-gradient); dqkv4 otherwise
         gx = None
@@ -1245,10 +1256,7 @@ class _MaskAttention(torch.autograd.Function):
         else:
             gw = _wgrad_raw(xe, dqkv_e, (3 * C, C, 1, 1), 1, gy_enc=True, x_enc=ctx.is_x).view(3 * C, C)
             gb = _colsum(dqkv4, 3 * C, encoded=enc_dqkv)
-        if cv != C:                  # gradients of the real (unpadded) parameters
-            return (gx, gw[:cv, :cv], gb[:cv], gw[C:C + cv, :cv], gb[C:C + cv], gw[2 * C:2 * C + cv, :cv], gb[2 * C:2 * C + cv],
-                    dg[:cv], db[:cv], None, None, None, None, None, None)
-        return (gx, gw[:C], gb[:C], gw[C:2 * C], gb[C:2 * C], gw[2 * C:], gb[2 * C:], dg, db, None, None, None, None, None, None)
+        return _attn_grads(gx, gw, gb, dg, db, C, ctx.cv, 6)
 
 
 ATTN_FUSED_ADD = os.environ.get("MU_ATTN_FUSED_ADD", "1") != "0"      # debug switch: 0 = projection data-gradient + mu_add
@@ -1304,14 +1312,11 @@ class _WideMaskAttention(torch.autograd.Function):
         B, H, W, C = x.shape
         N = H * W
         cv = wq.shape[0]
-        if scramble and cv != C:
-            raise RuntimeError("mask_attention: the re-viewed (scrambled) output needs an unpadded channel count")
+        _refuse_padded_scramble(scramble, cv, C)
         code = _lib.MU_F16 if x.dtype == torch.float16 else _lib.MU_F32
-        pw = lambda w: F.pad(w.detach().float(), (0, C - cv, 0, C - cv))      # noqa: E731
-        pv = lambda v: F.pad(v.detach().float(), (0, C - cv))                # noqa: E731
-        wqkv = torch.cat([pw(wq), pw(wk), pw(wv)], 0).to(x.dtype).contiguous()          # [3C, C]
-        bqkv = torch.cat([pv(bq), pv(bk), pv(bv)]).contiguous()
-        g, b_ = pv(lnw).contiguous(), pv(lnb).contiguous()
+        wqkv = torch.cat([_pad_param(w, C) for w in (wq, wk, wv)], 0).to(x.dtype).contiguous()          # [3C, C]
+        bqkv = torch.cat([_pad_param(v, C) for v in (bq, bk, bv)]).contiguous()
+        g, b_ = _pad_param(lnw, C).contiguous(), _pad_param(lnb, C).contiguous()
         qkv = torch.empty((B, N, 3 * C), dtype=x.dtype, device=x.device)
         _gemm_nt(x, C, B * N, C, wqkv, 3 * C, qkv, 3 * C, code, bias=bqkv)
         nk = pad32(kidx.shape[1])
@@ -1381,8 +1386,7 @@ class _WideMaskAttention(torch.autograd.Function):
             call("mu_add", ptr(gx), ptr(dY), ptr(gx), gx.numel(), dt(gx), stream())
         gw = _gemm_tn(x, C, dqkv, 3 * C, B * N, C, 3 * C, code)                                      # [3C, C]
         gb = _colsum_wide(dqkv.view(B * N, 3 * C))
-        return (gx, gw[:cv, :cv], gb[:cv], gw[C:C + cv, :cv], gb[C:C + cv], gw[2 * C:2 * C + cv, :cv], gb[2 * C:2 * C + cv],
-                dg[:cv], db[:cv], None, None, None, None)
+        return _attn_grads(gx, gw, gb, dg, db, C, cv, 4)
 
 
 def mask_attention(x, q, k, v, norm, kidx, kcnt, scramble=True, kidx_perm=False):

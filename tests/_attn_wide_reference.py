@@ -321,7 +321,7 @@ def cnt_set(ld):
 
 
 def gather_cases():
-    """(C, src_ld, rows_out, cnt): every channel count and stride at 1 and 32 rows; 4100 rows (beyond wide_grid's 4096 blocks) at C = 8"""
+    """(C, src_ld, rows_out, cnt): every channel count and stride at 1 and 32 rows; 4100 rows (beyond the grid cap of 4096 blocks) at C = 8"""
     out = []
     for C in C_SET:
         for ld in (C, 3 * C):
