@@ -512,6 +512,55 @@ long mu_sem_eval_workspace_bytes(int B, long HW, int C);
 int mu_sem_eval(const void* logits, const long* labels, int B, long HW, int C, long inner, long outer_stride, long c_stride,
                 long p_stride, long ignore_index, float inv_temperature, int* img_counts, double* img_loss, long* confusion,
                 int* cls_or_null, float* prob_or_null, void* workspace, long ws_bytes, int dtype, void* stream);
+/* Semantic evaluation at the labels' OWN resolution: what ADE20K, Cityscapes and COCO define as mIoU.  The logits of image b are upsampled
+ * bilinearly to the size of that image's label map, the first arg-max is taken there and counted against the labels, in one kernel that
+ * never writes the upsampled logits.  This text is the specification.
+ * logits: B images of h x w pixels and C real classes, element (pixel r of M = B * h * w, class c) at
+ * logits[(r / inner) * outer_stride + c * c_stride + (r % inner) * p_stride] exactly as mu_sem_eval (NCHW, or the channel-padded NHWC rows
+ * of a module output); MU_F32 or MU_F16; the values must be finite.  Labels: a ragged uint8 batch as mu_pil_resize_u8_nhwc takes one --
+ * image b is the H_b * W_b bytes at labels + offsets[b], (H_b, W_b) = sizes[b][0..1]; offsets int64 [B+1] in bytes and sizes int32 [B][2]
+ * are DEVICE arrays, image starts need no alignment, and the host passes only the bounds max_h, max_w.  ignore_index: any value outside
+ * [0, 255] means "none".
+ * Rule per image b and output pixel (Y, X); every fp32 operation is rounded on its own (NO fused multiply-add), fp16 logits are widened
+ * exactly to fp32:
+ *   sy = fp32(h) / fp32(H_b)                      (IEEE division; sx likewise from w, W_b)
+ *   fy = max(sy * (fp32(Y) + 0.5f) - 0.5f, 0.0f)
+ *   y0 = min((int)fy, h - 1);  y1 = y0 + (y0 < h - 1);  ly1 = fy - fp32(y0);  ly0 = 1.0f - ly1        (x0, x1, lx0, lx1 likewise)
+ *   v_c  = ly0 * (lx0 * x[c,y0,x0] + lx1 * x[c,y0,x1]) + ly1 * (lx0 * x[c,y1,x0] + lx1 * x[c,y1,x1])
+ *   pred = the first c in ascending order with the largest v_c      (strict > replaces; padded channels are never read)
+ * This is the formula of torch's upsample_bilinear2d(align_corners=False).  It agrees with torch bit for bit where the arithmetic is
+ * exact, and only to within rounding elsewhere (tests/test_native_eval_host.py holds both comparisons).
+ *   void       a pixel is void if its label equals ignore_index or is >= C;
+ *   REFUSED    image b is refused, exactly as in mu_pil_resize_u8_nhwc, if H_b or W_b lies outside [1, max_h] / [1, max_w], if
+ *              offsets[b] < 0 or if offsets[b+1] - offsets[b] < H_b * W_b: valid[b] = 0, nothing of it is read, it adds nothing to
+ *              confusion, its img_counts are zero and its class-map bytes are not written;
+ *   img_counts int32 [B][3][C], overwritten: I_c, P_c, L_c with the meaning of mu_sem_eval (P counts every pixel, I and L only the
+ *              non-void ones);
+ *   confusion  int64 [C+1][C], ADDED TO: row = the label, or C for void; column = pred;
+ *   valid      uint8 [B];
+ *   classes_or_null  uint8, laid out like labels with the same offsets: pred at native resolution (what a labelIds PNG submission is made
+ *              from).  Bytes between two images (offsets that leave gaps) are never written.
+ * Integer atomics only: every output is bit-identical from run to run.  Two launches (image descriptors into the workspace, then one
+ * workgroup per MU_SEM_NATIVE_TILE_H x MU_SEM_NATIVE_TILE_W tile of the bounds), stream-ordered, no host synchronisation, capturable.  A
+ * workgroup stages the source window of its tile in LDS as fp32 where C * (window pixels | 1) * 4 <= min(MU_SEM_NATIVE_WINDOW_BYTES,
+ * C * (h * w | 1) * 4) =: S and reads the same taps from global memory otherwise; it keeps the (C+1) x C counters in LDS where
+ * (3 * C + ceil((C + 1) * C / 2)) * 4 + S <= MU_SEM_NATIVE_LDS_BYTES and adds one 64-bit global atomic per pixel otherwise.  Every path gives
+ * the same results.
+ * Limits: B >= 1, 1 <= C <= 256 (labels and the class map are bytes), h, w >= 1, h * w <= 65536 (mu_sem_eval_native_supported, else
+ * MU_ERR_SHAPE), 1 <= max_h, max_w <= 16384.  A null pointer (classes_or_null apart), a workspace that is not 8-byte aligned, a scalar
+ * outside the limits, inner < 1 or a dtype other than MU_F32 / MU_F16: MU_ERR_ARG; a grid beyond 2^31 - 1 tiles: MU_ERR_SHAPE; a short
+ * workspace: MU_ERR_WORKSPACE; all before the first launch.  mu_sem_eval_native_supported and mu_sem_eval_native_workspace_bytes are host
+ * only; the latter is 0 for unsupported arguments. */
+#define MU_SEM_NATIVE_TILE_H 16
+#define MU_SEM_NATIVE_TILE_W 64
+#define MU_SEM_NATIVE_WINDOW_BYTES 65536
+#define MU_SEM_NATIVE_LDS_BYTES 159744
+int mu_sem_eval_native_supported(int C, int h, int w);
+long mu_sem_eval_native_workspace_bytes(int B, int C, int h, int w, int max_h, int max_w);
+int mu_sem_eval_native(const void* logits, int B, int C, int h, int w, long inner, long outer_stride, long c_stride, long p_stride,
+                       const unsigned char* labels, const long* offsets, const int* sizes, int max_h, int max_w, long ignore_index,
+                       int* img_counts, long* confusion, unsigned char* valid, unsigned char* classes_or_null, void* workspace,
+                       long ws_bytes, int dtype, void* stream);
 /* Instance matching: what evaluate_instances / evaluate_panoptic_metrics (ade_panoptic.py:520-586, city_instance.py:451-500) hand to
  * pycocotools and panopticapi, restated from the published algorithms (COCOeval.evaluateImg, maskUtils.iou, panopticapi's
  * pq_compute_single_core) on id maps; no RLE.  Not pinned to those packages.

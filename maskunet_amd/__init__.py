@@ -11,7 +11,7 @@ from .losses import CrossEntropyLoss, InstanceContrastiveLoss, cross_entropy, me
 from .instances import (Instances, generate_instance_mask, instances_from_embeddings, instances_from_id_map, instances_from_labels,
                         predict_instances)
 from .matching import CocoEval, CocoMatches, InstanceAP, Matches, PanopticQuality, coco_match, match_instances
-from .metrics import SemanticBatch, SemanticMetrics, metrics_from_counts, semantic_eval
+from .metrics import SemanticBatch, SemanticMetrics, SemanticNativeBatch, metrics_from_counts, semantic_eval, semantic_eval_native
 from .rle import RLEs, decode_rle, encode_rle, rle_counts_from_string, rle_string_from_counts
 from .coco import CocoMasks, coco_masks
 from .images import PackedImages, pack_images, resize_pil_to_nhwc
@@ -27,5 +27,6 @@ __all__ = ["ConvBlock", "DownSample", "UpSample", "Mask2FormerAttention", "UNet"
            "instances_from_labels", "generate_instance_mask", "Instances", "instances_from_embeddings", "match_instances", "Matches",
            "InstanceAP", "PanopticQuality", "RLEs", "encode_rle", "decode_rle", "rle_counts_from_string", "rle_string_from_counts",
            "coco_masks", "CocoMasks", "instances_from_id_map", "semantic_eval", "SemanticBatch", "SemanticMetrics",
-           "metrics_from_counts", "resize_pil_to_nhwc", "pack_images", "PackedImages", "coco_match", "CocoMatches", "CocoEval"]
+           "metrics_from_counts", "resize_pil_to_nhwc", "pack_images", "PackedImages", "coco_match", "CocoMatches", "CocoEval",
+           "semantic_eval_native", "SemanticNativeBatch"]
 __version__ = "0.1.0"

@@ -97,6 +97,9 @@ SIGNATURES = {
     "mu_sem_eval_supported": (I, [I]),
     "mu_sem_eval_workspace_bytes": (L, [I, L, I]),
     "mu_sem_eval": (I, [P, P, I, L, I, L, L, L, L, L, F, P, P, P, P, P, P, L, I, P]),
+    "mu_sem_eval_native_supported": (I, [I, I, I]),
+    "mu_sem_eval_native_workspace_bytes": (L, [I, I, I, I, I, I]),
+    "mu_sem_eval_native": (I, [P, I, I, I, I, L, L, L, L, P, P, P, I, I, L, P, P, P, P, P, L, I, P]),
     "mu_inst_triplet_workspace_bytes": (L, [I, I]),
     "mu_inst_triplet_fwd": (I, [P, P, I, I, I, I, I, F, P, I, I, P, L, P, P]),
     "mu_inst_triplet_bwd": (I, [P, I, I, I, I, P, I, I, P, P, P]),

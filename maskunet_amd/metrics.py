@@ -11,6 +11,10 @@ compute_iou_for_image on the host (city_panoptic.py:212-222).  `semantic_eval` t
 probability that the instance labelling consumes.  `SemanticMetrics` accumulates updates without ever synchronising; `compute()`
 brings the counters to the host once and derives the dataset-level metrics (the precision / recall / F1 / Jaccard that the scripts
 import from sklearn, pixel accuracy) and the three numbers the scripts print.  All host arithmetic is `metrics_from_counts`.
+
+The scripts score the network-size class map against labels resized down to it.  `semantic_eval_native` /
+`SemanticMetrics.update_native` score at each label map's OWN size instead, as the datasets define mIoU: bilinear upsampling, arg-max
+and counting in one kernel over a ragged batch of label maps (mu_sem_eval_native), into the same accumulator.
 """
 from __future__ import annotations
 
@@ -90,6 +94,78 @@ def semantic_eval(outputs, labels, num_classes=None, ignore_index=-100, temperat
     return SemanticBatch(img_counts, img_loss, confusion, cls, prob)
 
 
+@dataclass
+class SemanticNativeBatch:
+    """Device tensors of one semantic_eval_native call (contract: mu_sem_eval_native in include/maskunet_hip.h)."""
+    img_counts: torch.Tensor             # int32 [B,3,C]  per image I_c, P_c, L_c at the image's own label size; zero for a refused image
+    confusion: torch.Tensor              # int64 [C+1,C]  row = label (C: void), column = prediction; the tensor that was added into
+    valid: torch.Tensor                  # uint8 [B]      0 for an image the kernel refused (size outside the bounds, short byte span)
+    classes: torch.Tensor | None         # uint8, flat    the class maps, laid out like the labels' bytes (zero where nothing is written)
+    offsets: torch.Tensor                # int64 [B+1]    of the labels: byte offset of every image in `classes`
+    sizes: torch.Tensor                  # int32 [B,2]    (H_b, W_b)
+
+    def class_maps(self):
+        """The per-image [H_b, W_b] views of `classes` (no copy of the maps; None for a refused image).  Brings offsets, sizes and
+        valid to the host: this SYNCHRONISES."""
+        if self.classes is None:
+            raise RuntimeError("SemanticNativeBatch.class_maps needs the class map: call semantic_eval_native / update_native with classes=True")
+        off, sizes, ok = self.offsets.cpu().tolist(), self.sizes.cpu().tolist(), self.valid.cpu().tolist()
+        return [self.classes[o:o + H * W].view(H, W) if v else None for o, (H, W), v in zip(off, sizes, ok)]
+
+
+def _source_native(outputs, B, num_classes):
+    """(C, h, w, nhwc) of the logits of semantic_eval_native, from the shapes alone: [B,C,h,w] when num_classes is None or equals
+    shape[1] (tried first, as _source does), else a channel-padded [B,h,w,Cp] with num_classes real channels"""
+    if outputs.shape[0] == B and num_classes in (None, outputs.shape[1]):
+        return int(outputs.shape[1]), int(outputs.shape[2]), int(outputs.shape[3]), False
+    if outputs.shape[0] == B and num_classes is not None and outputs.shape[3] >= num_classes:
+        return int(num_classes), int(outputs.shape[1]), int(outputs.shape[2]), True
+    raise RuntimeError(f"semantic_eval_native: outputs {tuple(outputs.shape)} are neither [B,C,h,w] nor (with num_classes) a channel-padded "
+                       f"[B,h,w,Cp] for a batch of {B} label maps")
+
+
+def semantic_eval_native(outputs, labels, num_classes=None, ignore_index=255, classes=False, confusion=None):
+    """Semantic evaluation at the labels' own resolution, as ADE20K, Cityscapes and COCO define mIoU: the logits of every image are
+    upsampled bilinearly (the formula of F.interpolate(.., mode="bilinear", align_corners=False)) to the size of that image's label map
+    and the first arg-max is counted there, in one kernel that never writes the upsampled logits (mu_sem_eval_native).  outputs: the
+    module output [B,C,h,w] (fp32 or fp16; an untouched output is read through the NHWC tensor it was converted from) or a
+    channel-padded NHWC tensor [B,h,w,Cp] with `num_classes` given; labels: a PackedImages of B single-channel label maps of any sizes
+    (pack_images, once per batch).  A pixel is void if its label is `ignore_index` or >= C.  `confusion`: an int64 [C+1,C] tensor to add
+    into (a new zeroed one otherwise).  classes=True also returns the class maps at native resolution.  Never synchronises."""
+    from .images import PackedImages
+    if not torch.is_tensor(outputs) or outputs.dim() != 4 or not isinstance(labels, PackedImages):
+        raise RuntimeError("semantic_eval_native expects outputs [B,C,h,w] (or [B,h,w,Cp] with num_classes) and the labels as a PackedImages")
+    if labels.channels != 1:
+        raise RuntimeError(f"semantic_eval_native: label maps have one channel, got a PackedImages of {labels.channels}")
+    B = int(labels.sizes.shape[0])
+    C, h, w, nhwc = _source_native(outputs, B, num_classes)
+    lib = _lib.load()
+    if B < 1 or lib.mu_sem_eval_native_supported(C, h, w) != 0:
+        raise RuntimeError(f"maskunet_amd: native-resolution semantic evaluation needs B >= 1, 1 <= num_classes <= 256 and "
+                           f"1 <= h * w <= 65536, got B = {B}, {C} classes, {h}x{w}")
+    if confusion is not None and (confusion.dtype != torch.int64 or tuple(confusion.shape) != (C + 1, C) or not confusion.is_contiguous()):
+        raise RuntimeError(f"confusion must be a contiguous int64 [{C + 1},{C}] tensor on the GPU")
+    if not (outputs.is_cuda and labels.data.is_cuda and labels.offsets.is_cuda and labels.sizes.is_cuda
+            and (confusion is None or confusion.is_cuda)):
+        raise RuntimeError("semantic_eval_native expects the outputs and the labels on the GPU (the HIP path has no CPU fallback)")
+    if nhwc:
+        x = outputs.detach().contiguous()
+        inner, outer, cs, ps = B * h * w, 0, 1, x.shape[3]
+    else:
+        x, inner, outer, cs, ps = _strided_source(outputs)
+    dev = x.device
+    if confusion is None:
+        confusion = torch.zeros((C + 1, C), dtype=torch.int64, device=dev)
+    img_counts = torch.empty((B, 3, C), dtype=torch.int32, device=dev)
+    valid = torch.empty(B, dtype=torch.uint8, device=dev)
+    cls = torch.zeros_like(labels.data) if classes else None
+    nws = lib.mu_sem_eval_native_workspace_bytes(B, C, h, w, labels.max_h, labels.max_w)
+    ws = workspace(nws, dev)
+    call("mu_sem_eval_native", ptr(x), B, C, h, w, inner, outer, cs, ps, ptr(labels.data), ptr(labels.offsets), ptr(labels.sizes),
+         labels.max_h, labels.max_w, int(ignore_index), ptr(img_counts), ptr(confusion), ptr(valid), ptr(cls), ptr(ws), nws, dt(x), stream())
+    return SemanticNativeBatch(img_counts, confusion, valid, cls, labels.offsets, labels.sizes)
+
+
 def _ratio(num, den):
     """num / den in float64, 0 where den == 0 (sklearn's zero_division=0)"""
     num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
@@ -149,7 +225,9 @@ def metrics_from_counts(confusion, per_update_img_counts, per_update_img_loss, s
 class SemanticMetrics:
     """Accumulates semantic_eval over a validation set: `update(outputs, labels)` per batch, `compute()` at the end.  The confusion
     matrix is one device int64 tensor that every update adds into; the per-image tensors stay on the device until compute().  No
-    update synchronises.  (Across ranks: all-reduce `confusion` and gather the per-image tensors; not done here.)"""
+    update synchronises.  (Across ranks: all-reduce `confusion` and gather the per-image tensors; not done here.)
+    `update_native(outputs, packed_labels)` feeds the same accumulator at the labels' own resolution (semantic_eval_native); one
+    metrics object takes one kind of update only."""
 
     def __init__(self, num_classes, ignore_index=-100, temperature=0.5, smooth=1e-6):
         self.num_classes = int(num_classes)
@@ -158,22 +236,48 @@ class SemanticMetrics:
         self.ignore_index, self.temperature, self.smooth = int(ignore_index), float(temperature), float(smooth)
         self.confusion = None
         self._seen = []
+        self._native = None              # True / False once an update has been taken
+
+    def _begin(self, native, device):
+        if self._native is not None and self._native != native:
+            raise RuntimeError("SemanticMetrics takes one kind of update: update() and update_native() cannot be mixed (reset() first)")
+        if self.confusion is None:
+            self.confusion = torch.zeros((self.num_classes + 1, self.num_classes), dtype=torch.int64, device=device)
 
     def update(self, outputs, labels, classes=False):
         """One validation batch; returns its SemanticBatch (with the class map and probability when classes=True)."""
-        if self.confusion is None:
-            self.confusion = torch.zeros((self.num_classes + 1, self.num_classes), dtype=torch.int64, device=outputs.device)
+        self._begin(False, outputs.device)
         batch = semantic_eval(outputs, labels, self.num_classes, self.ignore_index, self.temperature, classes, self.confusion)
         self._seen.append((batch.img_counts, batch.img_loss))
+        self._native = False
+        return batch
+
+    def update_native(self, outputs, labels, classes=False):
+        """One validation batch at the labels' own resolution: labels is the PackedImages of the batch's label maps (pack_images once
+        per batch).  Returns its SemanticNativeBatch (with the native-resolution class maps when classes=True).  An ignore_index
+        outside [0, 255] means that no label value is void by itself."""
+        self._begin(True, outputs.device)
+        batch = semantic_eval_native(outputs, labels, self.num_classes, self.ignore_index, classes, self.confusion)
+        self._seen.append((batch.img_counts, batch.valid))
+        self._native = True
         return batch
 
     def reset(self):
         self.confusion = None
         self._seen = []
+        self._native = None
 
     def compute(self):
-        """metrics_from_counts of everything seen; the one place that copies to the host."""
+        """metrics_from_counts of everything seen; the one place that copies to the host.  After update_native no loss is defined (the
+        img_loss entries are zero, so reference["loss"] is NaN), the per-image numbers run over the images the kernel accepted, and
+        `refused` counts the others."""
         if not self._seen:
             raise RuntimeError("compute() before any update()")
-        return metrics_from_counts(self.confusion.cpu().numpy(), [c.cpu().numpy() for c, _ in self._seen],
-                                   [ls.cpu().numpy() for _, ls in self._seen], self.smooth)
+        conf = self.confusion.cpu().numpy()
+        if not self._native:
+            return metrics_from_counts(conf, [c.cpu().numpy() for c, _ in self._seen], [ls.cpu().numpy() for _, ls in self._seen], self.smooth)
+        ok = [v.cpu().numpy() != 0 for _, v in self._seen]
+        counts = [c.cpu().numpy()[k] for (c, _), k in zip(self._seen, ok)]
+        out = metrics_from_counts(conf, counts, [np.zeros((len(c), 2)) for c in counts], self.smooth)
+        out["refused"] = int(sum(int((~k).sum()) for k in ok))
+        return out
