@@ -485,6 +485,43 @@ long mu_id_instances_workspace_bytes(int B, int H, int W, int max_inst, int clas
 int mu_id_instances(const void* id_map, int id_kind, const int* sem, int B, int H, int W, int max_inst, int class_cap, int* ids,
                     int* table, float* score, int* count, int* order, int* values, int* invalid, void* workspace, long ws_bytes,
                     void* stream);
+/* Panoptic segments (the stage save_predictions / evaluate_panoptic leave open, coco_panoptic.py:388-439): the semantic map and the
+ * instances of mu_instances / mu_dbscan_instances / mu_id_instances merged into COCO panoptic segments.  The rule restates
+ * panopticapi's published format (id2rgb, segments_info, one segment per stuff class) and the usual semantic + instance merge.
+ * cls int32 [B,H,W]; ids int32 [B,H,W], table int32 [B,max_inst,8], score fp32 [B,max_inst], count int32 [B] as those entry points
+ * write them; kind int32 [num_classes]: 0 void, 1 stuff, 2 thing; category int32 [num_classes]: label -> dataset category id.
+ * For a pixel with k = ids, c = cls:
+ *   thing      1 <= k <= min(count, max_inst) and kind[table[k-1].class] == 2 (a class outside [0, num_classes) is void): the pixel
+ *              belongs to thing candidate k, kept iff table[k-1].area >= thing_area_limit and score[k-1] >= score_threshold (fp32);
+ *              the pixels of a candidate that is not kept are VOID, they do not become stuff.  max_inst < k <= count: void, and bit 2
+ *              of invalid[b].  k <= 0, k > count, or an instance whose class is not a thing: no instance;
+ *   stuff      otherwise, 0 <= c < num_classes and kind[c] == 1: a stuff candidate of class c; the class is kept iff the image has at
+ *              least max(stuff_area_limit, 1) such pixels, and all of them form ONE segment, connected or not;
+ *   void       everything else.
+ *   numbering  the kept segments that hold a pixel are 1..n by their first pixel in raster order; seg_count[b] = n, also past max_seg.
+ * seg int32 [B,H,W]: the segment number, 0 = void, complete also past max_seg.  seg_cls int32 [B,H,W]: the segment's class
+ * (table[k-1].class of a thing, c of stuff), 0 on void.  Per segment, rows [B,max_seg], zero past min(n, max_seg):
+ *   seg_table  int32 x 8, the columns of mu_instances over the segment's pixels; class_rank = the 1-based rank among the kept segments of
+ *              the class in segment order (always 1 for stuff);
+ *   seg_score  fp32: score[k-1] of a thing, 1.0 of stuff;   seg_order: segments by descending score, ties by ascending number;
+ *   seg_source the instance id k of a thing, 0 of stuff;
+ *   seg_values the COCO segment id category[class] * label_divisor + (thing ? class_rank : 0), or 0 where that id is <= 0, >= 2^24, or
+ *              a thing's class_rank >= label_divisor (ids would collide or not fit a PNG): bit 0 of invalid[b].
+ * id_map int32 [B,H,W]: seg_values of the pixel's segment; 0 on void, on a segment past max_seg and on one of bit 0.  rgb uint8
+ * [B,H,W,3]: panopticapi's id2rgb of id_map, R = v & 255, G = (v >> 8) & 255, B = v >> 16, stored R,G,B, or B,G,R with bgr = 1.
+ * invalid int32 [B]: bit 0 and bit 2 above, bit 1: n > max_seg (rows past max_seg are dropped).
+ * One launch, one workgroup per image, stream-ordered, nothing read back, integer atomics only: bit-identical from run to run; every
+ * output byte is written.  H*W <= 65536, 1 <= max_inst <= 4096, 1 <= max_seg <= 4096, 1 <= num_classes <= 1024, label_divisor >= 1,
+ * both area limits >= 0, else MU_ERR_SHAPE; bgr other than 0 / 1 is MU_ERR_ARG (mu_panoptic_supported and
+ * mu_panoptic_workspace_bytes: host only; the latter is 0 for unsupported shapes). */
+int mu_panoptic_supported(int H, int W, int max_inst, int num_classes, int max_seg, int label_divisor, int stuff_area_limit,
+                          int thing_area_limit);
+long mu_panoptic_workspace_bytes(int B, int H, int W, int max_inst, int num_classes, int max_seg);
+int mu_panoptic(const int* cls, const int* ids, const int* table, const float* score, const int* count, const int* kind,
+                const int* category, int B, int H, int W, int max_inst, int num_classes, int label_divisor, int stuff_area_limit,
+                int thing_area_limit, float score_threshold, int max_seg, int bgr, int* seg, int* seg_cls, int* seg_table,
+                float* seg_score, int* seg_count, int* seg_order, int* seg_source, int* seg_values, int* id_map, unsigned char* rgb,
+                int* invalid, void* workspace, long ws_bytes, void* stream);
 /* Semantic evaluation of one validation batch in ONE read of the logits: what the validation loops take from `outputs` --
  * criterion(outputs, labels) (ade_semantic.py:454; ignore_index = 255: city_semantic.py:341), mean_iou(outputs, labels, c_out)
  * (city_panoptic.py:225-236, ade_semantic.py:128-146), compute_iou_for_image per image (city_panoptic.py:212-222) and

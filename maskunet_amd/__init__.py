@@ -11,6 +11,7 @@ from .losses import CrossEntropyLoss, InstanceContrastiveLoss, cross_entropy, me
 from .instances import (Instances, generate_instance_mask, instances_from_embeddings, instances_from_id_map, instances_from_labels,
                         predict_instances)
 from .matching import CocoEval, CocoMatches, InstanceAP, Matches, PanopticQuality, coco_match, match_instances
+from .panoptic import Panoptic, panoptic_segments, predict_panoptic
 from .metrics import SemanticBatch, SemanticMetrics, SemanticNativeBatch, metrics_from_counts, semantic_eval, semantic_eval_native
 from .rle import RLEs, decode_rle, encode_rle, rle_counts_from_string, rle_string_from_counts
 from .coco import CocoMasks, coco_masks
@@ -28,5 +29,5 @@ __all__ = ["ConvBlock", "DownSample", "UpSample", "Mask2FormerAttention", "UNet"
            "InstanceAP", "PanopticQuality", "RLEs", "encode_rle", "decode_rle", "rle_counts_from_string", "rle_string_from_counts",
            "coco_masks", "CocoMasks", "instances_from_id_map", "semantic_eval", "SemanticBatch", "SemanticMetrics",
            "metrics_from_counts", "resize_pil_to_nhwc", "pack_images", "PackedImages", "coco_match", "CocoMatches", "CocoEval",
-           "semantic_eval_native", "SemanticNativeBatch"]
+           "semantic_eval_native", "SemanticNativeBatch", "Panoptic", "panoptic_segments", "predict_panoptic"]
 __version__ = "0.1.0"

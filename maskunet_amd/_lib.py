@@ -113,6 +113,9 @@ SIGNATURES = {
     "mu_id_instances_supported": (I, [I, I, I, I]),
     "mu_id_instances_workspace_bytes": (L, [I, I, I, I, I]),
     "mu_id_instances": (I, [P, I, P, I, I, I, I, I] + [P] * 8 + [L, P]),
+    "mu_panoptic_supported": (I, [I] * 8),
+    "mu_panoptic_workspace_bytes": (L, [I] * 6),
+    "mu_panoptic": (I, [P] * 7 + [I] * 8 + [F, I, I] + [P] * 11 + [P, L, P]),
     "mu_instance_pairs_supported": (I, [I, I, I, I]),
     "mu_instance_pairs_workspace_bytes": (L, [I, I, I, I, I]),
     "mu_instance_pairs": (I, [P, P, I, I, I, I, I, P, P, P, L, P]),

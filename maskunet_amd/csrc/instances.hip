@@ -330,9 +330,7 @@ __global__ __launch_bounds__(INST_THREADS) void inst_stats_kernel(const int* __r
             row[5] = (int)ymax[k];
             row[6] = f;
             score[k] = s;
-            unsigned u = __float_as_uint(s);
-            u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // ascending-sortable float bits
-            key = ((unsigned long long)(~u) << 32) | (unsigned)(k + 1);   // descending score, then ascending id
+            key = score_order_key(s, k);
         } else if (k < max_inst) {
             int* row = table + (long)k * 8;
 #pragma unroll
@@ -352,24 +350,10 @@ __global__ __launch_bounds__(INST_THREADS) void inst_stats_kernel(const int* __r
         table[(long)k * 8 + 7] = rank;
     }
 
-    // bitonic sort of the keys, ascending, over the power of two that holds K
+    // the keys in ascending order, over the power of two that holds K
     int S = 1;
     while (S < K) S <<= 1;
-    for (int size = 2; size <= S; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            __syncthreads();
-            for (int t = tid; t < (S >> 1); t += INST_THREADS) {
-                const int lo = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), hi = lo + stride;
-                const bool up = (lo & size) == 0;
-                const unsigned long long a = acc[lo], c = acc[hi];
-                if ((a > c) == up) {
-                    acc[lo] = c;
-                    acc[hi] = a;
-                }
-            }
-        }
-    }
-    __syncthreads();
+    block_sort_u64(acc, S, tid, INST_THREADS);
     for (int k = tid; k < max_inst; k += INST_THREADS) order[k] = k < K ? (int)(unsigned)(acc[k] & 0xffffffffull) : 0;
 }
 

@@ -1,5 +1,5 @@
-// Wave (64 lanes) and workgroup building blocks of the one-workgroup-per-image integer kernels (instances.hip, rle.hip): scans, flag
-// ranks, wave segments and the stable counting sort.  Device-only, no state.  The integer wave reductions are in common.h beside the
+// Wave (64 lanes) and workgroup building blocks of the one-workgroup-per-image integer kernels (instances.hip, rle.hip, panoptic.hip): scans,
+// flag ranks, wave segments, the stable counting sort and the score-order sort.  Device-only, no state.  The integer wave reductions are in common.h beside the
 // float ones.  `lane` = threadIdx.x & 63, `wave` = threadIdx.x >> 6 throughout.
 #pragma once
 #include "common.h"
@@ -72,6 +72,33 @@ __device__ __forceinline__ unsigned wave_flag_rank(bool flag, int lane, unsigned
     const unsigned rank = running + __popcll(mask & lanes_below(lane));
     running += __popcll(mask);
     return rank;
+}
+
+// sort key of row k (0-based) with score s: ascending keys = descending score, then ascending id (= k + 1, the low word)
+__device__ __forceinline__ unsigned long long score_order_key(float s, int k) {
+    unsigned u = __float_as_uint(s);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);           // ascending-sortable float bits
+    return ((unsigned long long)(~u) << 32) | (unsigned)(k + 1);
+}
+
+// bitonic sort of key[0..S), ascending, S a power of two (LDS or the workgroup's own global memory).  Holds barriers: every thread of
+// the workgroup calls it; the keys written before the call need no barrier of their own, the sorted ones are visible on return.
+__device__ __forceinline__ void block_sort_u64(unsigned long long* key, int S, int tid, int n_threads) {
+    for (int size = 2; size <= S; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            __syncthreads();
+            for (int t = tid; t < (S >> 1); t += n_threads) {
+                const int lo = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), hi = lo + stride;
+                const bool up = (lo & size) == 0;
+                const unsigned long long a = key[lo], c = key[hi];
+                if ((a > c) == up) {
+                    key[lo] = c;
+                    key[hi] = a;
+                }
+            }
+        }
+    }
+    __syncthreads();
 }
 
 // One 64-lane chunk of a stable counting sort: `has` = the lane holds an element, `key` its bucket, counter[] the wave's OWN counters
