@@ -639,12 +639,22 @@ def _bn_train_stats(x, stats, bn, nbt, momentum, mean, rstd):
              ptr(ws), ws.numel(), dt(x), stream())
 
 
+def _refuse_cumulative(*bns):
+    """torch's momentum=None is a cumulative average with the factor 1 / num_batches_tracked, which lives on the device: refused before
+    any launch (running buffers and step counters stay as they are) rather than updated with some other factor."""
+    for bn in bns:
+        if bn is not None and bn.training and bn.running_mean is not None and bn.momentum is None:
+            raise RuntimeError("BatchNorm2d(momentum=None) (cumulative moving average) is not supported in training mode with running "
+                               "statistics; set a momentum, or track_running_stats=False")
+
+
 def _bn_act_fwd(x, res, bn, act, stats=None, enc=False):
     """act(res + BatchNorm2d(x)): ade_semantic.py:200-201 (BN,GELU), :204,208 (BN, +x, GELU), :219,240 (BN), :285-286 (BN, ReLU)
     -> (y, saved).  bn: the nn.BatchNorm2d parameter container; training uses batch statistics and updates its running buffers in
     place.  enc (fp32x): y is returned as the _Enc3 of the 3x3 conv behind it, its only reader."""
     x = x.contiguous()
     training = bn.training or bn.running_mean is None
+    _refuse_cumulative(bn)
     # the step counter is bumped by the statistics kernel (one tiny torch kernel per BatchNorm otherwise: 39 per step)
     nbt = bn.num_batches_tracked if (bn.training and bn.num_batches_tracked is not None) else None
     if nbt is not None and (nbt.device != x.device or nbt.dtype != torch.int64):
@@ -895,6 +905,7 @@ def conv_blocks(x, blocks, tail_bn=None, res_link=None):
     params = [p for w1, bn1, w2, bn2, _ in blocks for p in (w1, bn1.weight, bn1.bias, w2, bn2.weight, bn2.bias)]
     if tail_bn is not None:
         params += [tail_bn.weight, tail_bn.bias]
+    _refuse_cumulative(tail_bn, *[bn for _, bn1, _, bn2, _ in blocks for bn in (bn1, bn2)])      # before the first layer of the run
     return _ConvBlocks.apply((blocks, tail_bn, res_link, torch.is_grad_enabled(), _cache_ok()), x, *params)
 
 

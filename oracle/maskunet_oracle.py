@@ -35,14 +35,21 @@ LN_EPS = 1e-5       # nn.LayerNorm default, ade_semantic.py:161,281
 # --------------------------------------------------------------------------------------
 # primitives
 # --------------------------------------------------------------------------------------
-def batchnorm2d(x, p: Params, prefix: str, training: bool, new_stats: Optional[dict] = None):
+def _flag(training, prefix: str) -> bool:
+    """`training` of one layer: a plain bool holds for every layer; a callable is asked per layer,
+    training(prefix) -> bool with the layer's state_dict prefix (partial training: single
+    BatchNorm layers in eval() inside a training model)."""
+    return bool(training(prefix)) if callable(training) else bool(training)
+
+
+def batchnorm2d(x, p: Params, prefix: str, training, new_stats: Optional[dict] = None):
     """nn.BatchNorm2d (ade_semantic.py:200,204,219,240,285).
 
     training: biased batch variance normalises; the running_var update uses the unbiased
-    variance, momentum 0.1.  eval: running statistics.
+    variance, momentum 0.1.  eval: running statistics.  training: bool, or callable(prefix) -> bool.
     """
     w, b = p[prefix + ".weight"], p[prefix + ".bias"]
-    if training:
+    if _flag(training, prefix):
         mean = x.mean(dim=(0, 2, 3))
         var = x.var(dim=(0, 2, 3), unbiased=False)
         if new_stats is not None:
@@ -179,7 +186,7 @@ def boundary_head(x, p: Params, prefix: str, training: bool, new_stats=None):
 # --------------------------------------------------------------------------------------
 # whole model
 # --------------------------------------------------------------------------------------
-def unet_forward(p: Params, x, keeps: Sequence[torch.Tensor], *, training: bool,
+def unet_forward(p: Params, x, keeps: Sequence[torch.Tensor], *, training,
                  dropout_masks: Optional[Sequence[torch.Tensor]] = None, p_drop: float = 0.3,
                  new_stats: Optional[dict] = None, q_block: Optional[int] = None,
                  three_head: bool = False):
@@ -191,8 +198,8 @@ def unet_forward(p: Params, x, keeps: Sequence[torch.Tensor], *, training: bool,
     reference's nn.Dropout(0.3) (:273,304,307) is ``x * mask / (1-p)`` in training and the
     identity in eval.  None = dropout disabled.
     """
-    def drop(t, i):
-        if not training or dropout_masks is None:
+    def drop(t, i):      # a callable `training`: dropout is off unless masks are given and training("dropout") is true
+        if dropout_masks is None or not _flag(training, "dropout"):
             return t
         return t * dropout_masks[i].to(t.dtype) / (1.0 - p_drop)
 

@@ -16,6 +16,13 @@ from oracle import maskunet_oracle as O
 import os
 
 TOL = {torch.float32: 1e-3, torch.float16: 3e-2}
+# parameter gradients of a module case are compared against max(|ref|max, PARAM_GRAD_FLOOR * the case's largest parameter gradient)
+PARAM_GRAD_FLOOR = {torch.float32: 1e-3, torch.float16: 5e-2}
+# whole-model parameter gradients against the oracle (check_unet_vs_oracle; the max-norm gate also in check_unet_golden): the floor of
+# the case's largest gradient below which a gradient counts as rounding noise, the loose max-norm gate and the tight 1 - cosine gate
+UNET_GRAD_FLOOR = {torch.float32: 1e-3, torch.float16: 1e-2}
+UNET_GRAD_MAXREL = {torch.float32: 5e-2, torch.float16: 3e-1}
+UNET_GRAD_COS = {torch.float32: 1e-4, torch.float16: 2e-2}
 # static loss scale used for the fp16 backward in whole-model checks (fp16 activation gradients underflow
 # without one: d(loss)/d(logit) ~ 1/(B*H*W)); fp32 needs none
 FP16_LOSS_SCALE = float(os.environ.get("MU_LOSS_SCALE", "1024"))
@@ -624,7 +631,7 @@ def check_golden_module(name, dtype):
             ref = torch.from_numpy(rec["gparam/" + k])
             # compare against the largest parameter-gradient scale of the case: gamma/beta feeding a
             # second BatchNorm and key.bias have analytically-zero gradients (pure rounding noise)
-            floor = (1e-3 if dtype == torch.float32 else 5e-2) * gmax
+            floor = PARAM_GRAD_FLOOR[dtype] * gmax
             if k == "key.bias" and "gparam/query.bias" in rec and _lib.mdt(dtype) == _lib.MU_F32X:
                 # analytically zero (a constant added to every key shifts all scores of a query alike: softmax invariance), so what any
                 # arithmetic returns is rounding noise of the dK rows summed over the keys.  ONLY in the fp32x mode (exact fp32 and fp16
@@ -698,7 +705,7 @@ def check_unet_golden(name, dtype):
     # flip under ANY reassociation of the fp32 sums (the reference's own fp32-vs-fp64 noise is ~1e-3 in this metric and a
     # different-but-equally-valid summation order moves single elements by a few %), so the max-norm gate is loose (5e-2
     # fp32, 3e-1 fp16) and the tight gate is the per-parameter cosine (check_unet_vs_oracle: 1-cos <= 1e-4 fp32, 2e-2 fp16).
-    gtol = 5e-2 if dtype == torch.float32 else 3e-1
+    gtol = UNET_GRAD_MAXREL[dtype]
     res.append((f"{name} worst grad [{worst[1]}]", worst[0], gtol))
     gsl = model.norm.weight.grad[:, ::16, ::16].float().cpu() / scale
     res.append((f"{name} d norm.weight slice", _rel_err(gsl, torch.from_numpy(rec["g_slice/norm.weight"])), 2 * gtol))
@@ -765,15 +772,15 @@ def check_unet_vs_oracle(dtype, B=2, c_out=150, three_head=False, seed=300, with
     scale = 1.0 if dtype == torch.float32 else FP16_LOSS_SCALE
     (loss * scale).backward()
     tol = TOL[dtype]
-    gtol = 5e-2 if dtype == torch.float32 else 3e-1          # max-norm: see check_unet_golden; the cosine below is the tight gate
-    ctol = 1e-4 if dtype == torch.float32 else 2e-2          # 1 - cosine similarity per parameter gradient
+    gtol = UNET_GRAD_MAXREL[dtype]          # max-norm: see check_unet_golden; the cosine below is the tight gate
+    ctol = UNET_GRAD_COS[dtype]             # 1 - cosine similarity per parameter gradient
     res = [(f"unet out{i} full", _err(o, r), tol) for i, (o, r) in enumerate(zip(outs, refs))]
     res.append((f"unet final-ReLU decisions taken from the HIP path: {forced['n']} of {dec.numel()}; largest overridden |pre-activation| "
                 f"relative to the output scale", forced["zrel"], tol))
     res.append(("unet loss", abs(loss.item() - lref.item()) / max(1.0, abs(lref.item())), tol))
     gmax = max(float(v.grad.abs().max()) for v in p.values() if v.requires_grad and v.grad is not None)
     worst, worst_cos = (0.0, ""), (0.0, "")
-    floor = (1e-3 if dtype == torch.float32 else 1e-2) * gmax
+    floor = UNET_GRAD_FLOOR[dtype] * gmax
     for k, v in model.named_parameters():
         r = p[k].grad
         assert (v.grad is None) == (r is None), k
