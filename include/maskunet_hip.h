@@ -419,6 +419,15 @@ int mu_inst_triplet_fwd(const float* feat, const long* mask, int B, int C, int H
                         const float* u, int id_cap, int max_inst, void* workspace, long ws_bytes, float* loss, void* stream);
 int mu_inst_triplet_bwd(const float* feat, int B, int C, int H, int W, const void* workspace, int id_cap, int max_inst,
                         const float* grad_out, float* dfeat, void* stream);
+/* Refusal order of the post-processing entry points (mu_instances, mu_dbscan_instances, mu_instance_pairs, mu_instance_match,
+ * mu_coco_match, mu_id_instances, mu_rle_encode / _decode, mu_coco_masks, mu_panoptic, mu_sem_eval, mu_sem_eval_native): a null pointer,
+ * a non-positive or otherwise invalid scalar, an unknown dtype / kind is MU_ERR_ARG; then a shape outside the limits of the entry's
+ * mu_*_supported is MU_ERR_SHAPE (the two match entries then check their thresholds / area ranges: MU_ERR_ARG; mu_sem_eval_native then
+ * its block count: MU_ERR_SHAPE); then ws_bytes below the entry's mu_*_workspace_bytes is MU_ERR_WORKSPACE (mu_sem_eval then checks its
+ * block count: MU_ERR_SHAPE); then a kernel that needs more dynamic LDS than the default limit is granted it, once per process and
+ * kernel: a failure is MU_ERR_LAUNCH; only then the first kernel or memset.  A refused call enqueues nothing, every buffer is left as it
+ * was.  mu_pil_resize_u8_nhwc keeps its own convention (below): MU_ERR_ARG for its limits and for a short workspace, -1 from its size
+ * query.  The size query of an entry and the carve of its workspace are one walk over one layout type in the entry's source file. */
 /* f5: instance post-processing of the instance / panoptic scripts on the device (no host round trip of the [B,c,H,W] output).
  * mu_argmax_prob: probs = softmax(outputs / 0.5, dim=1); preds = argmax(probs, 1) (ade_instance.py:408-411, ade_panoptic.py:529-532)
  * in one read of the logits, addressed as in mu_mean_iou.  cls[r] = first arg-max over the C channels (taken on the logits: softmax is

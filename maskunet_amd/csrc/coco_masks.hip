@@ -31,7 +31,7 @@
 #define CM_MAX_POINTS (1 << 21)                        // the counts of a chunk of edges, each clamped to max_points + 1, sum in an int
 #define CM_COORD_LIMIT 16777216.0
 
-struct CocoParams {
+struct CocoMaskParams {
     const double* xy;
     const int *poly_off, *ann_poly_off, *rle_counts, *ann_rle_off, *img_ann_off, *sizes;
     int B, A, P, n_points, n_counts, Ho, Wo, max_points;
@@ -167,7 +167,7 @@ __device__ __forceinline__ void cm_fill(unsigned* T, unsigned* U, CmScan& S, int
 }
 
 // Dynamic LDS: T and U, CM_WORDS words each (128 KiB); static: the edges of a chunk and the scan state (18 KiB).
-__global__ __launch_bounds__(CM_THREADS) void coco_masks_kernel(const CocoParams P) {
+__global__ __launch_bounds__(CM_THREADS) void coco_masks_kernel(const CocoMaskParams P) {
     extern __shared__ unsigned cm_lds[];
     __shared__ int e_xs[CM_THREADS], e_ys[CM_THREADS], e_xe[CM_THREADS], e_ye[CM_THREADS], e_pu[CM_THREADS], e_pv[CM_THREADS];
     __shared__ int e_start[CM_THREADS];
@@ -339,11 +339,8 @@ __global__ __launch_bounds__(256) void coco_zero_kernel(unsigned long long* __re
     }
 }
 
-static bool coco_lds_granted() {                       // once per process (see rle_lds_granted)
-    static const bool ok = hipFuncSetAttribute((const void*)coco_masks_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               2 * CM_WORDS * (int)sizeof(unsigned)) == hipSuccess;
-    return ok;
-}
+// dynamic LDS of coco_masks_kernel: both bitmaps, always at their full size; granted as such (common.h: mu_lds_grant)
+#define CM_LDS_BYTES (2 * CM_WORDS * (int)sizeof(unsigned))
 
 extern "C" int mu_coco_masks_supported(int Ho, int Wo, int max_points) {
     if (Ho <= 0 || Wo <= 0 || (long)Ho * Wo > CM_MAX_OUT_PIXELS || max_points < 1 || max_points > CM_MAX_POINTS) return MU_ERR_SHAPE;
@@ -367,12 +364,12 @@ extern "C" int mu_coco_masks(const double* xy, const int* poly_offsets, const in
     if (mu_coco_masks_supported(Ho, Wo, max_points) != MU_OK) return MU_ERR_SHAPE;
     if (ws_bytes < mu_coco_masks_workspace_bytes(B, A, Ho, Wo)) return MU_ERR_WORKSPACE;
     (void)workspace;
+    if (A > 0 && !mu_lds_grant<coco_masks_kernel>(CM_LDS_BYTES)) return MU_ERR_LAUNCH;
     const long n_out = (long)B * Ho * Wo;
-    const long zero_blocks = (n_out + 255) / 256;
-    coco_zero_kernel<<<(int)(zero_blocks < 4096 ? zero_blocks : 4096), 256, 0, (hipStream_t)stream>>>((unsigned long long*)cover, ids, n_out);
+    coco_zero_kernel<<<mu_grid(n_out, 256, 4096), 256, 0, (hipStream_t)stream>>>((unsigned long long*)cover, ids, n_out);
     MU_CHECK_LAUNCH();
     if (A == 0) return MU_OK;
-    CocoParams K;
+    CocoMaskParams K;
     K.xy = xy;
     K.poly_off = poly_offsets;
     K.ann_poly_off = ann_poly_offsets;
@@ -393,8 +390,7 @@ extern "C" int mu_coco_masks(const double* xy, const int* poly_offsets, const in
     K.masks = masks_or_null;
     K.area = area;
     K.valid = valid;
-    if (!coco_lds_granted()) return MU_ERR_LAUNCH;
-    coco_masks_kernel<<<A, CM_THREADS, 2 * CM_WORDS * sizeof(unsigned), (hipStream_t)stream>>>(K);
+    coco_masks_kernel<<<A, CM_THREADS, CM_LDS_BYTES, (hipStream_t)stream>>>(K);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }

@@ -38,6 +38,35 @@ template <typename F>
 static inline int with_storage2(int src_dtype, int dst_dtype, F&& f) {
     return with_storage(src_dtype, [&](auto s) -> int { return with_storage(dst_dtype, [&](auto d) -> int { return f(s, d); }); });
 }
+// the smallest power of two that is at least v (1 for v <= 1)
+static constexpr int mu_pow2(int v) {
+    int p = 1;
+    while (p < v) p <<= 1;
+    return p;
+}
+// Dynamic LDS beyond the default limit has to be granted per kernel (a CU has 160 KiB; one workgroup may take all of it).  The grant is
+// a property of the kernel, not of a call: it is set ONCE per process, to the most the kernel can ever ask for (`max_bytes`, the same
+// at every call site of a kernel), so concurrent callers with different shapes cannot undercut each other and no runtime call sits on
+// the per-call path.  false is the caller's MU_ERR_LAUNCH, returned before anything is enqueued.
+template <auto KERNEL>
+static inline bool mu_lds_grant(int max_bytes) {
+    static const bool ok = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, max_bytes) == hipSuccess;
+    return ok;
+}
+// Workspace walker: hands out consecutive typed regions of a caller's workspace and keeps the running byte count.  A layout type walks
+// its regions ONCE, in its constructor: with a null base the walk is the size query (`bytes`), with the caller's pointer it is the
+// carve, so the two cannot disagree.  Regions are packed: a layout orders them so that every one is aligned for its type.
+struct MuCarve {
+    void* base;
+    long bytes = 0;
+    constexpr explicit MuCarve(void* ws) : base(ws) {}
+    template <typename T>
+    constexpr T* take(long n) {
+        T* p = base ? (T*)((char*)base + bytes) : nullptr;
+        bytes += n * (long)sizeof(T);
+        return p;
+    }
+};
 
 // ------------------------------------------------------------------------------------------
 // MU_F32X ("fp32x"): fp32 STORAGE, matrix products on the bf16 matrix cores with every fp32 operand split into two bf16 parts,

@@ -357,23 +357,13 @@ __global__ __launch_bounds__(INST_THREADS) void inst_stats_kernel(const int* __r
     for (int k = tid; k < max_inst; k += INST_THREADS) order[k] = k < K ? (int)(unsigned)(acc[k] & 0xffffffffull) : 0;
 }
 
-static int inst_pow2(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
-// More than 64 KiB of dynamic LDS has to be granted per kernel (a CU has 160 KiB; one workgroup may take all of it).  The grant is
-// a property of the kernel, not of a call: it is set ONCE per process, to the most either kernel can ever ask for, so concurrent
-// callers with different shapes cannot undercut each other and no runtime call sits on the per-call path.
-#define INST_LDS_LABEL_MAX (INST_MAX_PIXELS * 2 + INST_WAVES * 4)
-#define INST_LDS_STATS_MAX (INST_MAX_INSTANCES * 28)
-static bool inst_lds_granted() {
-    static const bool ok =
-        hipFuncSetAttribute((const void*)inst_label_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, INST_LDS_LABEL_MAX) == hipSuccess &&
-        hipFuncSetAttribute((const void*)inst_stats_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, INST_LDS_STATS_MAX) == hipSuccess;
-    return ok;
-}
+// Dynamic LDS of the two kernels that need a grant (common.h: mu_lds_grant), and the most each can ever ask for
+static constexpr size_t inst_label_lds(int N) { return (size_t)((N + 1) >> 1) * 4 + INST_WAVES * sizeof(unsigned); }
+static constexpr size_t inst_stats_lds(int P) { return (size_t)P * (5 * sizeof(unsigned) + sizeof(unsigned long long)); }
+#define INST_LDS_LABEL_MAX ((int)inst_label_lds(INST_MAX_PIXELS))
+#define INST_LDS_STATS_MAX ((int)inst_stats_lds(INST_MAX_INSTANCES))
+static_assert(INST_LDS_LABEL_MAX == INST_MAX_PIXELS * 2 + INST_WAVES * 4 && INST_LDS_STATS_MAX == INST_MAX_INSTANCES * 28, "the grants");
+static bool inst_stats_granted() { return mu_lds_grant<inst_stats_kernel>(INST_LDS_STATS_MAX); }
 
 extern "C" int mu_instances_supported(int H, int W, int max_inst) {
     if (H <= 0 || W <= 0 || (long)H * W > INST_MAX_PIXELS) return MU_ERR_SHAPE;
@@ -381,10 +371,16 @@ extern "C" int mu_instances_supported(int H, int W, int max_inst) {
     return MU_OK;
 }
 
-// int first_pixel[B][max_inst]: the label kernel's hand-over to the statistics kernel
+struct InstancesWs {
+    MuCarve c;
+    int* first;     // [B][max_inst] first pixel of every instance: the label kernel's hand-over to the statistics kernel
+    constexpr InstancesWs(void* ws, int B, int max_inst) : c(ws), first(c.take<int>((long)B * max_inst)) {}
+};
+static_assert(InstancesWs(nullptr, 2, 5).c.bytes == 2 * 5 * 4 && InstancesWs(nullptr, 3, 4096).c.bytes == 3 * 4096 * 4, "mu_instances workspace");
+
 extern "C" long mu_instances_workspace_bytes(int B, int H, int W, int max_inst) {
     if (B <= 0 || mu_instances_supported(H, W, max_inst) != MU_OK) return 0;
-    return (long)B * max_inst * (long)sizeof(int);
+    return InstancesWs(nullptr, B, max_inst).c.bytes;
 }
 
 extern "C" int mu_instances(const int* cls, const float* prob_or_null, int B, int H, int W, int max_inst, int* ids, int* table,
@@ -392,16 +388,14 @@ extern "C" int mu_instances(const int* cls, const float* prob_or_null, int B, in
     if (!cls || !ids || !table || !score || !count || !order || !workspace || B <= 0 || H <= 0 || W <= 0) return MU_ERR_ARG;
     if (mu_instances_supported(H, W, max_inst) != MU_OK) return MU_ERR_SHAPE;
     if (ws_bytes < mu_instances_workspace_bytes(B, H, W, max_inst)) return MU_ERR_WORKSPACE;
+    if (!mu_lds_grant<inst_label_kernel>(INST_LDS_LABEL_MAX) || !inst_stats_granted()) return MU_ERR_LAUNCH;
     hipStream_t st = (hipStream_t)stream;
-    const int N = H * W, P = inst_pow2(max_inst);
-    int* first = (int*)workspace;
-    const size_t lds_label = (size_t)((N + 1) >> 1) * 4 + INST_WAVES * sizeof(unsigned);
-    const size_t lds_stats = (size_t)P * (5 * sizeof(unsigned) + sizeof(unsigned long long));
-    if (!inst_lds_granted()) return MU_ERR_LAUNCH;
-    inst_label_kernel<<<B, INST_THREADS, lds_label, st>>>(cls, N, W, max_inst, ids, count, first);
+    const int N = H * W, P = mu_pow2(max_inst);
+    const InstancesWs ws(workspace, B, max_inst);
+    inst_label_kernel<<<B, INST_THREADS, inst_label_lds(N), st>>>(cls, N, W, max_inst, ids, count, ws.first);
     MU_CHECK_LAUNCH();
-    inst_stats_kernel<<<B, INST_THREADS, lds_stats, st>>>(cls, prob_or_null, ids, count, first, nullptr, N, W, max_inst, P, table, score,
-                                                           order);
+    inst_stats_kernel<<<B, INST_THREADS, inst_stats_lds(P), st>>>(cls, prob_or_null, ids, count, ws.first, nullptr, N, W, max_inst, P, table,
+                                                                   score, order);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
@@ -704,14 +698,35 @@ extern "C" int mu_dbscan_supported(int H, int W, int D, int num_classes, int max
     return MU_OK;
 }
 
-static int db_max_tiles(int N, int num_classes) { return N / DB_TR + num_classes; }
+static constexpr int db_max_tiles(int N, int num_classes) { return N / DB_TR + num_classes; }
 
-// ints per image: perm, pos_of, link, lab [N each]; seg [num_classes + 1]; tiles [2 * max_tiles]; ntiles [1]; first [max_inst]
+struct DbscanWs {
+    MuCarve c;
+    int* perm;      // [B][N] pixels by class, raster order within a class
+    int* pos_of;    // [B][N] its inverse, -1 = background
+    int* link;      // [B][N] union-find parents of the core points
+    int* lab;       // [B][N] root per point, -1 = noise
+    int* seg;       // [B][num_classes + 1] start of every class in perm
+    int* tiles;     // [B][max_tiles][2] tile descriptors
+    int* ntiles;    // [B] tiles in use
+    int* first;     // [B][max_inst] first pixel of every instance, for the statistics kernel
+    constexpr DbscanWs(void* ws, int B, int N, int num_classes, int max_inst)
+        : c(ws), perm(c.take<int>((long)B * N)), pos_of(c.take<int>((long)B * N)), link(c.take<int>((long)B * N)),
+          lab(c.take<int>((long)B * N)), seg(c.take<int>((long)B * (num_classes + 1))),
+          tiles(c.take<int>((long)B * db_max_tiles(N, num_classes) * 2)), ntiles(c.take<int>(B)), first(c.take<int>((long)B * max_inst)) {}
+};
+static_assert(DbscanWs(nullptr, 2, 63, 3, 5).c.bytes == 2L * (4 * 63 + 3 + 1 + 2 * (63 / DB_TR + 3) + 1 + 5) * 4 &&
+              DbscanWs(nullptr, 3, 65536, 1024, 4096).c.bytes == 3L * (4 * 65536 + 1024 + 1 + 2 * (65536 / DB_TR + 1024) + 1 + 4096) * 4,
+              "mu_dbscan_instances workspace");
+
 extern "C" long mu_dbscan_workspace_bytes(int B, int H, int W, int num_classes, int max_inst) {
     if (B <= 0 || mu_dbscan_supported(H, W, 1, num_classes, max_inst) != MU_OK) return 0;
-    const long N = (long)H * W;
-    return (long)B * (4 * N + num_classes + 1 + 2 * db_max_tiles((int)N, num_classes) + 1 + max_inst) * (long)sizeof(int);
+    return DbscanWs(nullptr, B, H * W, num_classes, max_inst).c.bytes;
 }
+
+// dynamic LDS of the group and number kernels (44 KiB and 16 KiB at the limits: no grant needed)
+static size_t db_group_lds(int num_classes) { return (size_t)(DB_GROUP_WAVES + 3) * num_classes * sizeof(int); }
+static size_t db_number_lds(int max_inst) { return (size_t)(max_inst + INST_WAVES) * sizeof(int); }
 
 template <typename T, int DP>
 static int db_sweeps(const DbParams& P, int B, hipStream_t st) {
@@ -742,8 +757,10 @@ extern "C" int mu_dbscan_instances(const int* cls, const void* emb, int B, int H
     if (dtype != MU_F32 && dtype != MU_F16) return MU_ERR_ARG;
     if (mu_dbscan_supported(H, W, D, num_classes, max_inst) != MU_OK || min_samples < 1 || !(eps > 0.f) || B > 65535) return MU_ERR_SHAPE;
     if (ws_bytes < mu_dbscan_workspace_bytes(B, H, W, num_classes, max_inst)) return MU_ERR_WORKSPACE;
+    if (!inst_stats_granted()) return MU_ERR_LAUNCH;
     hipStream_t st = (hipStream_t)stream;
-    const int N = H * W, PW = inst_pow2(max_inst);
+    const int N = H * W, PW = mu_pow2(max_inst);
+    const DbscanWs ws(workspace, B, N, num_classes, max_inst);
     DbParams P;
     P.emb = emb;
     P.N = N;
@@ -756,26 +773,21 @@ extern "C" int mu_dbscan_instances(const int* cls, const void* emb, int B, int H
     P.c_stride = c_stride;
     P.p_stride = p_stride;
     P.eps2 = (double)eps * (double)eps;
-    int* w = (int*)workspace;
-    P.perm = w;
-    P.pos_of = P.perm + (long)B * N;
-    P.link = P.pos_of + (long)B * N;
-    P.lab = P.link + (long)B * N;
-    P.seg = P.lab + (long)B * N;
-    P.tiles = P.seg + (long)B * (num_classes + 1);
-    P.ntiles = P.tiles + (long)B * P.max_tiles * 2;
-    int* first = P.ntiles + B;
-    if (!inst_lds_granted()) return MU_ERR_LAUNCH;
-    const size_t lds_group = (size_t)(DB_GROUP_WAVES + 3) * num_classes * sizeof(int);
-    db_group_kernel<<<B, DB_GROUP_THREADS, lds_group, st>>>(cls, P);
+    P.perm = ws.perm;
+    P.pos_of = ws.pos_of;
+    P.link = ws.link;
+    P.lab = ws.lab;
+    P.seg = ws.seg;
+    P.tiles = ws.tiles;
+    P.ntiles = ws.ntiles;
+    db_group_kernel<<<B, DB_GROUP_THREADS, db_group_lds(num_classes), st>>>(cls, P);
     MU_CHECK_LAUNCH();
-    const int rc = dtype == MU_F16 ? db_sweeps_d<h16>(P, B, st) : db_sweeps_d<float>(P, B, st);
+    const int rc = with_storage(dtype, [&](auto tag) -> int { return db_sweeps_d<decltype(tag)>(P, B, st); });
     if (rc != MU_OK) return rc;
-    const size_t lds_number = (size_t)(max_inst + INST_WAVES) * sizeof(int);
-    db_number_kernel<<<B, INST_THREADS, lds_number, st>>>(P, max_inst, ids, count, first);
+    db_number_kernel<<<B, INST_THREADS, db_number_lds(max_inst), st>>>(P, max_inst, ids, count, ws.first);
     MU_CHECK_LAUNCH();
-    const size_t lds_stats = (size_t)PW * (5 * sizeof(unsigned) + sizeof(unsigned long long));
-    inst_stats_kernel<<<B, INST_THREADS, lds_stats, st>>>(cls, nullptr, ids, count, first, nullptr, N, W, max_inst, PW, table, score, order);
+    inst_stats_kernel<<<B, INST_THREADS, inst_stats_lds(PW), st>>>(cls, nullptr, ids, count, ws.first, nullptr, N, W, max_inst, PW, table, score,
+                                                                    order);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
@@ -879,7 +891,7 @@ __global__ __launch_bounds__(INST_THREADS) void inst_pairs_kernel(const int* __r
     }
 }
 
-static int pair_row_words(int max_inst_gt) { return (max_inst_gt + 1 + 31) >> 5; }      // bits 0..max_inst_gt
+static constexpr int pair_row_words(int max_inst_gt) { return (max_inst_gt + 1 + 31) >> 5; }      // bits 0..max_inst_gt
 
 extern "C" int mu_instance_pairs_supported(int H, int W, int max_inst_pred, int max_inst_gt) {
     if (H <= 0 || W <= 0 || (long)H * W > INST_MAX_PIXELS) return MU_ERR_SHAPE;
@@ -887,10 +899,20 @@ extern "C" int mu_instance_pairs_supported(int H, int W, int max_inst_pred, int 
     return MU_OK;
 }
 
-// per image: unsigned bits[max_inst_pred][words], unsigned pre[max_inst_pred][words]
+struct PairsWs {
+    MuCarve c;
+    unsigned* bits;     // [B][max_inst_pred][words] bit g of row p - 1: the pair (p, g) occurs
+    unsigned* pre;      // [B][max_inst_pred][words] set bits before each word: the pair's row
+    constexpr PairsWs(void* ws, int B, int max_inst_pred, int max_inst_gt)
+        : c(ws), bits(c.take<unsigned>((long)B * max_inst_pred * pair_row_words(max_inst_gt))),
+          pre(c.take<unsigned>((long)B * max_inst_pred * pair_row_words(max_inst_gt))) {}
+};
+static_assert(PairsWs(nullptr, 2, 5, 8).c.bytes == 2L * 5 * 1 * 2 * 4 && PairsWs(nullptr, 3, 4096, 4096).c.bytes == 3L * 4096 * 129 * 2 * 4,
+              "mu_instance_pairs workspace");
+
 extern "C" long mu_instance_pairs_workspace_bytes(int B, int H, int W, int max_inst_pred, int max_inst_gt) {
     if (B <= 0 || mu_instance_pairs_supported(H, W, max_inst_pred, max_inst_gt) != MU_OK) return 0;
-    return (long)B * max_inst_pred * pair_row_words(max_inst_gt) * 2 * (long)sizeof(unsigned);
+    return PairsWs(nullptr, B, max_inst_pred, max_inst_gt).c.bytes;
 }
 
 extern "C" int mu_instance_pairs(const int* pred_ids, const int* gt_ids, int B, int H, int W, int max_inst_pred, int max_inst_gt,
@@ -898,11 +920,9 @@ extern "C" int mu_instance_pairs(const int* pred_ids, const int* gt_ids, int B, 
     if (!pred_ids || !gt_ids || !pairs || !n_pairs || !workspace || B <= 0 || H <= 0 || W <= 0) return MU_ERR_ARG;
     if (mu_instance_pairs_supported(H, W, max_inst_pred, max_inst_gt) != MU_OK) return MU_ERR_SHAPE;
     if (ws_bytes < mu_instance_pairs_workspace_bytes(B, H, W, max_inst_pred, max_inst_gt)) return MU_ERR_WORKSPACE;
-    const int GW = pair_row_words(max_inst_gt);
-    unsigned* bits = (unsigned*)workspace;
-    unsigned* pre = bits + (long)B * max_inst_pred * GW;
-    inst_pairs_kernel<<<B, INST_THREADS, 0, (hipStream_t)stream>>>(pred_ids, gt_ids, H * W, max_inst_pred, max_inst_gt, GW, bits, pre,
-                                                                    pairs, n_pairs);
+    const PairsWs ws(workspace, B, max_inst_pred, max_inst_gt);
+    inst_pairs_kernel<<<B, INST_THREADS, 0, (hipStream_t)stream>>>(pred_ids, gt_ids, H * W, max_inst_pred, max_inst_gt,
+                                                                    pair_row_words(max_inst_gt), ws.bits, ws.pre, pairs, n_pairs);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
@@ -1078,11 +1098,20 @@ extern "C" int mu_instance_match_supported(int H, int W, int max_inst_pred, int 
     return MU_OK;
 }
 
-// int first_row[B][K]: where each detection's rows start in the pair table
+struct MatchWs {
+    MuCarve c;
+    int* dstart;    // [B][K] where each detection's rows start in the pair table
+    constexpr MatchWs(void* ws, int B, int K) : c(ws), dstart(c.take<int>((long)B * K)) {}
+};
+static_assert(MatchWs(nullptr, 2, 5).c.bytes == 2 * 5 * 4 && MatchWs(nullptr, 3, 4096).c.bytes == 3 * 4096 * 4, "mu_instance_match workspace");
+
 extern "C" long mu_instance_match_workspace_bytes(int B, int K) {
     if (B <= 0 || K < 1 || K > INST_MAX_INSTANCES) return 0;
-    return (long)B * K * (long)sizeof(int);
+    return MatchWs(nullptr, B, K).c.bytes;
 }
+
+// dynamic LDS of the two match kernels: 57348 and 58372 bytes at the limits, no grant needed
+static size_t inst_match_lds(int K, int max_inst_gt, int num_classes) { return (size_t)(2 * K + max_inst_gt + 2 * num_classes + 1) * sizeof(int); }
 
 extern "C" int mu_instance_match(const int* pairs, const int* n_pairs, const int* pred_table, const float* pred_score,
                                  const int* pred_order, const int* pred_count, const int* gt_table, const int* gt_count, int B, int H,
@@ -1124,10 +1153,9 @@ extern "C" int mu_instance_match(const int* pairs, const int* n_pairs, const int
     P.pq_iou = pq_iou;
     P.pq_fp = pq_fp;
     P.overflow = overflow;
-    P.dstart = (int*)workspace;
+    P.dstart = MatchWs(workspace, B, K).dstart;
     for (int t = 0; t < MATCH_MAX_T; ++t) P.thr[t] = t < T ? thr[t] : 1.0;
-    const size_t lds = (size_t)(2 * K + max_inst_gt + 2 * num_classes + 1) * sizeof(int);      // 57348 bytes at the limits: no grant needed
-    inst_match_kernel<<<B, INST_THREADS, lds, (hipStream_t)stream>>>(P);
+    inst_match_kernel<<<B, INST_THREADS, inst_match_lds(K, max_inst_gt, num_classes), (hipStream_t)stream>>>(P);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
@@ -1163,6 +1191,9 @@ struct CocoParams {
 };
 
 static int coco_bit_words(int max_inst_gt) { return ((max_inst_gt + 63) >> 6) << 1; }      // whole 64-lane ballots
+static size_t coco_match_lds(int K, int max_inst_gt, int num_classes) {
+    return inst_match_lds(K, max_inst_gt, num_classes) + (size_t)2 * coco_bit_words(max_inst_gt) * sizeof(int);
+}
 
 __device__ __forceinline__ bool coco_bit(const unsigned* bits, int g) { return (bits[(g - 1) >> 5] >> ((g - 1) & 31)) & 1u; }
 
@@ -1369,7 +1400,7 @@ extern "C" int mu_coco_match_supported(int H, int W, int max_inst_pred, int max_
     return MU_OK;
 }
 
-// int first_row[B][K], as mu_instance_match
+// MatchWs, as mu_instance_match
 extern "C" long mu_coco_match_workspace_bytes(int B, int K) { return mu_instance_match_workspace_bytes(B, K); }
 
 extern "C" int mu_coco_match(const int* pairs, const int* n_pairs, const int* pred_table, const float* pred_score, const int* pred_order,
@@ -1421,15 +1452,13 @@ extern "C" int mu_coco_match(const int* pairs, const int* n_pairs, const int* pr
     P.pq_iou = pq_iou;
     P.pq_fp = pq_fp;
     P.overflow = overflow;
-    P.dstart = (int*)workspace;
+    P.dstart = MatchWs(workspace, B, K).dstart;
     for (int t = 0; t < MATCH_MAX_T; ++t) P.thr[t] = t < T ? thr[t] : 1.0;
     for (int a = 0; a < COCO_MAX_A; ++a) {
         P.rng[a][0] = a < A ? area_rng[2 * a] : 0.0;
         P.rng[a][1] = a < A ? area_rng[2 * a + 1] : 0.0;
     }
-    // 58372 bytes at the limits: no grant needed
-    const size_t lds = (size_t)(2 * K + max_inst_gt + 2 * num_classes + 1 + 2 * coco_bit_words(max_inst_gt)) * sizeof(int);
-    coco_match_kernel<<<B, INST_THREADS, lds, (hipStream_t)stream>>>(P);
+    coco_match_kernel<<<B, INST_THREADS, coco_match_lds(K, max_inst_gt, num_classes), (hipStream_t)stream>>>(P);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }
@@ -1687,12 +1716,38 @@ extern "C" int mu_id_instances_supported(int H, int W, int max_inst, int class_c
     return MU_OK;
 }
 
-// ints per image: keys [2 N], first [max_inst], inst_cls [max_inst], bits and pre [max_inst * words each], pairs [3 N], n_pairs [1]
+struct IdmapWs {
+    MuCarve c;
+    unsigned* keys;     // [B][2][N] the radix sort's two key buffers
+    int* first;         // [B][max_inst] first pixel of every instance, for the statistics kernel
+    int* inst_cls;      // [B][max_inst] the median class of every instance
+    unsigned* bits;     // [B][max_inst][words] the pair bitmap of (id, class), as PairsWs
+    unsigned* pre;      // [B][max_inst][words]
+    int* pairs;         // [B][N][3] the pair table of (id, class)
+    int* n_pairs;       // [B] its rows
+    constexpr IdmapWs(void* ws, int B, int N, int max_inst, int class_cap)
+        : c(ws), keys(c.take<unsigned>((long)B * N * 2)), first(c.take<int>((long)B * max_inst)), inst_cls(c.take<int>((long)B * max_inst)),
+          bits(c.take<unsigned>((long)B * max_inst * pair_row_words(class_cap - 1))),
+          pre(c.take<unsigned>((long)B * max_inst * pair_row_words(class_cap - 1))), pairs(c.take<int>((long)B * N * 3)),
+          n_pairs(c.take<int>(B)) {}
+};
+static_assert(IdmapWs(nullptr, 2, 63, 5, 4).c.bytes == 2L * (5 * 63 + 2 * 5 * (1 + 1) + 1) * 4 &&
+              IdmapWs(nullptr, 3, 65536, 4096, 1024).c.bytes == 3L * (5 * 65536 + 2L * 4096 * (1 + 32) + 1) * 4, "mu_id_instances workspace");
+
 extern "C" long mu_id_instances_workspace_bytes(int B, int H, int W, int max_inst, int class_cap) {
     if (B <= 0 || mu_id_instances_supported(H, W, max_inst, class_cap) != MU_OK) return 0;
-    const long N = (long)H * W;
-    return (long)B * (5 * N + 2L * max_inst * (1 + pair_row_words(class_cap - 1)) + 1) * (long)sizeof(int);
+    return IdmapWs(nullptr, B, H * W, max_inst, class_cap).c.bytes;
 }
+
+// kind dispatch (host): f(integral_constant<int, KIND>) for the three id-map kinds; any other kind is MU_ERR_ARG
+template <typename F>
+static inline int with_idmap_kind(int id_kind, F&& f) {
+    if (id_kind == MU_IDMAP_I32) return f(std::integral_constant<int, MU_IDMAP_I32>{});
+    if (id_kind == MU_IDMAP_I64) return f(std::integral_constant<int, MU_IDMAP_I64>{});
+    if (id_kind == MU_IDMAP_RGB8) return f(std::integral_constant<int, MU_IDMAP_RGB8>{});
+    return MU_ERR_ARG;
+}
+static size_t idmap_rank_lds(int max_inst) { return (size_t)((INST_WAVES + 1) * IDMAP_DIGITS + max_inst) * sizeof(int); }      // 13 KiB + 16 KiB
 
 extern "C" int mu_id_instances(const void* id_map, int id_kind, const int* sem, int B, int H, int W, int max_inst, int class_cap, int* ids,
                                int* table, float* score, int* count, int* order, int* values, int* invalid, void* workspace,
@@ -1702,33 +1757,24 @@ extern "C" int mu_id_instances(const void* id_map, int id_kind, const int* sem, 
     if (id_kind != MU_IDMAP_I32 && id_kind != MU_IDMAP_I64 && id_kind != MU_IDMAP_RGB8) return MU_ERR_ARG;
     if (mu_id_instances_supported(H, W, max_inst, class_cap) != MU_OK) return MU_ERR_SHAPE;
     if (ws_bytes < mu_id_instances_workspace_bytes(B, H, W, max_inst, class_cap)) return MU_ERR_WORKSPACE;
+    if (!inst_stats_granted()) return MU_ERR_LAUNCH;
     hipStream_t st = (hipStream_t)stream;
-    const int N = H * W, P = inst_pow2(max_inst), GW = pair_row_words(class_cap - 1);
-    unsigned* keys = (unsigned*)workspace;
-    int* first = (int*)(keys + (long)B * N * 2);
-    int* inst_cls = first + (long)B * max_inst;
-    unsigned* bits = (unsigned*)(inst_cls + (long)B * max_inst);
-    unsigned* pre = bits + (long)B * max_inst * GW;
-    int* pairs = (int*)(pre + (long)B * max_inst * GW);
-    int* n_pairs = pairs + (long)B * N * 3;
-    if (!inst_lds_granted()) return MU_ERR_LAUNCH;
-    const size_t lds_rank = (size_t)((INST_WAVES + 1) * IDMAP_DIGITS + max_inst) * sizeof(int);
-    if (id_kind == MU_IDMAP_I32)
-        idmap_rank_kernel<MU_IDMAP_I32><<<B, INST_THREADS, lds_rank, st>>>(id_map, sem, N, max_inst, class_cap, keys, ids, count, values,
-                                                                          invalid, first);
-    else if (id_kind == MU_IDMAP_I64)
-        idmap_rank_kernel<MU_IDMAP_I64><<<B, INST_THREADS, lds_rank, st>>>(id_map, sem, N, max_inst, class_cap, keys, ids, count, values,
-                                                                          invalid, first);
-    else
-        idmap_rank_kernel<MU_IDMAP_RGB8><<<B, INST_THREADS, lds_rank, st>>>(id_map, sem, N, max_inst, class_cap, keys, ids, count, values,
-                                                                           invalid, first);
+    const int N = H * W, P = mu_pow2(max_inst);
+    const IdmapWs ws(workspace, B, N, max_inst, class_cap);
+    const int rc = with_idmap_kind(id_kind, [&](auto kind) -> int {
+        idmap_rank_kernel<decltype(kind)::value><<<B, INST_THREADS, idmap_rank_lds(max_inst), st>>>(id_map, sem, N, max_inst, class_cap, ws.keys, ids,
+                                                                                                     count, values, invalid, ws.first);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
+    if (rc != MU_OK) return rc;
+    inst_pairs_kernel<<<B, INST_THREADS, 0, st>>>(ids, sem, N, max_inst, class_cap - 1, pair_row_words(class_cap - 1), ws.bits, ws.pre, ws.pairs,
+                                                   ws.n_pairs);
     MU_CHECK_LAUNCH();
-    inst_pairs_kernel<<<B, INST_THREADS, 0, st>>>(ids, sem, N, max_inst, class_cap - 1, GW, bits, pre, pairs, n_pairs);
+    idmap_median_kernel<<<B, INST_THREADS, 0, st>>>(ws.pairs, ws.n_pairs, count, N, max_inst, ws.inst_cls);
     MU_CHECK_LAUNCH();
-    idmap_median_kernel<<<B, INST_THREADS, 0, st>>>(pairs, n_pairs, count, N, max_inst, inst_cls);
-    MU_CHECK_LAUNCH();
-    const size_t lds_stats = (size_t)P * (5 * sizeof(unsigned) + sizeof(unsigned long long));
-    inst_stats_kernel<<<B, INST_THREADS, lds_stats, st>>>(sem, nullptr, ids, count, first, inst_cls, N, W, max_inst, P, table, score, order);
+    inst_stats_kernel<<<B, INST_THREADS, inst_stats_lds(P), st>>>(sem, nullptr, ids, count, ws.first, ws.inst_cls, N, W, max_inst, P, table, score,
+                                                                   order);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }

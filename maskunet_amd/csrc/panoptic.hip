@@ -27,7 +27,6 @@
 #define PAN_MAX_ROWS 4096                                      // max_inst and max_seg
 #define PAN_MAX_CLASSES 1024
 #define PAN_NONE 0x7fffffff
-#define PAN_LDS_MAX ((2 * (PAN_MAX_ROWS + PAN_MAX_CLASSES) + PAN_MAX_CLASSES + 5 * PAN_MAX_ROWS) * 4)
 
 struct PanParams {
     const int* cls;
@@ -272,18 +271,11 @@ __global__ __launch_bounds__(PAN_THREADS) void panoptic_kernel(const PanParams P
     for (int r = tid; r < max_seg; r += PAN_THREADS) seg_order[r] = r < M ? (int)(unsigned)(keys[r] & 0xffffffffull) : 0;
 }
 
-static int pan_pow2(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
+// dynamic LDS of panoptic_kernel; more than 64 KiB at the limits, so granted to the most it can ask for (common.h: mu_lds_grant)
+static constexpr size_t pan_lds_bytes(int max_inst, int num_classes, int max_seg) {
+    return (size_t)(2 * (max_inst + num_classes) + num_classes + 5 * max_seg) * sizeof(int);
 }
-
-// more than 64 KiB of dynamic LDS is granted per kernel, once per process, to the most the kernel can ask for (as instances.hip does)
-static bool pan_lds_granted() {
-    static const bool ok =
-        hipFuncSetAttribute((const void*)panoptic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PAN_LDS_MAX) == hipSuccess;
-    return ok;
-}
+#define PAN_LDS_MAX ((int)pan_lds_bytes(PAN_MAX_ROWS, PAN_MAX_CLASSES, PAN_MAX_ROWS))
 
 extern "C" int mu_panoptic_supported(int H, int W, int max_inst, int num_classes, int max_seg, int label_divisor, int stuff_area_limit,
                                      int thing_area_limit) {
@@ -294,10 +286,16 @@ extern "C" int mu_panoptic_supported(int H, int W, int max_inst, int num_classes
     return MU_OK;
 }
 
-// unsigned long long keys[B][max_seg rounded up to a power of two]: the score order is sorted here
+struct PanWs {
+    MuCarve c;
+    unsigned long long* keys;       // [B][max_seg rounded up to a power of two] the score order is sorted here
+    constexpr PanWs(void* ws, int B, int max_seg) : c(ws), keys(c.take<unsigned long long>((long)B * mu_pow2(max_seg))) {}
+};
+static_assert(PanWs(nullptr, 2, 5).c.bytes == 2 * 8 * 8 && PanWs(nullptr, 3, 4096).c.bytes == 3 * 4096 * 8, "mu_panoptic workspace");
+
 extern "C" long mu_panoptic_workspace_bytes(int B, int H, int W, int max_inst, int num_classes, int max_seg) {
     if (B <= 0 || mu_panoptic_supported(H, W, max_inst, num_classes, max_seg, 1, 0, 0) != MU_OK) return 0;
-    return (long)B * pan_pow2(max_seg) * (long)sizeof(unsigned long long);
+    return PanWs(nullptr, B, max_seg).c.bytes;
 }
 
 extern "C" int mu_panoptic(const int* cls, const int* ids, const int* table, const float* score, const int* count, const int* kind,
@@ -313,6 +311,7 @@ extern "C" int mu_panoptic(const int* cls, const int* ids, const int* table, con
     if (mu_panoptic_supported(H, W, max_inst, num_classes, max_seg, label_divisor, stuff_area_limit, thing_area_limit) != MU_OK)
         return MU_ERR_SHAPE;
     if (ws_bytes < mu_panoptic_workspace_bytes(B, H, W, max_inst, num_classes, max_seg)) return MU_ERR_WORKSPACE;
+    if (!mu_lds_grant<panoptic_kernel>(PAN_LDS_MAX)) return MU_ERR_LAUNCH;
     PanParams P;
     P.cls = cls;
     P.ids = ids;
@@ -326,7 +325,7 @@ extern "C" int mu_panoptic(const int* cls, const int* ids, const int* table, con
     P.max_inst = max_inst;
     P.num_classes = num_classes;
     P.max_seg = max_seg;
-    P.P = pan_pow2(max_seg);
+    P.P = mu_pow2(max_seg);
     P.label_divisor = label_divisor;
     P.stuff_area_limit = stuff_area_limit;
     P.thing_area_limit = thing_area_limit;
@@ -343,10 +342,8 @@ extern "C" int mu_panoptic(const int* cls, const int* ids, const int* table, con
     P.invalid = invalid;
     P.seg_score = seg_score;
     P.rgb = rgb;
-    P.keys = (unsigned long long*)workspace;
-    if (!pan_lds_granted()) return MU_ERR_LAUNCH;
-    const size_t lds = (size_t)(2 * (max_inst + num_classes) + num_classes + 5 * max_seg) * sizeof(int);
-    panoptic_kernel<<<B, PAN_THREADS, lds, (hipStream_t)stream>>>(P);
+    P.keys = PanWs(workspace, B, max_seg).keys;
+    panoptic_kernel<<<B, PAN_THREADS, pan_lds_bytes(max_inst, num_classes, max_seg), (hipStream_t)stream>>>(P);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }

@@ -294,16 +294,17 @@ extern "C" int mu_pil_resize_u8_nhwc(const unsigned char* src, const long* offse
     const long blocks = (long)B * bands * chunks;
     if (blocks > 0x7fffffffL) return MU_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    const long nco = (long)B * (Wd + Hd);
-    const int cgrid = (int)((nco + 255) / 256 < 65536 ? (nco + 255) / 256 : 65536);
-    pil_coeff_kernel<<<cgrid, 256, 0, st>>>(offsets, sizes, B, C, max_h, max_w, Hd, Wd, (int*)workspace, valid);
+    pil_coeff_kernel<<<mu_grid((long)B * (Wd + Hd), 256, 65536), 256, 0, st>>>(offsets, sizes, B, C, max_h, max_w, Hd, Wd, (int*)workspace, valid);
     MU_CHECK_LAUNCH();
-#define PIL_LAUNCH(T, CC) \
-    pil_resample_kernel<T, CC><<<(unsigned)blocks, PIL_COLS * CC, 0, st>>>(src, offsets, sizes, max_h, max_w, swap_rb, (T*)dst, u8_out, Hd, Wd, \
-                                                                           Cp, (const int*)workspace, bands, chunks)
-    if (dtype == MU_F32) { if (C == 1) PIL_LAUNCH(float, 1); else PIL_LAUNCH(float, 3); }
-    else { if (C == 1) PIL_LAUNCH(h16, 1); else PIL_LAUNCH(h16, 3); }
-#undef PIL_LAUNCH
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    auto resample = [&](auto tag, auto channels) -> int {
+        using T = decltype(tag);
+        constexpr int CC = decltype(channels)::value;
+        pil_resample_kernel<T, CC><<<(unsigned)blocks, PIL_COLS * CC, 0, st>>>(src, offsets, sizes, max_h, max_w, swap_rb, (T*)dst, u8_out, Hd, Wd, Cp,
+                                                                              (const int*)workspace, bands, chunks);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    };
+    return with_storage(dtype, [&](auto tag) -> int {
+        return C == 1 ? resample(tag, std::integral_constant<int, 1>{}) : resample(tag, std::integral_constant<int, 3>{});
+    });
 }

@@ -227,13 +227,9 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_encode_kernel(const RleParams
     for (int i = word0 / 4 + tid; i < L; i += RLE_THREADS) strw[i] = 0;
 }
 
-static size_t rle_lds_bytes(int K) { return (size_t)K * (4 * sizeof(int) + RLE_WAVES * sizeof(rle_u16)) + 2 * sizeof(int); }
-static bool rle_lds_granted() {                        // once per process, to the most the kernel can ever ask for (see inst_lds_granted)
-    static const bool ok =
-        hipFuncSetAttribute((const void*)rle_encode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)rle_lds_bytes(RLE_MAX_ROWS)) == hipSuccess;
-    return ok;
-}
+// dynamic LDS of rle_encode_kernel; granted to the most it can ask for (common.h: mu_lds_grant)
+static constexpr size_t rle_lds_bytes(int K) { return (size_t)K * (4 * sizeof(int) + RLE_WAVES * sizeof(rle_u16)) + 2 * sizeof(int); }
+#define RLE_LDS_MAX ((int)rle_lds_bytes(RLE_MAX_ROWS))
 
 extern "C" int mu_rle_encode_supported(int H, int W, int K, int max_id) {
     if (H <= 0 || W <= 0 || (long)H * W > RLE_MAX_PIXELS) return MU_ERR_SHAPE;
@@ -241,11 +237,19 @@ extern "C" int mu_rle_encode_supported(int H, int W, int K, int max_id) {
     return MU_OK;
 }
 
-static long rle_ws_ints(long N, int max_id) { return (long)max_id + 1 + 2 * N + (N + 1) / 2; }
+// ints of workspace per image, carved by the kernel: table [max_id + 1], bnd [2 N], rowmap [N] as 16-bit values
+static constexpr long rle_ws_ints(long N, int max_id) { return (long)max_id + 1 + 2 * N + (N + 1) / 2; }
+struct RleWs {
+    MuCarve c;
+    int* images;    // [B][rle_ws_ints] one slab per image (RleParams::ws, ws_stride)
+    constexpr RleWs(void* ws, int B, long N, int max_id) : c(ws), images(c.take<int>((long)B * rle_ws_ints(N, max_id))) {}
+};
+static_assert(RleWs(nullptr, 2, 63, 5).c.bytes == 2L * (5 + 1 + 2 * 63 + 32) * 4 && RleWs(nullptr, 3, 64, 8).c.bytes == 3L * (8 + 1 + 2 * 64 + 32) * 4,
+              "mu_rle_encode workspace");
 
 extern "C" long mu_rle_encode_workspace_bytes(int B, int H, int W, int K, int max_id) {
     if (B <= 0 || mu_rle_encode_supported(H, W, K, max_id) != MU_OK) return 0;
-    return (long)B * rle_ws_ints((long)H * W, max_id) * (long)sizeof(int);
+    return RleWs(nullptr, B, (long)H * W, max_id).c.bytes;
 }
 
 extern "C" int mu_rle_encode(const int* ids, const int* sel, int B, int H, int W, int K, int max_id, int* offsets, int* counts, int* area,
@@ -255,6 +259,7 @@ extern "C" int mu_rle_encode(const int* ids, const int* sel, int B, int H, int W
     if ((uintptr_t)str_bytes & 3) return MU_ERR_ARG;      // the tail of the strings is zeroed by words
     if (mu_rle_encode_supported(H, W, K, max_id) != MU_OK) return MU_ERR_SHAPE;
     if (ws_bytes < mu_rle_encode_workspace_bytes(B, H, W, K, max_id)) return MU_ERR_WORKSPACE;
+    if (!mu_lds_grant<rle_encode_kernel>(RLE_LDS_MAX)) return MU_ERR_LAUNCH;
     RleParams P;
     P.ids = ids;
     P.sel = sel;
@@ -270,8 +275,7 @@ extern "C" int mu_rle_encode(const int* ids, const int* sel, int B, int H, int W
     P.area = area;
     P.str_offsets = str_offsets;
     P.str_bytes = str_bytes;
-    P.ws = (int*)workspace;
-    if (!rle_lds_granted()) return MU_ERR_LAUNCH;
+    P.ws = RleWs(workspace, B, P.N, max_id).images;
     rle_encode_kernel<<<B, RLE_THREADS, rle_lds_bytes(K), (hipStream_t)stream>>>(P);
     MU_CHECK_LAUNCH();
     return MU_OK;

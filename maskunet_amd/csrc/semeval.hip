@@ -41,10 +41,10 @@ static inline int sem_bpi(int B, long HW) {
     const long by_grid = B >= SE_TARGET_BLOCKS ? 1 : (SE_TARGET_BLOCKS + B - 1) / B;
     return (int)(by_rows < by_grid ? by_rows : by_grid);
 }
-static inline size_t sem_lds_bytes(int C, bool lds_conf) {
+static constexpr size_t sem_lds_bytes(int C, bool lds_conf) {
     return ((size_t)3 * C + (lds_conf ? (size_t)(C + 1) * C : 0)) * sizeof(unsigned);
 }
-#define SE_LDS_MAX ((3 * MU_SEM_EVAL_LDS_MAX_C + (MU_SEM_EVAL_LDS_MAX_C + 1) * MU_SEM_EVAL_LDS_MAX_C) * 4)
+#define SE_LDS_MAX ((int)sem_lds_bytes(MU_SEM_EVAL_LDS_MAX_C, true))
 static_assert(SE_LDS_MAX + 1024 <= 160 * 1024, "the privatised confusion matrix must fit the 160 KiB of a CU");
 
 // offset of pixel row r = b * HW + p: the two layouts a module output has are division-free
@@ -317,41 +317,53 @@ __global__ void sem_loss_final_kernel(const double* __restrict__ part, int B, in
     img_loss[b * 2 + 1] = n;
 }
 
-// once per process and kernel: the most dynamic LDS it can ever ask for (see inst_lds_granted, instances.hip)
-template <auto KERNEL>
-static bool sem_lds_granted() {
-    static const bool ok = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, SE_LDS_MAX) == hipSuccess;
-    return ok;
-}
-template <auto KERNEL>
-static int sem_launch(const SemParams& P, int grid, int threads, size_t lds, hipStream_t st) {
-    if (lds > 48 * 1024 && !sem_lds_granted<KERNEL>()) return MU_ERR_LAUNCH;
-    KERNEL<<<grid, threads, lds, st>>>(P);
-    return MU_OK;
-}
-template <typename T, bool PROB>
-static int sem_launch_vec(const SemParams& P, int grid, size_t lds, hipStream_t st) {
-    constexpr int VN = Vec16<T>::N;
-    const int nv = (P.C + 16 * VN - 1) / (16 * VN);
-    if (nv == 1) return sem_launch<sem_eval_vec_kernel<T, 1, 4, PROB>>(P, grid, SE_THREADS, lds, st);
-    if (nv == 2) return sem_launch<sem_eval_vec_kernel<T, 2, 4, PROB>>(P, grid, SE_THREADS, lds, st);
-    if (nv == 3) return sem_launch<sem_eval_vec_kernel<T, 3, 2, PROB>>(P, grid, SE_THREADS, lds, st);
-    return sem_launch<sem_eval_vec_kernel<T, 0, 1, PROB>>(P, grid, SE_THREADS, lds, st);
+// The sweep kernel of a call, picked before anything is enqueued: its launch, and its LDS grant (common.h: mu_lds_grant), which a call
+// asks for only where it needs more than 48 KiB.  The kernels are launched by name: a host object built with the sanitizers drops a launch
+// through a kernel-valued template parameter (tools/post_host_launches.cpp would record no sweep).
+struct SemSweep {
+    void (*launch)(const SemParams& P, int grid, size_t lds, hipStream_t st);
+    bool (*grant)(int max_bytes);
+};
+template <typename T, int NV, int RPW, bool PROB>
+static SemSweep sem_sweep_vec_as() {
+    return {[](const SemParams& P, int grid, size_t lds, hipStream_t st) { sem_eval_vec_kernel<T, NV, RPW, PROB><<<grid, SE_THREADS, lds, st>>>(P); },
+            mu_lds_grant<sem_eval_vec_kernel<T, NV, RPW, PROB>>};
 }
 template <typename T>
-static int sem_launch_t(const SemParams& P, int grid, size_t lds, hipStream_t st) {
+static SemSweep sem_sweep_strided() {
+    return {[](const SemParams& P, int grid, size_t lds, hipStream_t st) { sem_eval_strided_kernel<T><<<grid, SE_STRIDED_THREADS, lds, st>>>(P); },
+            mu_lds_grant<sem_eval_strided_kernel<T>>};
+}
+template <typename T, bool PROB>
+static SemSweep sem_sweep_vec(const SemParams& P) {
+    constexpr int VN = Vec16<T>::N;
+    const int nv = (P.C + 16 * VN - 1) / (16 * VN);
+    if (nv == 1) return sem_sweep_vec_as<T, 1, 4, PROB>();
+    if (nv == 2) return sem_sweep_vec_as<T, 2, 4, PROB>();
+    if (nv == 3) return sem_sweep_vec_as<T, 3, 2, PROB>();
+    return sem_sweep_vec_as<T, 0, 1, PROB>();
+}
+template <typename T>
+static SemSweep sem_sweep_t(const SemParams& P) {
     constexpr long VN = Vec16<T>::N;
     const long row = (P.C + VN - 1) / VN * VN;                 // what the 16-byte loads of a row touch
     const bool vec = P.cs == 1 && P.ps % VN == 0 && P.outer % VN == 0 && ((uintptr_t)P.logits & 15) == 0 && P.ps >= row;
-    if (!vec) return sem_launch<sem_eval_strided_kernel<T>>(P, grid, SE_STRIDED_THREADS, lds, st);
-    return P.prob ? sem_launch_vec<T, true>(P, grid, lds, st) : sem_launch_vec<T, false>(P, grid, lds, st);
+    if (!vec) return sem_sweep_strided<T>();
+    return P.prob ? sem_sweep_vec<T, true>(P) : sem_sweep_vec<T, false>(P);
 }
 
 extern "C" int mu_sem_eval_supported(int C) { return C >= 1 && C <= 4096 ? MU_OK : MU_ERR_SHAPE; }
 
+struct SemWs {
+    MuCarve c;
+    double* part;       // [B][blocks per image][2] (loss sum, counted pixels) of every block
+    constexpr SemWs(void* ws, int B, int bpi) : c(ws), part(c.take<double>((long)B * bpi * 2)) {}
+};
+static_assert(SemWs(nullptr, 2, 3).c.bytes == 2 * 3 * 2 * 8 && SemWs(nullptr, 5, 1).c.bytes == 5 * 2 * 8, "mu_sem_eval workspace");
+
 extern "C" long mu_sem_eval_workspace_bytes(int B, long HW, int C) {
     if (B < 1 || HW < 1 || HW >= (1L << 31) || mu_sem_eval_supported(C) != MU_OK) return 0;
-    return (long)B * sem_bpi(B, HW) * 2 * (long)sizeof(double);
+    return SemWs(nullptr, B, sem_bpi(B, HW)).c.bytes;
 }
 
 extern "C" int mu_sem_eval(const void* logits, const long* labels, int B, long HW, int C, long inner, long outer_stride, long c_stride,
@@ -370,14 +382,15 @@ extern "C" int mu_sem_eval(const void* logits, const long* labels, int B, long H
     P.inner = inner; P.outer = outer_stride; P.cs = c_stride; P.ps = p_stride;
     P.ignore = ignore_index; P.k2 = inv_temperature * 1.44269504088896340736f;
     P.img_counts = img_counts; P.confusion = (unsigned long long*)confusion; P.cls = cls_or_null; P.prob = prob_or_null;
-    P.part = (double*)workspace;
+    P.part = SemWs(workspace, B, bpi).part;
     P.lds_conf = C <= MU_SEM_EVAL_LDS_MAX_C;
     const size_t lds = sem_lds_bytes(C, P.lds_conf);
+    SemSweep sweep;
+    if (int e = with_storage(dtype, [&](auto tag) -> int { sweep = sem_sweep_t<decltype(tag)>(P); return MU_OK; })) return e;
+    if (lds > 48 * 1024 && !sweep.grant(SE_LDS_MAX)) return MU_ERR_LAUNCH;
     if (hipMemsetAsync(img_counts, 0, (size_t)B * 3 * C * sizeof(int), st) != hipSuccess) return MU_ERR_LAUNCH;
-    const int grid = B * bpi;
-    const int rc = dtype == MU_F16 ? sem_launch_t<h16>(P, grid, lds, st) : sem_launch_t<float>(P, grid, lds, st);
-    if (rc != MU_OK) return rc;
-    sem_loss_final_kernel<<<(B + 255) / 256, 256, 0, st>>>((const double*)workspace, B, bpi, img_loss);
+    sweep.launch(P, B * bpi, lds, st);
+    sem_loss_final_kernel<<<(B + 255) / 256, 256, 0, st>>>(P.part, B, bpi, img_loss);
     MU_CHECK_LAUNCH();
     return MU_OK;
 }

@@ -226,13 +226,12 @@ __global__ __launch_bounds__(SN_THREADS) void sem_native_kernel(const NativePara
     }
 }
 
-// once per process and kernel: the most dynamic LDS it can ever ask for (see sem_lds_granted, semeval.hip)
-template <typename T>
-bool native_lds_granted() {
-    static const bool ok = hipFuncSetAttribute((const void*)sem_native_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)SN_LDS_BYTES) == hipSuccess;
-    return ok;
-}
+struct NativeWs {
+    MuCarve c;
+    NativeImage* images;        // [B] written by the prepare kernel, read by the sweep
+    constexpr NativeWs(void* ws, int B) : c(ws), images(c.take<NativeImage>(B)) {}
+};
+static_assert(NativeWs(nullptr, 2).c.bytes == 64 && NativeWs(nullptr, 5).c.bytes == 160, "mu_sem_eval_native workspace");
 
 }  // namespace
 
@@ -242,7 +241,7 @@ extern "C" int mu_sem_eval_native_supported(int C, int h, int w) {
 
 extern "C" long mu_sem_eval_native_workspace_bytes(int B, int C, int h, int w, int max_h, int max_w) {
     if (B < 1 || max_h < 1 || max_w < 1 || max_h > 16384 || max_w > 16384 || mu_sem_eval_native_supported(C, h, w) != MU_OK) return 0;
-    return (long)B * (long)sizeof(NativeImage);
+    return NativeWs(nullptr, B).c.bytes;
 }
 
 extern "C" int mu_sem_eval_native(const void* logits, int B, int C, int h, int w, long inner, long outer_stride, long c_stride, long p_stride,
@@ -258,10 +257,10 @@ extern "C" int mu_sem_eval_native(const void* logits, int B, int C, int h, int w
     if (blocks > 0x7fffffffL) return MU_ERR_SHAPE;
     if (ws_bytes < mu_sem_eval_native_workspace_bytes(B, C, h, w, max_h, max_w)) return MU_ERR_WORKSPACE;
     const NativeLds lds = native_lds(C, h, w);
-    if (lds.bytes > 48 * 1024 && !(dtype == MU_F16 ? native_lds_granted<h16>() : native_lds_granted<float>())) return MU_ERR_LAUNCH;
+    const NativeWs ws(workspace, B);
     hipStream_t st = (hipStream_t)stream;
     NativeParams P;
-    P.logits = logits; P.labels = labels; P.images = (const NativeImage*)workspace;
+    P.logits = logits; P.labels = labels; P.images = ws.images;
     P.C = C; P.h = h; P.w = w;
     P.HW = (long)h * w; P.M = (long)B * P.HW; P.inner = inner; P.outer = outer_stride; P.cs = c_stride; P.ps = p_stride;
     P.ignore = ignore_index;
@@ -269,11 +268,14 @@ extern "C" int mu_sem_eval_native(const void* logits, int B, int C, int h, int w
     P.tiles_x = tiles_x; P.tiles_per_image = tiles_y * tiles_x;
     P.win_floats = (int)lds.win_floats; P.lds_conf = lds.lds_conf ? 1 : 0;
     const long n_counts = (long)B * 3 * C;
-    sem_native_prepare_kernel<<<mu_grid(n_counts > B ? n_counts : B, 256, 1024), 256, 0, st>>>(offsets, sizes, B, h, w, max_h, max_w,
-                                                                                            (NativeImage*)workspace, valid, img_counts, n_counts);
-    MU_CHECK_LAUNCH();
-    if (dtype == MU_F16) sem_native_kernel<h16><<<(unsigned)blocks, SN_THREADS, (size_t)lds.bytes, st>>>(P);
-    else sem_native_kernel<float><<<(unsigned)blocks, SN_THREADS, (size_t)lds.bytes, st>>>(P);
-    MU_CHECK_LAUNCH();
-    return MU_OK;
+    return with_storage(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        if (lds.bytes > 48 * 1024 && !mu_lds_grant<sem_native_kernel<T>>((int)SN_LDS_BYTES)) return MU_ERR_LAUNCH;
+        sem_native_prepare_kernel<<<mu_grid(n_counts > B ? n_counts : B, 256, 1024), 256, 0, st>>>(offsets, sizes, B, h, w, max_h, max_w, ws.images,
+                                                                                                valid, img_counts, n_counts);
+        MU_CHECK_LAUNCH();
+        sem_native_kernel<T><<<(unsigned)blocks, SN_THREADS, (size_t)lds.bytes, st>>>(P);
+        MU_CHECK_LAUNCH();
+        return MU_OK;
+    });
 }
