@@ -775,6 +775,62 @@ long mu_pil_resize_workspace_bytes(int B, int max_h, int max_w, int Hd, int Wd);
 int mu_pil_resize_u8_nhwc(const unsigned char* src, const long* offsets, const int* sizes, int B, int C, int max_h, int max_w, int swap_rb,
                           void* dst, unsigned char* u8_out, unsigned char* valid, int Hd, int Wd, int Cp, int dtype, void* workspace,
                           long workspace_bytes, void* stream);
+/* f4, the cv2 half for RAGGED batches: the sample preparation of the loaders that read with OpenCV, whose images and maps have sizes of
+ * their own (ade_semantic.py:65-78, ade_panoptic.py:89, city_semantic.py:84-88, city_instance.py:81-106, city_panoptic.py:97-115,
+ * coco_semantic.py:70-84, coco_panoptic.py:70-95).  The three entry points below take a ragged batch exactly as mu_pil_resize_u8_nhwc
+ * does: ONE flat device buffer, offsets int64 [B+1] in BYTES and sizes int32 [B][2] = (h, w) as DEVICE arrays, and from the host only the
+ * bounds max_h, max_w.  The resize rules are those of mu_resize_u8_nhwc / mu_resize_nearest_u8 (one piece of code, csrc/cv2_rule.h), with
+ * the scales derived on the device per image as scale = 1.0 / ((double)Wd / (double)w), two separately rounded fp64 operations, rows
+ * likewise: exact against the restated OpenCV 4.10 rule (oracle/cv2_resize_oracle.py), NOT pinned to bytes of a real cv2 build.
+ * Common to the three: image b is the bytes [offsets[b], offsets[b+1]) of the buffer and is REFUSED (valid[b] = 0, valid is uint8 [B],
+ * none of its bytes read) if h or w lies outside [1, max_h] / [1, max_w], if offsets[b] < 0 or is not a multiple of the element size, or
+ * if offsets[b+1] - offsets[b] < h * w * (bytes per pixel); a refused image does not affect its neighbours.  Every output element is
+ * written on every call.  One launch each, stream-ordered, no atomics, no workspace, no host synchronisation: bit-identical from run to
+ * run and capturable in a graph.  Limits (mu_cv2_ragged_supported, host only: MU_OK or MU_ERR_SHAPE): B >= 1, 1 <= max_h, max_w, Hd, Wd <= 16384,
+ * B * ceil(Hd * Wd / 256) < 2^31.  Refusal order as for the post-processing entry points: a null pointer (optional ones apart), B < 1 or
+ * an unknown dtype / kind or otherwise invalid scalar is MU_ERR_ARG; then a shape outside the limits is MU_ERR_SHAPE; a refused call
+ * enqueues nothing. */
+int mu_cv2_ragged_supported(int B, int max_h, int max_w, int Hd, int Wd);
+/* Images: for every valid image the bytes (u8_out [B][Hd][Wd][C], may be NULL) and dst [B][Hd][Wd][Cp] are exactly what
+ * mu_resize_u8_nhwc(image alone as [1,h,w,C], .., Hd, Wd, Cp, dtype) produces -- the 11-bit fixed-point INTER_LINEAR with the left / right
+ * tap collapse and clamped rows, the `& 0xFF` narrowing, the INTER_AREA shortcut where w == 2 * Wd && h == 2 * Hd (decided per image),
+ * swap_rb != 0 swapping channels 0 and 2 of a 3-channel image, dst = byte / 255 by IEEE division rounded to the storage type, padding
+ * channels +0.  All outputs of a refused image are +0.  C in {1, 3}, Cp % 8 == 0, Cp >= C (else MU_ERR_SHAPE); dtype MU_F32 or MU_F16. */
+int mu_cv2_resize_ragged_u8_nhwc(const unsigned char* src, const long* offsets, const int* sizes, int B, int C, int max_h, int max_w,
+                                 int swap_rb, void* dst, unsigned char* u8_out, unsigned char* valid, int Hd, int Wd, int Cp, int dtype,
+                                 void* stream);
+/* Id maps: dst int64 [B][Hd][Wd] = torch.from_numpy(cv2.resize(map, (Wd, Hd), interpolation=cv2.INTER_NEAREST)).long() with the
+ * Cityscapes clean-ups folded in.  kind names the element of the map: MU_MAP_U8 (IMREAD_GRAYSCALE label maps), MU_MAP_U16 (instanceIds
+ * PNGs under IMREAD_UNCHANGED), MU_MAP_I32 (signed; the maps the COCO loaders build), MU_MAP_RGB8 (three bytes per pixel, value =
+ * byte0 + 256 * byte1 + 65536 * byte2: rgb2id of an RGB image) and MU_MAP_BGR8 (the same with bytes 0 and 2 exchanged: rgb2id of
+ * cv2.imread bytes -- the channel swap is a fifth kind, not a flag).  U16 / I32 elements are little-endian, and src and every
+ * offsets[b] must be multiples of the element size (2 / 4; a misaligned src is MU_ERR_ARG, a misaligned offset refuses that image).
+ *   v = map[min(floor(i * ify), h - 1)][min(floor(j * ifx), w - 1)]           ifx, ify as in mu_resize_nearest_u8
+ *   divisor > 1:    v = floor(v / divisor)     (Python's //: -1 // 1000 = -1; it commutes with the nearest resize, so this is
+ *                                               `instance_mask // 1000` before cv2.resize, city_instance.py:85)
+ *   n_classes > 0:  v = fill unless 0 <= v < n_classes     (np.where((m >= 0) & (m < 19), m, 255), city_semantic.py:84;
+ *                                                           mask[mask >= n] = 255, city_instance.py:106)
+ * Every element of a refused image equals fill.  divisor >= 1 and n_classes >= 0, else MU_ERR_ARG. */
+#define MU_MAP_U8 0
+#define MU_MAP_U16 1
+#define MU_MAP_I32 2
+#define MU_MAP_RGB8 3
+#define MU_MAP_BGR8 4
+int mu_cv2_nearest_ragged(const void* src, const long* offsets, const int* sizes, int kind, int B, int max_h, int max_w, int divisor,
+                          int n_classes, long fill, long* dst, unsigned char* valid, int Hd, int Wd, void* stream);
+/* The COCO panoptic target (coco_panoptic.py:70-95; its semantic half is coco_semantic.py:70-86): png is a ragged batch of 3-byte
+ * pixels; id = rgb2id of the nearest-sampled pixel (byte0 + 256 * byte1 + 65536 * byte2; swap_rb != 0 exchanges bytes 0 and 2:
+ * cv2.imread bytes).  The segments of image b are rows img_seg_offsets[b] .. img_seg_offsets[b+1] (int32 [B+1]) of seg_ids / seg_labels
+ * (int32 [S] each), their ids STRICTLY ASCENDING: the packer keeps the last-listed entry of a duplicated id, as the reference's loop
+ * over segments_info does, and sorts.  If id is among the image's seg_ids: semantic = its label, instance = id; otherwise both are 0,
+ * the reference's zero-initialised maps (an id-0 pixel is 0 / 0 unless id 0 is listed).  Outputs int64 [B][Hd][Wd] each.  An image is
+ * REFUSED also if its table is not strictly ascending, has more than MU_PANOPTIC_SEG_MAX rows (the table is held in LDS: 8 KiB of a
+ * workgroup's default 64 KiB, no grant needed), or its table offsets are out of order or outside [0, S]; then semantic = fill and
+ * instance = 0.  S = 0 is legal (seg_ids / seg_labels may then be NULL); S < 0 is MU_ERR_ARG. */
+#define MU_PANOPTIC_SEG_MAX 1024
+int mu_panoptic_targets(const unsigned char* png, const long* offsets, const int* sizes, const int* seg_ids, const int* seg_labels,
+                        const int* img_seg_offsets, int B, int S, int max_h, int max_w, int swap_rb, long fill, long* semantic,
+                        long* instance, unsigned char* valid, int Hd, int Wd, void* stream);
 /* f2: optim.AdamW step (ade_semantic.py:379,401) for every parameter in one launch.  table: device array of `ntensors` entries
  * {float* p; const float* g; float* m; float* v; long n; long step;} (48 bytes; g may be NULL = no gradient this step; step = that
  * tensor's own count of attempted updates including this one, torch keeps one counter per parameter); block_tensor/block_chunk:

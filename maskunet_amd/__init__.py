@@ -17,6 +17,8 @@ from .rle import RLEs, decode_rle, encode_rle, rle_counts_from_string, rle_strin
 from .coco import CocoMasks, coco_masks
 from .images import PackedImages, pack_images, resize_pil_to_nhwc
 from .ops import resize_labels_u8, resize_u8_to_nhwc
+from .targets import (PackedMaps, PanopticTargets, pack_maps, pack_segments, panoptic_targets, resize_cv2_to_nhwc,
+                      resize_labels_cv2)
 from .optim import FusedAdamW
 from .graph import GraphedStep
 from ._lib import get_float32_matmul_precision, set_float32_matmul_precision
@@ -29,5 +31,6 @@ __all__ = ["ConvBlock", "DownSample", "UpSample", "Mask2FormerAttention", "UNet"
            "InstanceAP", "PanopticQuality", "RLEs", "encode_rle", "decode_rle", "rle_counts_from_string", "rle_string_from_counts",
            "coco_masks", "CocoMasks", "instances_from_id_map", "semantic_eval", "SemanticBatch", "SemanticMetrics",
            "metrics_from_counts", "resize_pil_to_nhwc", "pack_images", "PackedImages", "coco_match", "CocoMatches", "CocoEval",
-           "semantic_eval_native", "SemanticNativeBatch", "Panoptic", "panoptic_segments", "predict_panoptic"]
+           "semantic_eval_native", "SemanticNativeBatch", "Panoptic", "panoptic_segments", "predict_panoptic",
+           "PackedMaps", "PanopticTargets", "pack_maps", "pack_segments", "panoptic_targets", "resize_cv2_to_nhwc", "resize_labels_cv2"]
 __version__ = "0.1.0"

@@ -18,6 +18,8 @@ LIB_PATH = os.environ.get("MU_LIB_PATH") or os.path.join(_HERE, "libmaskunet_hip
 MU_F32, MU_F16, MU_F32X = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
 MU_IDMAP_I32, MU_IDMAP_I64, MU_IDMAP_RGB8 = 0, 1, 2
+MU_MAP_U8, MU_MAP_U16, MU_MAP_I32, MU_MAP_RGB8, MU_MAP_BGR8 = 0, 1, 2, 3, 4
+MU_PANOPTIC_SEG_MAX = 1024
 _ERR = {-1: "MU_ERR_ARG", -2: "MU_ERR_SHAPE", -3: "MU_ERR_LAUNCH", -4: "MU_ERR_WORKSPACE"}
 
 # name -> (restype, argtypes); must list EVERY symbol of include/maskunet_hip.h (tests/test_abi.py checks)
@@ -147,6 +149,10 @@ SIGNATURES = {
     "mu_resize_nearest_u8": (I, [P, I, I, I, P, I, I, P]),
     "mu_pil_resize_workspace_bytes": (L, [I, I, I, I, I]),
     "mu_pil_resize_u8_nhwc": (I, [P, P, P, I, I, I, I, I, P, P, P, I, I, I, I, P, L, P]),
+    "mu_cv2_ragged_supported": (I, [I, I, I, I, I]),
+    "mu_cv2_resize_ragged_u8_nhwc": (I, [P, P, P, I, I, I, I, I, P, P, P, I, I, I, I, P]),
+    "mu_cv2_nearest_ragged": (I, [P, P, P, I, I, I, I, I, I, L, P, P, I, I, P]),
+    "mu_panoptic_targets": (I, [P, P, P, P, P, P, I, I, I, I, I, L, P, P, P, I, I, P]),
     "mu_conv_fwd_fused": (I, [P, P, P, P, P, I, P, I, I, I, I, I, I, L, L, I, P]),
     "mu_bn_eval_fold": (I, [P, P, P, P, F, P, P, P, P, F, P, P, P, I, I, P]),
     "mu_attn_bwd_phases": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, L, I, I, P]),

@@ -3,6 +3,7 @@
 // nn.MaxPool2d(2) (:216), nn.Upsample(bilinear, align_corners=True) + torch.cat (:235,250-253),
 // nn.Dropout(0.3) (:273,304,307), and the OIHW<->tap-major weight re-layouts of this build.
 #include "common.h"
+#include "cv2_rule.h"
 // Operands a kernel reads exactly once are loaded nontemporally (`load_nt`: past the CU's L1, L2-served): see the head of norm.hip.
 #include "../../include/maskunet_hip.h"
 
@@ -1187,22 +1188,7 @@ extern "C" int mu_prep_qkv(const float* wq, const float* wk, const float* wv, co
 // The resized bytes are produced bit-exactly (u8_out, optional) and leave as [0,1] activations in the NHWC compute layout
 // (x / 255, channel-padded with zeros), optionally with channels 0 and 2 swapped (BGR -> RGB).
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void cv_lin_coef(int d, double scale, int sn, bool clamp_taps, int& s, int& c0, int& c1) {
-    // two separately rounded double operations, as the host code this restates runs them: no fused multiply-add contraction (HIP's
-    // __dmul_rn / __dadd_rn are plain operators and would contract)
-#pragma clang fp contract(off)
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    int si = (int)floorf(f);
-    f -= (float)si;
-    if (clamp_taps) {
-        if (si < 0) { f = 0.f; si = 0; }
-        if (si + 1 >= sn) { f = 0.f; si = sn - 1; }
-    }
-    s = si;
-    c0 = __float2int_rn((1.0f - f) * 2048.0f);               // cvRound: round half to even
-    c1 = __float2int_rn(f * 2048.0f);
-}
-
+// cv_scale, cv_lin_coef and cv_nearest_index live in cv2_rule.h, shared with the ragged kernels of cv2_ragged.hip
 template <typename T>
 __global__ __launch_bounds__(256) void resize_linear_u8_kernel(const uint8_t* __restrict__ src, int B, int Hs, int Ws, int C, int swap_rb,
                                                                double scale_x, double scale_y, T* __restrict__ dst, uint8_t* __restrict__ u8_out,
@@ -1248,7 +1234,7 @@ extern "C" int mu_resize_u8_nhwc(const unsigned char* src, int B, int Hs, int Ws
     if (!src || !dst || B <= 0 || Hs <= 0 || Ws <= 0 || Hd <= 0 || Wd <= 0) return MU_ERR_ARG;
     if (C <= 0 || C > 4 || Cp < C || Cp % 8) return MU_ERR_SHAPE;
     // exactly what cv::resize derives from dsize: inv_scale = dsize / ssize, scale = 1 / inv_scale (doubles)
-    const double scale_x = 1.0 / ((double)Wd / (double)Ws), scale_y = 1.0 / ((double)Hd / (double)Hs);
+    const double scale_x = cv_scale(Wd, Ws), scale_y = cv_scale(Hd, Hs);
     hipStream_t st = (hipStream_t)stream;
     const int grid = mu_grid((long)B * Hd * Wd, 256, 8192);
     return with_storage(dtype, [&](auto tag) -> int {
@@ -1265,16 +1251,14 @@ __global__ __launch_bounds__(256) void resize_nearest_u8_kernel(const uint8_t* _
     const long total = (long)B * Hd * Wd;
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         const int dx = (int)(idx % Wd), dy = (int)((idx / Wd) % Hd), b = (int)(idx / ((long)Wd * Hd));
-        int sx = (int)floor((double)dx * ifx), sy = (int)floor((double)dy * ify);
-        sx = sx < Ws - 1 ? sx : Ws - 1;
-        sy = sy < Hs - 1 ? sy : Hs - 1;
+        const int sx = cv_nearest_index(dx, ifx, Ws), sy = cv_nearest_index(dy, ify, Hs);
         dst[idx] = (long)src[((long)b * Hs + sy) * Ws + sx];
     }
 }
 
 extern "C" int mu_resize_nearest_u8(const unsigned char* src, int B, int Hs, int Ws, long* dst, int Hd, int Wd, void* stream) {
     if (!src || !dst || B <= 0 || Hs <= 0 || Ws <= 0 || Hd <= 0 || Wd <= 0) return MU_ERR_ARG;
-    const double ifx = 1.0 / ((double)Wd / (double)Ws), ify = 1.0 / ((double)Hd / (double)Hs);
+    const double ifx = cv_scale(Wd, Ws), ify = cv_scale(Hd, Hs);
     resize_nearest_u8_kernel<<<mu_grid((long)B * Hd * Wd, 256, 8192), 256, 0, (hipStream_t)stream>>>(src, B, Hs, Ws, ifx, ify, dst, Hd, Wd);
     MU_CHECK_LAUNCH();
     return MU_OK;

@@ -395,7 +395,9 @@ class UNet(_HipModule):
         4.10 8-bit algorithm (11-bit fixed-point coefficients, 2x2 area shortcut; its CPU restatement lives with the test
         infrastructure) -- exact against that restatement, NOT pinned to bytes produced by a real cv2 build (cv2 is not installed here and not vendored by the reference:
         SURVEY 8-f4 stays "partial" for this half).  ToTensor's division by 255 is exact.  Images that already have the network's size
-        skip the resize (cv2.resize to the same size is the identity).
+        skip the resize (cv2.resize to the same size is the identity).  ``images_u8_hwc`` may also be a list of device images of
+        different sizes, [h, w, 3] each, or a ``PackedImages`` (the ADE20K and COCO loaders): the same rule per image in one launch
+        (targets.resize_cv2_to_nhwc); a uniform tensor takes the path it always took.
 
         ``resample="pil"`` stands in for the COCO instance loader instead, ``forward(ToTensor(Resize((hw, hw))(ToPILImage(img))))``
         (coco_instance.py:43-47,68): Pillow's antialiased bilinear resize, pinned to Pillow's own bytes (images.resize_pil_to_nhwc).
@@ -414,6 +416,19 @@ class UNet(_HipModule):
             return self._finish(self.forward_nhwc(x))
         if resample != "cv2":
             raise ValueError(f'resample must be "cv2" or "pil", got {resample!r}')
+        from . import images as _images
+        if isinstance(images_u8_hwc, (list, tuple, _images.PackedImages)):
+            # a ragged batch, [h, w, 3] device images of sizes of their own (the ADE20K and COCO loaders): one launch of the same rule
+            # (targets.resize_cv2_to_nhwc); check=True raises for an image that kernel refuses, as above
+            from . import targets as _targets
+            packed = images_u8_hwc if isinstance(images_u8_hwc, _images.PackedImages) else _images.pack_images(images_u8_hwc)
+            self._check_device(packed.data)
+            H, W = int(self.norm.normalized_shape[1]), int(self.norm.normalized_shape[2])
+            x, valid = _targets.resize_cv2_to_nhwc(packed, (W, H), self.compute_dtype, bgr=bgr)
+            if check and not bool(valid.all()):
+                raise RuntimeError(f"maskunet_amd: the cv2 resize refused images {(valid == 0).nonzero().flatten().tolist()} (size or bytes "
+                                   "outside the contract)")
+            return self._finish(self.forward_nhwc(x))
         self._check_device(images_u8_hwc)
         H, W = int(self.norm.normalized_shape[1]), int(self.norm.normalized_shape[2])
         if tuple(images_u8_hwc.shape[1:3]) == (H, W) and not bgr:
